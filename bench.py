@@ -10,7 +10,10 @@ Multi-GPU (--gpus N, launched by torch.distributed.run): the adaptive rule needs
 after every probe, so it does not shard by list; every rank holds a replica of the
 index and searches its own 5000 queries -- weak scaling, no data-path collective.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline; --full adds
+everything else the line can hold (the untimed legs, the CPU baseline and the parity check against the compiled reference,
+BASELINE configs 1, 3, 5, the guaranteed-bound workload and, at N > 1, the list-id shards).  --dump-outputs DIR writes what the
+last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -66,6 +69,16 @@ def kfd_gpu_count():
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array; float32 stays float32, everything else (ids, probe counts) becomes float64,
+    which holds them exactly"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        np.save(os.path.join(dirname, name + ".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+    log(f"outputs of the last timed step: {', '.join(sorted(arrays))} in {dirname}")
 
 
 def gen_data(torch, dev, nb, nq, d, nblobs, sigma, seed):
@@ -281,6 +294,8 @@ def run_shards(args, torch, dist, capi, rank, world, local, dev, red_dev):
     barrier()
     elapsed = time.perf_counter() - t0
     h.set_async_depth(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"distances": out[0], "ids": out[1]})  # (the merged tables of the last step)
     if world > 1:
         t = torch.tensor([elapsed], device=red_dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -466,7 +481,17 @@ def main():
     ap.add_argument("--in-flight", type=int, default=6,
                     help="batches kept in flight per GPU, each from its own host thread on its own search context "
                          "(amd_ivf_clone); 1 = one batch at a time")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline, after it: the untimed legs, the CPU baseline and the parity check against the "
+                         "compiled reference, BASELINE configs 1, 3, 5, the guaranteed-bound workload and, at N > 1, the list-id shards "
+                         "(--no-cpu, --no-legs, --no-other and --no-ref leave parts out).  Without it a run sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: distances, ids and, in the adaptive "
+                         "mode, the probe count of every query) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_legs = args.no_cpu = True  # (a plain run: nothing after the clock but the line and the outputs)
     # --gpus N > 1 without a launcher: start the N ranks ourselves, exactly as the driver would (one process per GPU, RCCL),
     # BEFORE anything in this process touches the GPU (the parent only counts devices, which does not initialise HIP), wait for
     # them and leave with their exit code.  A run that was asked for N GPUs never degrades to fewer silently: too few visible
@@ -708,7 +733,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def account(acc, tm, hinted, short, redone, res, det=None):
+    def account(acc, tm, hinted, short, redone, res, sn, det=None):
         if det:  # per phase: (ms by HIP events on the phase's own stream, launches); bytes the dense / threshold rounds had to move
             ph = acc.setdefault("phases", {})
             for key, val in det.items():
@@ -723,7 +748,8 @@ def main():
         for key in ("scan_ms", "scan_bytes", "scan_launches", "coarse_ms", "select_ms", "scan_min_bytes"):
             acc[key] = acc.get(key, 0.0) + tm[key]
         acc["slot_eff"] = acc.get("slot_eff", 0.0) + tm["slot_efficiency"]
-        acc["last"] = res
+        if sn >= acc.get("last_step", -1):  # (the highest-numbered step, whichever thread finished last)
+            acc["last"], acc["last_step"] = res, sn
 
     def run_steps_async(nsteps, acc, keep=None):
         """one caller thread keeps up to nfl steps in flight: submit step s, and once nfl are out wait for the oldest first.
@@ -739,7 +765,7 @@ def main():
                 log(f"async step done at {1e3 * (time.perf_counter() - t_async0):.2f} ms: engine wall {tm['total_ms']:.2f} ms")
             if kept_bufs is not None:
                 keep.note(sn, start, buf, np_)
-            account(acc, tm, dg["hinted_launches"], dg["short_hints"], dg["tie_redone"], (D, I, np_, start))
+            account(acc, tm, dg["hinted_launches"], dg["short_hints"], dg["tie_redone"], (D, I, np_, start), sn)
 
         aslots = len(async_outs)
         t_async0 = time.perf_counter()
@@ -775,7 +801,7 @@ def main():
                     hints = ctxs[j].last_round_hints()
                     det = ctxs[j].last_timing_detail()
                     with lock:
-                        account(acc, tm, hints[0], hints[1], ctxs[j].last_tie_redone(), res, det)
+                        account(acc, tm, hints[0], hints[1], ctxs[j].last_tie_redone(), res, sn, det)
             except Exception as e:  # noqa: BLE001
                 errs.append(e)
 
@@ -821,6 +847,8 @@ def main():
     D, I, my_np, q_start = acc["last"]
     D, I, my_np = D.copy(), I.copy(), my_np.copy()  # (the result buffers are reused by the legs below)
     my_sl = my_np[q_start:q_start + ses]  # my_nprobe of the slice the last timed step searched
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"distances": D, "ids": I, "nprobe": my_sl})
     gt_sl = gtD[q_start:q_start + ses]
     skip_legs = set(filter(None, os.environ.get("AUNCEL_BENCH_SKIP_LEGS", "").split(",")))  # (diagnosis: one_batch, fp32, exact_ties)
     def timed_leg(nsteps):
@@ -1123,7 +1151,8 @@ def main():
             "achieved": (bytes_per_launch / 1e9) / (a_ms / a_l / 1e3) if a_ms > 0 else None,
             "peak": 8000.0,
             "unit": "GB/s",
-            "measured": "one batch at a time, same run, after the timed region" if solo else "timed region (one batch at a time)",
+            "measured": "one batch at a time, same run, after the timed region" if solo else "timed region (one batch at a time)" if nfl == 1
+                        else f"timed region ({nfl} batches in flight: --full measures one batch at a time)",
             "traffic": traffic,
             "traffic_source": traffic_source if traffic is not None else "none committed for this workload: achieved uses min_bytes_per_launch",
             "min_bytes_per_launch": alone["scan_min_bytes"] / a_l,
@@ -1407,7 +1436,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             log("guaranteed_bound_workload failed:", repr(e))
             out["guaranteed_bound_workload"] = {"error": repr(e)}
-    if world > 1:
+    if world > 1 and args.full:
         # north_star's split next to the replicas: the inverted lists sharded by list id over the same N GPUs (BASELINE config 4,
         # Auncel/IndexShards.cpp:261-311), fixed nprobe, run after the replica timing; one driver command records both
         while len(ctxs) > 1:  # (the search contexts go before the index they were cloned from)

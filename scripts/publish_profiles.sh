@@ -1,11 +1,12 @@
 #!/bin/bash
 # copy what scripts/refresh_round.sh brought back under gpurun_out/ into the tracked profiles/ directory
 tag=${1:-r06}
+res=${RESULTS_DIR:-results}  # where refresh_round.sh put the two full bench lines
 cp gpurun_out/summary_$tag/${tag}_summary.md gpurun_out/summary_$tag/${tag}_pmc.json gpurun_out/summary_$tag/${tag}_kernel_stats.csv profiles/
 cp gpurun_out/summary_$tag/${tag}_pmc_cfg5.json gpurun_out/summary_$tag/${tag}_pmc_cfg3.json profiles/ 2>/dev/null
-cp gpurun_out/bench_$tag.json profiles/${tag}_bench_line.json
+cp "$res/bench_$tag.json" profiles/${tag}_bench_line.json
 cp gpurun_out/configs_$tag.jsonl profiles/${tag}_other_configs.jsonl
-cp gpurun_out/shards_$tag.json profiles/${tag}_shards_one_gpu.json
+cp "$res/shards_$tag.json" profiles/${tag}_shards_one_gpu.json
 cp gpurun_out/effect_time_$tag.jsonl profiles/${tag}_effect_time.jsonl
 cp gpurun_out/latency1_$tag.txt profiles/${tag}_latency_batch1.txt
 cp gpurun_out/gpu_tests_$tag.txt profiles/${tag}_gpu_tests.txt

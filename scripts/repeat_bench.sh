@@ -4,9 +4,9 @@
 tag=${1:-r06}; n=${2:-10}
 out=gpurun_out/bench_lines_repeat_$tag.jsonl
 : > $out
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 >> $out
+python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 >> $out
 for i in $(seq 2 $n); do
-  AUNCEL_BENCH_SKIP_LEGS=one_batch,fp32,id_ties,latency1 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-other 2>/dev/null | tail -1 >> $out
+  AUNCEL_BENCH_SKIP_LEGS=one_batch,fp32,id_ties,latency1 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-other 2>/dev/null | tail -1 >> $out
 done
 python - <<PY
 import json, statistics

@@ -75,7 +75,7 @@ def test_default_mode_two_ranks_records_both_splits(tmp_path):
     """the command the driver issues for N > 1 (no --mode): replicas of the adaptive search, and behind them the list-id shards of
     north_star / BASELINE config 4 as a `shards` block of the same line; query slices rotate; real-data files are taken when given"""
     small = ["--nb", "200000", "--nlist", "1024", "--train", "500", "--test", "500", "--blobs", "500", "--steps", "4", "--warmup", "1",
-             "--no-cpu", "--no-legs", "--kmeans", "torch", "--in-flight", "2"]
+             "--no-cpu", "--no-legs", "--kmeans", "torch", "--in-flight", "2", "--full"]  # (--full: the shards block)
     port = 29900 + os.getpid() % 90
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(port), "bench.py", "--gpus", "2"] + small, {"BENCH_DIST_BACKEND": "gloo", "BENCH_DEVICE": "0"})
@@ -113,3 +113,21 @@ def test_bench_takes_real_data_files(tmp_path):
     assert j["data"].startswith("real: sift_base.u8bin") and j["dtype"] == "u8"
     assert j["config"]["nb"] == 60000 and j["config"]["query_slices"] == 2
     assert j["config"]["ground_truth_file"]["agrees_with_brute_force"] is True
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_timed_step(tmp_path):
+    """a plain run (no --full) prints the headline alone; --dump-outputs writes what the last timed step returned, and two runs
+    with the same arguments write the same bytes"""
+    import numpy as np
+    small = ["--nb", "200000", "--nlist", "1024", "--train", "500", "--test", "500", "--blobs", "500", "--steps", "3", "--warmup", "1",
+             "--kmeans", "torch", "--in-flight", "2"]
+    runs = [_run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / str(i))] + small, {}) for i in range(2)]
+    for j in runs:
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["dtype"] == "u8"
+        assert not {"cpu_baseline", "fp32_path", "one_batch_at_a_time", "fixed_nprobe_32", "other_configs"} & set(j)
+    for name, dtype, shape in (("distances", np.float32, (500, 100)), ("ids", np.float64, (500, 100)), ("nprobe", np.float64, (500,))):
+        a, b = (np.load(tmp_path / str(i) / (name + ".npy")) for i in range(2))
+        assert a.dtype == dtype and a.shape == shape and np.array_equal(a, b), name
+    ids = np.load(tmp_path / "0" / "ids.npy")
+    assert ((ids >= -1) & (ids < 200000) & (ids == np.floor(ids))).all()  # (-1: fewer than 100 vectors probed)
