@@ -4763,6 +4763,11 @@ int amd_ivf_kmeans(int d, size_t n, const float* x_in, size_t k, int metric, int
     namespace km = amdivf_kmeans;
     if (d <= 0 || k == 0) throw EngineError("bad dimension / k");
     if (n < k) throw EngineError("Number of training points should be at least as large as number of clusters");
+    // the reference checks the whole input before sub-sampling (Clustering.cpp:85-89); nothing has touched the device yet
+    for (size_t i = 0; i < n * (size_t)d; i++)
+        if (!std::isfinite(x_in[i])) throw EngineError("input contains NaN's or Inf's");
+    // (the reference would sub-sample to no point at all and read its permutation out of range)
+    if (max_points_per_centroid == 0) throw EngineError("max_points_per_centroid must be positive");
     const float* x = x_in;
     std::vector<float> sub;
     size_t nx = n;
@@ -4802,13 +4807,13 @@ int amd_ivf_kmeans(int d, size_t n, const float* x_in, size_t k, int metric, int
     keys_out.ensure(nx * 4);
     idx_in.ensure(nx * 4);
     idx_out.ensure(nx * 4);
-    counts.ensure(k * 4);
+    counts.ensure((k + 1) * 4);  // (+ the flag of an assignment outside [0, k): launch_kmeans_group)
     seg.ensure((k + 1) * 4);
     const size_t temp_bytes = kmeans_sort_temp_bytes(nx);
     temp.ensure(std::max<size_t>(temp_bytes, 16));
     d_cen.ensure(k * (size_t)d * 4);
     std::vector<float> dis(nx);
-    std::vector<uint32_t> cnt(k), off(k + 1);
+    std::vector<uint32_t> cnt(k + 1), off(k + 1);
     std::vector<size_t> hassign(k);
     for (int it = 0; it < niter; it++) {
         if (amd_ivf_set_centroids(h.get(), centroids)) throw EngineError(g_last_error);
@@ -4817,8 +4822,9 @@ int amd_ivf_kmeans(int d, size_t n, const float* x_in, size_t k, int metric, int
         HIP_CHECK(hipMemcpyAsync(dis.data(), d_dis.p, nx * 4, hipMemcpyDeviceToHost, s));
         launch_kmeans_group(d_keys.as<int64_t>(), nx, (uint32_t)k, keys_in.as<uint32_t>(), keys_out.as<uint32_t>(), idx_in.as<uint32_t>(),
                             idx_out.as<uint32_t>(), counts.as<uint32_t>(), temp.p, temp_bytes, s);
-        HIP_CHECK(hipMemcpyAsync(cnt.data(), counts.p, k * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(cnt.data(), counts.p, (k + 1) * 4, hipMemcpyDeviceToHost, s));
         HIP_CHECK(stream_sync(s));
+        if (cnt[k]) throw EngineError("k-means: the assignment step returned a centroid number outside [0, k)");
         float err = 0;  // the reference's running fp32 sum, in point order
         for (size_t j = 0; j < nx; j++) err += dis[j];
         if (obj) obj[it] = err;

@@ -603,7 +603,8 @@ void launch_scatter_rows(const void* in, const uint32_t* idx, uint32_t m, uint32
 // packed upper triangle (IVF_pro.cpp:21-39 layout) of a full nlist x nlist distance matrix
 void launch_pack_upper(const float* full, uint32_t nlist, float* out, hipStream_t s);
 
-// k-means centroid update (ivf_kmeans.hip): points grouped by centroid with a stable sort, then fp32 sums in point order
+// k-means centroid update (ivf_kmeans.hip): points grouped by centroid with a stable sort, then fp32 sums in point order.
+// counts: k + 1 entries, points per centroid and, in counts[k], a flag raised by any assignment outside [0, k)
 size_t kmeans_sort_temp_bytes(size_t n);
 void launch_kmeans_group(const int64_t* assign, size_t n, uint32_t k, uint32_t* keys_in, uint32_t* keys_out, uint32_t* idx_in,
                          uint32_t* idx_out, uint32_t* counts, void* temp, size_t temp_bytes, hipStream_t s);

@@ -9,13 +9,20 @@
 
 namespace amdivf {
 
-__global__ __launch_bounds__(256) void kmeans_keys_kernel(const int64_t* assign, size_t n, uint32_t* keys, uint32_t* idx, uint32_t* counts) {
+// counts: k + 1 entries; counts[k] is raised when an assignment is not a centroid number (a -1 or garbage key from the
+// assignment step), which is then left uncounted -- the host turns the flag into an error before the sums run
+__global__ __launch_bounds__(256) void kmeans_keys_kernel(const int64_t* assign, size_t n, uint32_t k, uint32_t* keys, uint32_t* idx,
+                                                          uint32_t* counts) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const uint32_t c = (uint32_t)assign[i];
+    const int64_t a = assign[i];
+    const uint32_t c = a >= 0 && a < (int64_t)k ? (uint32_t)a : k;
     keys[i] = c;
     idx[i] = (uint32_t)i;
-    atomicAdd(&counts[c], 1u);
+    if (c < k)
+        atomicAdd(&counts[c], 1u);
+    else
+        atomicOr(&counts[k], 1u);
 }
 
 __global__ __launch_bounds__(64) void kmeans_sums_kernel(const float* x, size_t stride, int d, const uint32_t* idx, const uint32_t* seg_off,
@@ -39,8 +46,8 @@ size_t kmeans_sort_temp_bytes(size_t n) {
 
 void launch_kmeans_group(const int64_t* assign, size_t n, uint32_t k, uint32_t* keys_in, uint32_t* keys_out, uint32_t* idx_in,
                          uint32_t* idx_out, uint32_t* counts, void* temp, size_t temp_bytes, hipStream_t s) {
-    (void)hipMemsetAsync(counts, 0, (size_t)k * 4, s);
-    LAUNCH(kmeans_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, assign, n, keys_in, idx_in, counts);
+    (void)hipMemsetAsync(counts, 0, ((size_t)k + 1) * 4, s);
+    LAUNCH(kmeans_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, assign, n, k, keys_in, idx_in, counts);
     int bits = 1;
     while ((1ull << bits) < k) bits++;
     (void)hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, idx_in, idx_out, (int)n, 0, bits, s);

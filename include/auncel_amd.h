@@ -224,7 +224,12 @@ int amd_ivf_merge_tables(int metric, size_t n, size_t k, size_t nshard, const fl
  * 1 |x|^2+|y|^2-2xy on the matrix cores, -1 the reference's switch), objective, km_update_centroids (utils.cpp:1078-1159)
  * in its fp32 summation order, void-cluster splitting }, spherical / int_centroids post-processing.  nredo 1, no input
  * centroids.  centroids: k x d out; obj: niter objective values out (may be NULL).  With coarse_mode 0 the centroids
- * equal the reference's bit for bit wherever its BLAS assignment picks the same centroids (tests/golden/kmeans_*). */
+ * equal the reference's bit for bit wherever its BLAS assignment picks the same centroids (tests/golden/kmeans_*).
+ * Before anything reaches the device, returns -2 (as the reference throws) when n < k, when x (all n rows, before
+ * sub-sampling) holds a NaN or an Inf ("input contains NaN's or Inf's"), or when max_points_per_centroid is 0; -2 also
+ * when an assignment step yields a centroid number outside [0, k), which is then never used as an index.  When the
+ * training set (after sub-sampling) has exactly k points, the centroids are the first k rows of x -- the reference's
+ * corner case, even where sub-sampling chose other rows -- and obj is not written. */
 int amd_ivf_kmeans(int d, size_t n, const float* x, size_t k, int metric, int niter, long seed, size_t max_points_per_centroid,
                    int spherical, int int_centroids, int coarse_mode, int device, float* centroids, float* obj);
 

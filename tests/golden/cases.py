@@ -152,6 +152,20 @@ def kmeans_sub_int():
     return _kmeans(xb, 24, 8, max_pts=100)
 
 
+def kmeans_sub_int_d100():
+    # d = 100 (two blocks of 64 dimensions, not a multiple of 64), k = 300 past coarse_pick's lower bound, sub-sampled;
+    # integer data with more tight blobs than clusters: the reference's BLAS assignment picks the exact kernel's centroids
+    # in every iteration (with fewer blobs than clusters, split blobs make near-ties on which the two disagree)
+    xb, _ = synth.sift_like(20000, 1, d=100, nblobs=600, sigma=4.0, seed=45)
+    return _kmeans(xb, 300, 6, max_pts=40)
+
+
+def kmeans_ip_spherical_d96():
+    # IP + spherical at d = 96, sub-sampled, more blobs than clusters (the BLAS and exact rankings agree on the best centroid)
+    xb, _ = synth.deep_like(6000, 1, d=96, nblobs=200, sigma=0.1, seed=46)
+    return _kmeans(xb, 100, 5, metric=METRIC_IP, spherical=1, max_pts=50)
+
+
 def io_ragged():
     c = fixed_ragged()
     c["kind"] = "io"
@@ -166,7 +180,8 @@ def io_sift():
 
 
 CASES = {f.__name__: f for f in [io_ragged, io_sift, fixed_sift_l2, fixed_gauss_l2_d96, fixed_deep_ip_d96, fixed_gist_l2_d960,
-                                  fixed_odd_d30, fixed_ragged, fixed_dups, auncel_sift_d32, auncel_gauss_d64, auncel_deep_ip_d64, auncel_sift_nl4096, kmeans_toy, kmeans_void, kmeans_toy_ip, kmeans_sub_int]}
+                                  fixed_odd_d30, fixed_ragged, fixed_dups, auncel_sift_d32, auncel_gauss_d64, auncel_deep_ip_d64, auncel_sift_nl4096, kmeans_toy, kmeans_void, kmeans_toy_ip, kmeans_sub_int,
+                                  kmeans_sub_int_d100, kmeans_ip_spherical_d96]}
 
 
 def input_sha(case):

@@ -49,6 +49,33 @@ def test_no_cpu_fallback(capi):
     assert e.value.code == -4
 
 
+@pytest.mark.parametrize("what", ["nan", "inf", "nan_beyond_sample", "max_points_0"])
+def test_kmeans_rejects_bad_input_before_the_device(capi, what):
+    """amd_ivf_kmeans refuses what the reference's Clustering::train throws on (Clustering.cpp:85-89: NaN / Inf anywhere in
+    the input, before sub-sampling) and a max_points_per_centroid of 0 (nothing to sample), before it touches a device: an
+    EngineError (-2) with or without a GPU, never the -4 of a missing device"""
+    rs = np.random.RandomState(7)
+    x = rs.randn(600, 8).astype(np.float32)
+    k, max_pts = 4, 256
+    if what == "nan":
+        x[123, 5] = np.nan
+    elif what == "inf":
+        x[0, 0] = np.inf
+    elif what == "nan_beyond_sample":
+        # 600 points > k * max_pts = 400: sub-sampling keeps 400 rows, the check still covers all 600
+        max_pts = 100
+        x[599, 7] = -np.inf
+    else:
+        max_pts = 0
+    with pytest.raises(capi.EngineError) as e:
+        capi.kmeans(capi.METRIC_L2, x, k, niter=2, max_points_per_centroid=max_pts, coarse_mode=0, device=0)
+    assert e.value.code == -2
+    if what != "max_points_0":
+        assert "input contains NaN's or Inf's" in str(e.value)
+    else:
+        assert "max_points_per_centroid" in str(e.value)
+
+
 @pytest.mark.parametrize("name", [n for n in FIXED if n not in ("fixed_gist_l2_d960", "fixed_odd_d30")])
 def test_merge_tables_host(capi, oracle, name):
     case, gold = load_case(name)
