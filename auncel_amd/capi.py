@@ -30,6 +30,7 @@ SYMBOLS = [
     "amd_ivf_kmeans",
     "amd_ivf_range_search_preassigned", "amd_ivf_range_search", "amd_ivf_range_results",
     "amd_ivf_scan_arith",
+    "amd_ivf_update_lists", "amd_ivf_remove_ids", "amd_ivf_last_update", "amd_ivf_layout_digest",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -297,6 +298,36 @@ class Handle:
         ids = np.empty(n, np.int64)
         _chk(lib().amd_ivf_get_list(self._h, C.c_size_t(l), _f(codes), _i(ids)))
         return codes, ids
+
+    # ---- changes in place (include/auncel_amd.h: amd_ivf_update_lists ...)
+    def update_lists(self, sizes, where, ids, codes):
+        """new list sizes + written entries: where[i] = list << 32 | offset, ids[i], codes[i] (d floats)"""
+        sizes = np.ascontiguousarray(sizes, dtype=np.uintp)
+        assert sizes.shape == (self.nlist,)
+        where = np.ascontiguousarray(where, dtype=np.uint64)
+        ids, codes = i64(ids), f32(codes).reshape(-1, self.d)
+        assert where.shape[0] == ids.shape[0] == codes.shape[0]
+        _chk(lib().amd_ivf_update_lists(self._h, sizes.ctypes.data_as(_szp), C.c_size_t(where.shape[0]), where.ctypes.data_as(_u64p),
+                                        _i(ids), _f(codes)))
+
+    def remove_ids(self, ids):
+        """IndexIVF::remove_ids with an IDSelectorBatch of `ids`; returns how many entries went"""
+        ids = i64(ids)
+        n = C.c_size_t(0)
+        _chk(lib().amd_ivf_remove_ids(self._h, C.c_size_t(ids.shape[0]), _i(ids), C.byref(n)))
+        return n.value
+
+    def last_update(self):
+        """(0 none / 1 incremental / 2 full, host-to-device bytes, entries written, blocks re-encoded) of the last refresh"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_last_update(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def layout_digest(self):
+        """digests of the device layout: offsets, rows, ids, byte fragments, fp16 copy, fp32 copy, lane copy, flags"""
+        out = (C.c_uint64 * 8)()
+        _chk(lib().amd_ivf_layout_digest(self._h, out))
+        return tuple(int(v) for v in out)
 
     # ---- search
     def coarse(self, x, nprobe, mode=0):

@@ -107,6 +107,9 @@ struct IndexIVF : Index, Level1Quantizer {
     void copy_subset_to(IndexIVF& other, int subset_type, idx_t a1, idx_t a2) const;
 
     size_t get_list_size(size_t list_no) const { return invlists->list_size(list_no); }
+    /// IndexIVF.cpp:1015-1040: `other`'s lists appended to this index's (ids + add_id); `other` is left empty
+    virtual void check_compatible_for_merge(const IndexIVF& other) const;
+    virtual void merge_from(IndexIVF& other, idx_t add_id);
     void replace_invlists(InvertedLists* il, bool own = false);
 
     /// the engine handle (created lazily; contents refreshed when centroids / lists / traces changed)

@@ -14,6 +14,9 @@ struct IndexIVFFlat : IndexIVF {
     virtual void add_core(idx_t n, const float* x, const long* xids, const long* precomputed_idx);
     void add_with_ids(idx_t n, const float* x, const long* xids) override;
     void reconstruct_from_offset(idx_t list_no, idx_t offset, float* recons) const override;  ///< IndexIVFFlat.cpp:226-230
+    /// IndexIVFFlat.cpp:190-224: vectors with ids new_ids[i] (< ntotal, direct map on) replaced by x[i]: the old entry leaves its
+    /// list (the list's last entry takes its place), the new one is appended to the list of its nearest centroid
+    virtual void update_vectors(int nv, idx_t* new_ids, const float* x);
 };
 
 /// faiss::IndexIVFFlatDedup (Auncel/IndexIVFFlat.h:62-107): equal vectors are stored once; `instances` maps the id that
@@ -33,6 +36,7 @@ struct IndexIVFFlatDedup : IndexIVFFlat {
     void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result) const override;
     void reconstruct_from_offset(idx_t list_no, idx_t offset, float* recons) const override;
     long remove_ids(const IDSelector& sel) override;  ///< IndexIVFFlat.cpp:381-448
+    void update_vectors(int nv, idx_t* new_ids, const float* x) override;  ///< "not implemented", as the reference's
 
    private:
     void expand_instances(idx_t n, idx_t k, float* distances, idx_t* labels) const;

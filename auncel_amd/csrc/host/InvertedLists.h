@@ -30,11 +30,43 @@ struct InvertedLists {
     virtual void update_entry(size_t list_no, size_t offset, idx_t id, const uint8_t* code) { update_entries(list_no, offset, 1, &id, code); }
     virtual void reset() {
         for (size_t i = 0; i < nlist; i++) resize(i, 0);
+        journal_lost();
     }
+    /// InvertedLists.cpp:77-97: every list of `oivf` appended to this one's (ids + add_id), and `oivf` emptied
+    virtual void merge_from(InvertedLists* oivf, size_t add_id);
     virtual void prefetch_lists(const long*, int) const {}
 
     /// bumped by every write: lets the owning index know its HBM copy is stale
     size_t version = 0;
+
+    /// The entries written since version `journal_base` (list << 32 | offset; entries past every position a list had are all in
+    /// it): the owning index sends only those to the engine (IndexIVF::sync_engine -> amd_ivf_update_lists).  journal_ok false:
+    /// the changes are not known entry by entry (reset, a read from a file, a journal grown past a quarter of the entries).
+    std::vector<uint64_t> journal;
+    bool journal_ok = false;
+    size_t journal_base = 0;
+    void journal_record(size_t list_no, size_t offset, size_t n) {
+        if (!journal_ok) return;
+        for (size_t i = 0; i < n; i++) journal.push_back((uint64_t)list_no << 32 | (uint64_t)(offset + i));
+        if ((offset + n) >> 32) journal_lost();
+        const size_t j = journal.size();
+        if (j >= 4096 && (j & (j - 1)) == 0) {  // (looked at now and then: a journal longer than a quarter of the entries is dropped)
+            size_t total = 0;
+            for (size_t l = 0; l < nlist; l++) total += list_size(l);
+            if (j * 4 > total) journal_lost();
+        }
+    }
+    void journal_lost() {
+        journal_ok = false;
+        journal.clear();
+        journal.shrink_to_fit();
+    }
+    /// the engine now holds these lists: the journal starts again from here
+    void journal_restart() {
+        journal.clear();
+        journal_ok = true;
+        journal_base = version;
+    }
 
     struct ScopedIds {
         const InvertedLists* il;

@@ -107,6 +107,7 @@ size_t ArrayInvertedLists::add_entries(size_t list_no, size_t n_entry, const idx
     ids[list_no].insert(ids[list_no].end(), ids_in, ids_in + n_entry);
     codes[list_no].insert(codes[list_no].end(), code, code + n_entry * code_size);
     version++;
+    journal_record(list_no, o, n_entry);
     return o;
 }
 
@@ -115,12 +116,30 @@ void ArrayInvertedLists::update_entries(size_t list_no, size_t offset, size_t n_
     memcpy(ids[list_no].data() + offset, ids_in, n_entry * sizeof(idx_t));
     memmove(codes[list_no].data() + offset * code_size, code, n_entry * code_size);  // (an entry may be moved within its own list)
     version++;
+    journal_record(list_no, offset, n_entry);
 }
 
 void ArrayInvertedLists::resize(size_t list_no, size_t new_size) {
+    const size_t o = ids[list_no].size();
     ids[list_no].resize(new_size);
     codes[list_no].resize(new_size * code_size);
     version++;
+    if (new_size > o) journal_record(list_no, o, new_size - o);  // (entries that appear are new entries)
+}
+
+void InvertedLists::merge_from(InvertedLists* oivf, size_t add_id) {
+    for (size_t i = 0; i < nlist; i++) {
+        const size_t n = oivf->list_size(i);
+        ScopedIds ids(oivf, i);
+        if (add_id == 0) {
+            add_entries(i, n, ids.get(), ScopedCodes(oivf, i).get());
+        } else {
+            std::vector<idx_t> new_ids(n);
+            for (size_t j = 0; j < n; j++) new_ids[j] = ids[j] + (idx_t)add_id;
+            add_entries(i, n, new_ids.data(), ScopedCodes(oivf, i).get());
+        }
+        oivf->resize(i, 0);
+    }
 }
 
 // ------------------------------------------------------------------------------------- error_pro / Trace
@@ -493,6 +512,27 @@ void IndexIVF::sync_engine(bool need_tuner) const {
         centroid_version_ = qf->version;
         interdis_uploaded_ = nullptr;  // the centroid table belongs to the old centroids
     }
+    if (lists_version_ != invlists->version && invlists->journal_ok && invlists->journal_base == lists_version_) {
+        // the engine holds the lists of version journal_base: only the entries written since then travel (amd_ivf_update_lists)
+        FAISS_THROW_IF_NOT_MSG(code_size == sizeof(float) * d, "IVF-Flat codes expected");
+        std::vector<size_t> sizes(nlist);
+        for (size_t l = 0; l < nlist; l++) sizes[l] = invlists->list_size(l);
+        std::vector<uint64_t> where(invlists->journal);
+        std::sort(where.begin(), where.end());
+        where.erase(std::unique(where.begin(), where.end()), where.end());
+        where.erase(std::remove_if(where.begin(), where.end(), [&](uint64_t e) { return (e & 0xffffffffull) >= sizes[e >> 32]; }), where.end());
+        std::vector<int64_t> wids(where.size());
+        std::vector<float> wcodes(where.size() * d);
+        for (size_t i = 0; i < where.size(); i++) {
+            const size_t l = where[i] >> 32, o = where[i] & 0xffffffffull;
+            wids[i] = (int64_t)invlists->get_single_id(l, o);
+            InvertedLists::ScopedCodes c(invlists, l);
+            memcpy(&wcodes[i * d], c.get() + o * code_size, code_size);
+        }
+        AMD(amd_ivf_update_lists(gpu_, sizes.data(), where.size(), where.data(), wids.data(), wcodes.data()));
+        lists_version_ = invlists->version;
+        invlists->journal_restart();
+    }
     if (lists_version_ != invlists->version) {
         FAISS_THROW_IF_NOT_MSG(code_size == sizeof(float) * d, "IVF-Flat codes expected");
         std::vector<size_t> sizes(nlist);
@@ -505,6 +545,7 @@ void IndexIVF::sync_engine(bool need_tuner) const {
         }
         AMD(amd_ivf_set_lists(gpu_, sizes.data(), codes.data(), ids.data()));
         lists_version_ = invlists->version;
+        invlists->journal_restart();
         resident_ptr_ = nullptr;  // nothing else to refresh, but keep the invariant explicit
     }
     // interdis_cem is a public vector the caller may refill in place (train_q1 does): pointer and size alone would miss
@@ -1069,6 +1110,50 @@ void IndexIVFFlatDedup::search_preassigned(idx_t n, const float* x, idx_t k, con
     IndexIVFFlat::search_preassigned(n, x, k, assign, centroid_dis, distances, labels, false, params);
     expand_instances(n, k & 0xffffffff, distances, labels);
 }
+
+void IndexIVF::check_compatible_for_merge(const IndexIVF& other) const {
+    FAISS_THROW_IF_NOT(other.d == d);
+    FAISS_THROW_IF_NOT(other.nlist == nlist);
+    FAISS_THROW_IF_NOT(other.code_size == code_size);
+    FAISS_THROW_IF_NOT_MSG(typeid(*this) == typeid(other), "can only merge indexes of the same type");
+}
+
+void IndexIVF::merge_from(IndexIVF& other, idx_t add_id) {
+    check_compatible_for_merge(other);
+    FAISS_THROW_IF_NOT_MSG((!maintain_direct_map && !other.maintain_direct_map), "direct map copy not implemented");
+    invlists->merge_from(other.invlists, add_id);
+    ntotal += other.ntotal;
+    other.ntotal = 0;
+}
+
+void IndexIVFFlat::update_vectors(int n, idx_t* new_ids, const float* x) {
+    FAISS_THROW_IF_NOT(maintain_direct_map);
+    FAISS_THROW_IF_NOT(is_trained);
+    std::vector<idx_t> assign(n);
+    quantizer->assign(n, x, assign.data());
+    for (int i = 0; i < n; i++) {
+        const idx_t id = new_ids[i];
+        FAISS_THROW_IF_NOT_MSG(0 <= id && id < ntotal, "id to update out of range");
+        {  // remove the old one
+            const long dm = direct_map[id], ofs = dm & 0xffffffff, il = dm >> 32;
+            const size_t l = invlists->list_size(il);
+            if ((size_t)ofs != l - 1) {  // move l - 1 to ofs
+                const idx_t id2 = invlists->get_single_id(il, l - 1);
+                direct_map[id2] = (il << 32) | ofs;
+                invlists->update_entry(il, ofs, id2, invlists->get_codes(il) + (l - 1) * code_size);
+            }
+            invlists->resize(il, l - 1);
+        }
+        {  // insert the new one
+            const long il = assign[i];
+            const size_t l = invlists->list_size(il);
+            direct_map[id] = (il << 32) | (long)l;
+            invlists->add_entry(il, id, reinterpret_cast<const uint8_t*>(x + (size_t)i * d));
+        }
+    }
+}
+
+void IndexIVFFlatDedup::update_vectors(int, idx_t*, const float*) { FAISS_THROW_MSG("not implemented"); }
 
 // Removal (IndexIVF.cpp:955-987): a removed entry's place is taken by the list's last entry, list by list; the lists in HBM are
 // refreshed before the next search (the version counter of the inverted lists).

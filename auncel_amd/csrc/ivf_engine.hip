@@ -20,6 +20,7 @@
 #include <string>
 #include <mutex>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/auncel_amd.h"
@@ -79,6 +80,8 @@ enum OptId {
                         // at 4 / 5 / 6 / 8 at a time); the others wait inside their calls
     OPT_COALESCE,       // asynchronous adaptive searches: queued tickets over adjacent resident ranges (same parameters, adjacent result
                         // buffers) that one pass over the lists may serve together (1: every ticket its own pass)
+    OPT_INCREMENTAL,    // changes of the lists between searches applied in HBM from a journal of the written entries (1, ivf_update.hip) or
+                        // by sending every list again (0)
     N_OPT
 };
 struct OptSpec {
@@ -105,6 +108,7 @@ const OptSpec OPT_TABLE[N_OPT] = {
     {"lanes", "AUNCEL_AMD_LANES", nullptr},
     {"fp32_in_flight", "AUNCEL_AMD_FP32_IN_FLIGHT", nullptr},
     {"coalesce", "AUNCEL_AMD_COALESCE", nullptr},
+    {"incremental", "AUNCEL_AMD_INCREMENTAL", nullptr},
 };
 struct Options {
     // (atomic: amd_ivf_set_option on the owner may run while search contexts cloned from it are searching; a search reads the
@@ -316,6 +320,7 @@ enum { CAT_COARSE = 0, CAT_SCAN = 1, CAT_SELECT = 2, CAT_SCAN_THR = 3, CAT_SELEC
 
 struct amd_ivf;
 static void async_shutdown(amd_ivf* h);  // (stops the handle's worker threads and frees their contexts)
+static bool tickets_out(amd_ivf* h);     // (asynchronous searches submitted and not yet waited for)
 
 struct amd_ivf {
     int d = 0, dpad = 0, metric = METRIC_L2, device = 0;
@@ -327,6 +332,14 @@ struct amd_ivf {
     std::vector<std::vector<int64_t>> h_ids;
     std::vector<uint64_t> h_list_off;
     bool lists_dirty = true;
+    // in-place updates (ivf_update.hip): the entries written since the device layout was built (list << 32 | offset), applied by
+    // upload_lists; the range of every list by itself (db_range is their merge after an entry was removed or overwritten)
+    bool journal_pending = false;
+    std::vector<uint64_t> journal;
+    std::vector<IntRange> list_range;
+    uint64_t last_update[4] = {0, 0, 0, 0};  // amd_ivf_last_update
+    PinnedBuf p_upd;
+    DevBuf d_upd;
     DevBuf d_codes, d_ids, d_list_off, d_centroids, d_centroid_norms;
     std::vector<float> h_centroids;  // nlist x dpad
     bool have_centroids = false;
@@ -664,11 +677,237 @@ void ensure_aux(amd_ivf* h, int lo, int hi) {
 }
 
 // ------------------------------------------------------------------------------------ lists
+// the range of list l's values (IntRange; a list that is not integer-valued is found so at its first chunk that is not)
+IntRange list_int_range(const amd_ivf* h, size_t l) {
+    IntRange r;
+    const std::vector<float>& c = h->h_codes[l];
+    for (size_t i = 0; i < c.size() && r.ok; i += 4096) r.add(c.data() + i, std::min<size_t>(4096, c.size() - i));
+    return r;
+}
+// whether taking this row out of a list can change the list's range (ok again, or a bound that moves)
+bool row_bounds_range(const IntRange& r, const float* row, int d) {
+    if (!r.ok) return true;
+    for (int c = 0; c < d; c++)
+        if (row[c] != 0.f && (row[c] == r.lo || row[c] == r.hi)) return true;
+    return false;
+}
+void merge_list_ranges(amd_ivf* h) {
+    IntRange all;
+    for (const IntRange& r : h->list_range) all.merge(r);
+    h->db_range = all;
+}
+static void swap_buf(DevBuf& a, DevBuf& b) {
+    std::swap(a.p, b.p);
+    std::swap(a.cap, b.cap);
+}
+
+// The journal applied in HBM (ivf_update.hip): the device then holds what the full upload below would have made of the same lists --
+// offsets, block tables, rows, ids and every derived copy that exists.  Returns false (nothing changed on the device that the full
+// upload does not rebuild) where the incremental path is off or cannot be used.
+bool apply_journal(amd_ivf* h) {
+    if (opt(h, OPT_INCREMENTAL, 1) == 0) return false;
+    const size_t nlist = h->nlist;
+    const int d = h->d, dpad = h->dpad;
+    std::vector<uint64_t> off(nlist + 1, 0), boff(nlist + 1, 0);
+    for (size_t l = 0; l < nlist; l++) {
+        off[l + 1] = off[l] + h->h_ids[l].size();
+        boff[l + 1] = boff[l] + mfma_list_blocks(h->h_ids[l].size());
+    }
+    const uint64_t nt = off[nlist], nt_old = h->h_list_off[nlist], nblk = boff[nlist];
+    if (nt == 0 || nt_old == 0 || h->h_block_off.size() != nlist + 1 || nt >= (1ull << SCAN_VB_BITS)) return false;
+    // the written entries: final values, each once, in (list, offset) order; an entry past its list's end went with a later removal
+    std::vector<uint64_t>& w = h->journal;
+    std::sort(w.begin(), w.end());
+    w.erase(std::unique(w.begin(), w.end()), w.end());
+    w.erase(std::remove_if(w.begin(), w.end(), [&](uint64_t e) { return (e & 0xffffffffull) >= h->h_ids[e >> 32].size(); }), w.end());
+    const size_t nw = w.size();
+    if (nw * 4 > nt) return false;
+    // 32-vector blocks to encode again: those holding a written entry, those whose padding changed, those the list did not have
+    std::vector<uint64_t> d32, d64;
+    size_t wi = 0;
+    for (size_t l = 0; l < nlist; l++) {
+        const uint64_t os = h->h_list_off[l + 1] - h->h_list_off[l], ns = off[l + 1] - off[l];
+        const uint64_t ob = h->h_block_off[l + 1] - h->h_block_off[l], nb = boff[l + 1] - boff[l];
+        const size_t first = d32.size();
+        for (; wi < nw && (w[wi] >> 32) == l; wi++) d32.push_back(boff[l] + (w[wi] & 0xffffffffull) / 32);
+        const uint64_t lo = std::min(os, ns), hi = std::max(os, ns);
+        if (os != ns)
+            for (uint64_t b = lo / 32; b < nb; b++)
+                if (b >= ob || 32 * b < hi) d32.push_back(boff[l] + b);
+        std::sort(d32.begin() + first, d32.end());
+        d32.erase(std::unique(d32.begin() + first, d32.end()), d32.end());
+    }
+    for (uint64_t b : d32)
+        if (d64.empty() || d64.back() != b / 2) d64.push_back(b / 2);
+    // one staged upload: new offsets, new block table, the written rows, their places and ids, the block lists
+    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_off = 0, o_boff = al((nlist + 1) * 8), o_vals = o_boff + al((nlist + 1) * 8), o_rows = o_vals + nw * dpad * 4,
+                 o_wids = o_rows + al(nw * 8), o_d32 = o_wids + al(nw * 8), o_d64 = o_d32 + al(d32.size() * 8), total = o_d64 + al(d64.size() * 8);
+    h->p_upd.ensure(total);
+    uint8_t* st = h->p_upd.as<uint8_t>();
+    memcpy(st + o_off, off.data(), (nlist + 1) * 8);
+    memcpy(st + o_boff, boff.data(), (nlist + 1) * 8);
+    for (size_t i = 0; i < nw; i++) {
+        const uint64_t l = w[i] >> 32, p = w[i] & 0xffffffffull;
+        memcpy(st + o_vals + i * dpad * 4, &h->h_codes[l][p * dpad], dpad * 4);
+        reinterpret_cast<uint64_t*>(st + o_rows)[i] = off[l] + p;
+        reinterpret_cast<int64_t*>(st + o_wids)[i] = h->h_ids[l][p];
+    }
+    memcpy(st + o_d32, d32.data(), d32.size() * 8);
+    memcpy(st + o_d64, d64.data(), d64.size() * 8);
+    const bool codes8 = h->allow_bytes && h->db_range.bytes() && (double)d * 255.0 * 255.0 < 2147483648.0;
+    const bool f32_possible = h->allow_filter && nt < 0xffffffffull;
+    try {
+        h->d_upd.ensure(total);
+        HIP_CHECK(hipMemcpyAsync(h->d_upd.p, st, total, hipMemcpyHostToDevice, h->stream));
+        uint8_t* du = h->d_upd.as<uint8_t>();
+        const uint64_t* n_off = reinterpret_cast<const uint64_t*>(du + o_off);
+        const uint64_t* n_boff = reinterpret_cast<const uint64_t*>(du + o_boff);
+        const uint64_t* l32 = reinterpret_cast<const uint64_t*>(du + o_d32);
+        const uint64_t* l64 = reinterpret_cast<const uint64_t*>(du + o_d64);
+        const uint64_t* o_loff = h->d_list_off.as<uint64_t>();
+        const uint64_t* o_bo = h->d_block_off.as<uint64_t>();
+        const uint32_t nl = (uint32_t)nlist;
+        auto retire = [&](DevBuf& cur, DevBuf& made) {  // the new buffer in, the old one out once the stream is past it
+            swap_buf(cur, made);
+            HIP_CHECK(stream_sync(h->stream));
+            made.release();
+        };
+        {  // rows and ids
+            DevBuf nc, ni;
+            nc.ensure(nt * dpad * sizeof(float));
+            ni.ensure(nt * sizeof(int64_t));
+            launch_relayout_rows(h->d_codes.as<float>(), h->d_ids.as<int64_t>(), o_loff, n_off, nl, nt, dpad, nc.as<float>(), ni.as<int64_t>(), h->stream);
+            launch_scatter_rows(reinterpret_cast<const uint64_t*>(du + o_rows), reinterpret_cast<const int64_t*>(du + o_wids),
+                                reinterpret_cast<const float*>(du + o_vals), nw, dpad, nc.as<float>(), ni.as<int64_t>(), h->stream);
+            retire(h->d_ids, ni);
+            retire(h->d_codes, nc);
+        }
+        const float* codes = h->d_codes.as<float>();
+        if (codes8) {  // byte fragments + cy: kept, or built now that the lists qualify
+            const uint64_t bb = (uint64_t)mfma_ksteps(d) * 1024;
+            DevBuf nf, ncy;
+            nf.ensure(nblk * bb);
+            ncy.ensure(nblk * 32 * sizeof(int32_t));
+            if (h->have_codes8) {
+                launch_relayout_blocks(h->d_frag.p, nf.p, bb, h->d_cy.p, ncy.p, 128, o_bo, n_boff, nl, nblk, 0, h->stream);
+                launch_frag_from_f32_list(codes, n_off, n_boff, nl, l32, d32.size(), d, dpad, h->metric, nf.as<uint8_t>(), ncy.as<int32_t>(), h->stream);
+            } else {
+                launch_frag_from_f32(codes, n_off, n_boff, nl, nblk, d, dpad, h->metric, nf.as<uint8_t>(), ncy.as<int32_t>(), h->stream);
+            }
+            retire(h->d_cy, ncy);
+            retire(h->d_frag, nf);
+        } else {
+            h->d_frag.release();
+            h->d_cy.release();
+        }
+        h->have_codes8 = codes8;
+        const bool keep32 = h->have_frag32 && f32_possible;
+        bool keep16 = h->frag16_state == 1 && f32_possible;
+        bool yn_done = false;
+        if (keep32) {  // fp32 fragments + yn
+            const uint64_t bb = (uint64_t)filter_steps(d) * 1024;
+            DevBuf nf, nyn;
+            nf.ensure(nblk * bb);
+            nyn.ensure(nblk * 32 * sizeof(float));
+            launch_relayout_blocks(h->d_frag32.p, nf.p, bb, h->d_yn.p, nyn.p, 128, o_bo, n_boff, nl, nblk, 0, h->stream);
+            launch_frag32_from_f32_list(codes, n_off, n_boff, nl, l32, d32.size(), d, dpad, h->metric, nf.as<float>(), nyn.as<float>(), h->stream);
+            retire(h->d_yn, nyn);
+            retire(h->d_frag32, nf);
+            yn_done = true;
+        } else {
+            h->d_frag32.release();
+            h->have_frag32 = false;
+        }
+        if (keep16) {  // fp16 fragments + yn: the scale is the whole index's (launch_amax); when it moves, the whole copy is encoded again
+            DevBuf ninfo;
+            ninfo.ensure(16);
+            HIP_CHECK(hipMemsetAsync(ninfo.p, 0, 16, h->stream));
+            launch_amax(codes, nt, dpad, ninfo.as<uint32_t>(), h->stream);
+            uint32_t was[4] = {0, 0, 0, 0}, now[4] = {0, 0, 0, 0};
+            HIP_CHECK(hipMemcpyAsync(was, h->d_yinfo.p, 16, hipMemcpyDeviceToHost, h->stream));
+            HIP_CHECK(hipMemcpyAsync(now, ninfo.p, 16, hipMemcpyDeviceToHost, h->stream));
+            HIP_CHECK(stream_sync(h->stream));
+            const float s_now = filter_half_scale(now, d), s_was = filter_half_scale(was, d);
+            if (s_now == 0.f) {
+                keep16 = false;  // (the next fp32 search finds the scale unusable, as after a full upload)
+            } else {
+                const uint64_t bb = (uint64_t)filter_steps16(d) * 1024;
+                DevBuf nf, nyn;
+                nf.ensure(nblk * bb);
+                if (!yn_done) nyn.ensure(nblk * 32 * sizeof(float));
+                float* yn = yn_done ? h->d_yn.as<float>() : nyn.as<float>();
+                if (s_now == s_was) {
+                    launch_relayout_blocks(h->d_frag16.p, nf.p, bb, yn_done ? nullptr : h->d_yn.p, yn_done ? nullptr : nyn.p, 128, o_bo, n_boff, nl, nblk,
+                                           0, h->stream);
+                    launch_frag16_from_f32_list(codes, n_off, n_boff, nl, l32, d32.size(), d, dpad, h->metric, ninfo.as<uint32_t>(), nf.as<float>(), yn,
+                                                h->stream);
+                } else {
+                    launch_frag16_from_f32(codes, n_off, n_boff, nl, nblk, d, dpad, h->metric, ninfo.as<uint32_t>(), nf.as<float>(), yn, h->stream);
+                }
+                if (!yn_done) retire(h->d_yn, nyn);
+                yn_done = true;
+                retire(h->d_yinfo, ninfo);
+                retire(h->d_frag16, nf);
+            }
+        }
+        if (!keep16) h->d_frag16.release();
+        h->frag16_state = keep16 ? 1 : 0;
+        if (!yn_done) h->d_yn.release();
+        // the lane-ordered copy (64-vector blocks), where ensure_lanes would build it for these lists: the copy leaves a quarter of
+        // itself + 1 GiB free (the old copy still counted: it goes once the new one is made)
+        const uint64_t lanes_bytes = nblk / 2 * (uint64_t)dpad * 64 * sizeof(float), lanes_want = lanes_bytes + lanes_bytes / 8 + 256;
+        size_t free_b = 0, total_b = 0;
+        const bool lanes_fit = h->lanes_state.load() == 1 && nblk / 2 < (1ull << (64 - SCAN_VB_BITS)) && !getenv("AUNCEL_AMD_LANES_NOFIT") &&
+                               hipMemGetInfo(&free_b, &total_b) == hipSuccess && (uint64_t)free_b >= lanes_want + lanes_want / 4 + (1ull << 30);
+        if (lanes_fit) {
+            const uint64_t bb = (uint64_t)dpad * 64 * sizeof(float);
+            DevBuf nlz;
+            nlz.ensure(nblk / 2 * bb);
+            launch_relayout_blocks(h->d_lanes.p, nlz.p, bb, nullptr, nullptr, 0, o_bo, n_boff, nl, nblk / 2, 1, h->stream);
+            launch_lanes_from_f32_list(codes, n_off, n_boff, nl, l64, d64.size(), dpad, nlz.as<float>(), h->stream);
+            retire(h->d_lanes, nlz);
+        } else {
+            h->d_lanes.release();
+            h->lanes_state = 0;
+        }
+        HIP_CHECK(hipMemcpyAsync(h->d_list_off.p, n_off, (nlist + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->d_block_off.p, n_boff, (nlist + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
+        HIP_CHECK(stream_sync(h->stream));
+    } catch (const std::exception& e) {
+        // (an allocation that failed, most likely: the full upload rebuilds every buffer this may have left half done)
+        (void)hipGetLastError();
+        if (getenv("AUNCEL_AMD_VERBOSE")) fprintf(stderr, "[auncel_amd] in-place update failed (%s): every list is sent again\n", e.what());
+        return false;
+    }
+    h->h_list_off.swap(off);
+    h->h_block_off.swap(boff);
+    h->frag32_possible = f32_possible;
+    {
+        double s1 = 0, s2 = 0;
+        for (size_t l = 0; l < nlist; l++) {
+            const double len = (double)h->h_ids[l].size();
+            s1 += len;
+            s2 += len * len;
+        }
+        h->probed_len = s1 > 0 ? s2 / s1 : 0.0;
+    }
+    h->last_update[0] = 1;
+    h->last_update[1] = total;
+    h->last_update[2] = nw;
+    h->last_update[3] = d32.size();
+    return true;
+}
+
 void upload_lists(amd_ivf* h) {
     h = ix(h);
     std::lock_guard<std::mutex> lock(h->upload_mu);
-    if (!h->lists_dirty) return;
+    if (!h->lists_dirty && !h->journal_pending) return;
     use_device(h);
+    const bool incremental = !h->lists_dirty && apply_journal(h);
+    h->journal.clear();
+    h->journal_pending = false;
+    if (incremental) return;
     h->h_list_off.assign(h->nlist + 1, 0);
     for (size_t l = 0; l < h->nlist; l++) h->h_list_off[l + 1] = h->h_list_off[l] + h->h_ids[l].size();
     size_t nt = h->h_list_off[h->nlist];
@@ -724,6 +963,10 @@ void upload_lists(amd_ivf* h) {
     }
     HIP_CHECK(stream_sync(h->stream));
     h->lists_dirty = false;
+    h->last_update[0] = 2;
+    h->last_update[1] = nt * (h->dpad * sizeof(float) + sizeof(int64_t)) + (h->nlist + 1) * sizeof(uint64_t) * (nt > 0 ? 2 : 1);
+    h->last_update[2] = nt;
+    h->last_update[3] = h->have_codes8 ? h->h_block_off[h->nlist] : 0;
 }
 
 // Byte view of n query rows (row stride dpad floats) when the lists have one and the queries qualify; fills
@@ -3144,6 +3387,7 @@ int amd_ivf_create(int d, size_t nlist, int metric, int device, amd_ivf_t** out)
     ensure_context_streams(h.get());
     h->h_codes.resize(nlist);
     h->h_ids.resize(nlist);
+    h->list_range.resize(nlist);
     h->h_list_off.assign(nlist + 1, 0);
     if (getenv("AUNCEL_AMD_NO_FUSED")) h->allow_fused = 0;
     if (getenv("AUNCEL_AMD_NO_BYTES")) h->allow_bytes = 0;
@@ -3227,6 +3471,8 @@ int amd_ivf_set_lists(amd_ivf_t* h, const size_t* sizes, const float* const* cod
     for (size_t l = 0; l < h->nlist; l++) {
         size_t n = sizes[l];
         h->db_range.add(codes[l], n * (size_t)h->d);
+        h->list_range[l] = IntRange();
+        h->list_range[l].add(codes[l], n * (size_t)h->d);
         h->h_codes[l].assign(n * h->dpad, 0.f);
         for (size_t j = 0; j < n; j++) memcpy(&h->h_codes[l][j * h->dpad], codes[l] + j * h->d, h->d * sizeof(float));
         h->h_ids[l].assign(ids[l], ids[l] + n);
@@ -3234,6 +3480,8 @@ int amd_ivf_set_lists(amd_ivf_t* h, const size_t* sizes, const float* const* cod
     }
     h->ntotal = nt;
     h->lists_dirty = true;
+    h->journal.clear();
+    h->journal_pending = false;
     upload_lists(h);
     API_END
 }
@@ -3242,6 +3490,9 @@ int amd_ivf_add(amd_ivf_t* h, size_t n, const float* x, const int64_t* xids, con
     API_BEGIN
     OWNER_ONLY(h);
     use_device(h);
+    // (the device layout moves at the next search: not under searches that are still running)
+    const bool journal = !h->lists_dirty && opt(h, OPT_INCREMENTAL, 1) != 0;
+    if (journal && n && tickets_out(h)) throw EngineError("tickets are still out: wait for them before changing the index");
     std::vector<int64_t> assign;
     const int64_t* idx = precomputed_idx;
     if (!idx) {
@@ -3269,13 +3520,21 @@ int amd_ivf_add(amd_ivf_t* h, size_t n, const float* x, const int64_t* xids, con
         if ((size_t)l >= h->nlist) throw EngineError("Invalid list number in add");
         std::vector<float>& c = h->h_codes[l];
         size_t o = c.size();
+        if (journal) h->journal.push_back((uint64_t)l << 32 | (uint64_t)h->h_ids[l].size());
         c.resize(o + h->dpad, 0.f);
         memcpy(&c[o], x + i * h->d, h->d * sizeof(float));
         h->h_ids[l].push_back(id);
+        h->list_range[l].add(x + i * h->d, h->d);
     }
     h->db_range.add(x, n * (size_t)h->d);
     h->ntotal += n;
-    h->lists_dirty = true;
+    if (journal && n) {
+        h->journal_pending = true;
+        for (size_t l = 0; l < h->nlist; l++)
+            if (h->h_ids[l].size() >> 32) h->lists_dirty = true;  // (an offset the journal cannot hold)
+    } else {
+        h->lists_dirty = true;
+    }
     API_END
 }
 
@@ -5295,6 +5554,194 @@ int amd_ivf_last_timing(amd_ivf_t* h, double out[8]) {
 int amd_ivf_last_timing_detail(amd_ivf_t* h, double out[16]) {
     for (int i = 0; i < 2 * NCAT + 2; i++) out[i] = h->timing_detail[i];
     return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------ in-place updates
+static bool tickets_out(amd_ivf* h) {
+    if (!h->async) return false;
+    std::lock_guard<std::mutex> lk(h->async->mu);
+    return !h->async->jobs.empty();
+}
+
+namespace {
+// 64-bit digest of a byte range (FNV-1a over 8-byte words, then the length)
+uint64_t digest_bytes(const void* p, size_t n, uint64_t hsh = 1469598103934665603ull) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    size_t i = 0;
+    for (; i + 8 <= n; i += 8) {
+        uint64_t w;
+        memcpy(&w, b + i, 8);
+        hsh = (hsh ^ w) * 1099511628211ull;
+    }
+    for (; i < n; i++) hsh = (hsh ^ b[i]) * 1099511628211ull;
+    return (hsh ^ n) * 1099511628211ull;
+}
+uint64_t digest_device(amd_ivf* h, const void* p, size_t n, uint64_t hsh = 1469598103934665603ull) {
+    std::vector<uint8_t> tmp(n);
+    if (n) {
+        HIP_CHECK(hipMemcpyAsync(tmp.data(), p, n, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(stream_sync(h->stream));
+    }
+    return digest_bytes(tmp.data(), n, hsh);
+}
+void refuse_with_tickets(amd_ivf* h) {
+    if (tickets_out(h)) throw EngineError("tickets are still out: wait for them before changing the index");
+}
+// after entries of list l were removed or overwritten
+void retake_range(amd_ivf* h, size_t l, bool moved) {
+    if (moved) h->list_range[l] = list_int_range(h, l);
+}
+}  // namespace
+
+extern "C" {
+
+int amd_ivf_update_lists(amd_ivf_t* h, const size_t* sizes, size_t nw, const uint64_t* where, const int64_t* ids, const float* codes) {
+    API_BEGIN
+    if (!h) throw EngineError("null handle");
+    OWNER_ONLY(h);
+    if (!sizes || (nw && (!where || !ids || !codes))) throw EngineError("null argument");
+    const size_t nlist = h->nlist, dpad = h->dpad, d = h->d;
+    // every check before anything changes: places inside the new sizes, every entry past a list's old size written
+    std::vector<size_t> grow_off(nlist + 1, 0);
+    for (size_t l = 0; l < nlist; l++) {
+        if (sizes[l] >> 32) throw EngineError("list too long for an update");
+        grow_off[l + 1] = grow_off[l] + (sizes[l] > h->h_ids[l].size() ? sizes[l] - h->h_ids[l].size() : 0);
+    }
+    std::vector<char> covered(grow_off[nlist], 0);
+    for (size_t i = 0; i < nw; i++) {
+        const uint64_t l = where[i] >> 32, p = where[i] & 0xffffffffull;
+        if (l >= nlist) throw EngineError("update_lists: list number out of range");
+        if (p >= sizes[l]) throw EngineError("update_lists: offset past the list's new size");
+        const size_t os = h->h_ids[l].size();
+        if (p >= os) covered[grow_off[l] + (p - os)] = 1;
+    }
+    for (char c : covered)
+        if (!c) throw EngineError("update_lists: an entry past a list's old size is not written");
+    refuse_with_tickets(h);
+    use_device(h);
+    const bool journal = !h->lists_dirty && opt(h, OPT_INCREMENTAL, 1) != 0;
+    std::vector<char> moved(nlist, 0);
+    for (size_t l = 0; l < nlist; l++) {  // (entries cut off take their values out of the list's range)
+        const size_t os = h->h_ids[l].size();
+        for (size_t p = sizes[l]; p < os && !moved[l]; p++) moved[l] = row_bounds_range(h->list_range[l], &h->h_codes[l][p * dpad], (int)d);
+        h->h_ids[l].resize(sizes[l], -1);
+        h->h_codes[l].resize(sizes[l] * dpad, 0.f);
+    }
+    size_t nt = 0;
+    for (size_t l = 0; l < nlist; l++) nt += sizes[l];
+    for (size_t i = 0; i < nw; i++) {
+        const uint64_t l = where[i] >> 32, p = where[i] & 0xffffffffull;
+        float* row = &h->h_codes[l][p * dpad];
+        if (!moved[l]) moved[l] = row_bounds_range(h->list_range[l], row, (int)d);
+        memcpy(row, codes + i * d, d * sizeof(float));
+        h->h_ids[l][p] = ids[i];
+        if (!moved[l]) h->list_range[l].add(row, d);
+        if (journal) h->journal.push_back(where[i]);
+    }
+    for (size_t l = 0; l < nlist; l++) retake_range(h, l, moved[l]);
+    merge_list_ranges(h);
+    h->ntotal = nt;
+    if (journal) h->journal_pending = true;
+    else h->lists_dirty = true;
+    upload_lists(h);
+    API_END
+}
+
+int amd_ivf_remove_ids(amd_ivf_t* h, size_t n, const int64_t* ids, size_t* nremoved) {
+    API_BEGIN
+    if (!h) throw EngineError("null handle");
+    OWNER_ONLY(h);
+    if (!nremoved || (n && !ids)) throw EngineError("null argument");
+    *nremoved = 0;
+    refuse_with_tickets(h);
+    const std::unordered_set<int64_t> sel(ids, ids + n);
+    // (every entry of every list is looked at: a bit per hashed id, small enough to stay in cache, turns away most of them before
+    // the set is asked -- a hash lookup per entry was 0.1 s of a 10M-entry index)
+    std::vector<uint64_t> bloom(1u << 14, 0);
+    auto bit = [](int64_t v) { return (uint32_t)(((uint64_t)v * 0x9E3779B97F4A7C15ull) >> 44); };
+    for (size_t i = 0; i < n; i++) bloom[bit(ids[i]) >> 6] |= 1ull << (bit(ids[i]) & 63);
+    auto member = [&](int64_t v) { const uint32_t b = bit(v); return ((bloom[b >> 6] >> (b & 63)) & 1) && sel.count(v); };
+    const size_t dpad = h->dpad;
+    const bool journal = !h->lists_dirty && opt(h, OPT_INCREMENTAL, 1) != 0;
+    size_t total = 0;
+    // IndexIVF::remove_ids: a removed entry takes the list's last entry, and the entry that arrives there is looked at in turn
+    for (size_t l = 0; l < h->nlist; l++) {
+        std::vector<int64_t>& I = h->h_ids[l];
+        std::vector<float>& c = h->h_codes[l];
+        size_t len = I.size(), j = 0;
+        const size_t l0 = len;
+        bool moved = false;
+        while (j < len) {
+            if (member(I[j])) {
+                if (!moved) moved = row_bounds_range(h->list_range[l], &c[j * dpad], h->d);
+                len--;
+                if (j < len) {
+                    I[j] = I[len];
+                    memcpy(&c[j * dpad], &c[len * dpad], dpad * sizeof(float));
+                    if (journal) h->journal.push_back((uint64_t)l << 32 | j);
+                }
+            } else {
+                j++;
+            }
+        }
+        if (len != l0) {
+            I.resize(len);
+            c.resize(len * dpad);
+            total += l0 - len;
+            retake_range(h, l, moved);
+        }
+    }
+    *nremoved = total;
+    if (total) {
+        use_device(h);
+        merge_list_ranges(h);
+        h->ntotal -= total;
+        if (journal) h->journal_pending = true;
+        else h->lists_dirty = true;
+        upload_lists(h);
+    }
+    API_END
+}
+
+int amd_ivf_last_update(amd_ivf_t* h, uint64_t out[4]) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("null argument");
+    for (int i = 0; i < 4; i++) out[i] = ix(h)->last_update[i];
+    API_END
+}
+
+int amd_ivf_layout_digest(amd_ivf_t* h, uint64_t out[8]) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("null argument");
+    OWNER_ONLY(h);
+    use_device(h);
+    upload_lists(h);
+    std::lock_guard<std::mutex> lock(h->upload_mu);
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    const size_t nlist = h->nlist, nt = h->h_list_off[nlist];
+    const uint64_t nblk = nt ? h->h_block_off[nlist] : 0;
+    const int d = h->d, dpad = h->dpad;
+    out[0] = digest_device(h, h->d_list_off.p, (nlist + 1) * 8);
+    if (nt) {
+        out[0] = digest_device(h, h->d_block_off.p, (nlist + 1) * 8, out[0]);
+        out[1] = digest_device(h, h->d_codes.p, nt * dpad * sizeof(float));
+        out[2] = digest_device(h, h->d_ids.p, nt * sizeof(int64_t));
+    }
+    if (h->have_codes8) out[3] = digest_device(h, h->d_cy.p, nblk * 128, digest_device(h, h->d_frag.p, nblk * mfma_ksteps(d) * 1024));
+    if (h->frag16_state == 1)
+        out[4] = digest_device(h, h->d_yinfo.p, 16, digest_device(h, h->d_yn.p, nblk * 128, digest_device(h, h->d_frag16.p, nblk * filter_steps16(d) * 1024)));
+    if (h->have_frag32) out[5] = digest_device(h, h->d_yn.p, nblk * 128, digest_device(h, h->d_frag32.p, nblk * filter_steps(d) * 1024));
+    if (h->lanes_state == 1) out[6] = digest_device(h, h->d_lanes.p, nblk / 2 * (uint64_t)dpad * 64 * sizeof(float));
+    const double pl = h->probed_len;
+    const uint64_t flags[8] = {(uint64_t)h->have_codes8, (uint64_t)h->frag32_possible, (uint64_t)h->db_range.ok, (uint64_t)h->db_range.bytes(),
+                               h->db_range.ok ? (uint64_t)(int64_t)h->db_range.lo : 0, h->db_range.ok ? (uint64_t)(int64_t)h->db_range.hi : 0,
+                               (uint64_t)h->ntotal, (uint64_t)nt};
+    out[7] = digest_bytes(&pl, sizeof(pl), digest_bytes(flags, sizeof(flags)));
+    for (int i = 0; i < 8; i++)
+        if (out[i] == 0 && (i == 0 || i == 7)) out[i] = 1;
+    API_END
 }
 
 }  // extern "C"

@@ -61,9 +61,9 @@ typedef const v4f __attribute__((address_space(1)))* gv4f;
 // fp32 lists (CSR rows, row stride dpad) -> fragment order: a list is a run of 32-vector blocks (block_off[l] = its first, an
 // even number of them as for the byte codes); a block is filter_steps(d) pieces of 64 lanes x 16 bytes, lane (v = l & 31,
 // h = l >> 5) of piece j holding elements 8 j + 4 h .. + 3 of vector v (zero beyond d).  yn[slot] = |y|^2 (L2) or |y| (IP).
-__global__ __launch_bounds__(64) void frag32_from_f32_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
-                                                             int d, int dpad, int metric, float* out, float* yn) {
-    const uint64_t blk = blockIdx.x;
+// (one wave: block `blk` of the copy; the whole-copy kernel and the block-list kernel below share it)
+__device__ __forceinline__ void frag32_from_f32_block(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                             int d, int dpad, int metric, float* out, float* yn, uint64_t blk) {
     const int lane = threadIdx.x, v = lane & 31, h = lane >> 5;
     uint32_t lo = 0, hi = nlist;  // largest l with block_off[l] <= blk
     while (hi - lo > 1) {
@@ -90,11 +90,25 @@ __global__ __launch_bounds__(64) void frag32_from_f32_kernel(const float* codes,
     sq += __shfl_xor(sq, 32);
     if (h == 0) yn[blk * 32 + v] = !ok ? 0.f : metric == METRIC_L2 ? (float)sq : (float)sqrt(sq);
 }
+__global__ __launch_bounds__(64) void frag32_from_f32_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                             int d, int dpad, int metric, float* out, float* yn) {
+    frag32_from_f32_block(codes, list_off, block_off, nlist, d, dpad, metric, out, yn, blockIdx.x);
+}
+// the same for the blocks listed in `blocks` (ivf_update.hip: the blocks an update changed)
+__global__ __launch_bounds__(64) void frag32_from_f32_list_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                             int d, int dpad, int metric, float* out, float* yn, const uint64_t* blocks) {
+    frag32_from_f32_block(codes, list_off, block_off, nlist, d, dpad, metric, out, yn, blocks[blockIdx.x]);
+}
 
 void launch_frag32_from_f32(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, uint64_t nblocks, int d,
                             int dpad, int metric, float* out, float* yn, hipStream_t s) {
     if (nblocks == 0) return;
     LAUNCH(frag32_from_f32_kernel, dim3((unsigned)nblocks), dim3(64), 0, s, codes, list_off, block_off, nlist, d, dpad, metric, out, yn);
+}
+void launch_frag32_from_f32_list(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, const uint64_t* blocks,
+                                 uint64_t nlisted, int d, int dpad, int metric, float* out, float* yn, hipStream_t s) {
+    if (nlisted == 0) return;
+    LAUNCH(frag32_from_f32_list_kernel, dim3((unsigned)nlisted), dim3(64), 0, s, codes, list_off, block_off, nlist, d, dpad, metric, out, yn, blocks);
 }
 
 // query rows (stride dpad) -> rows of 8 J floats (zero beyond d) + |x|^2 (L2) or |x| (IP); one wave per row
@@ -209,9 +223,9 @@ float filter_half_scale(const uint32_t info[4], int d) { return half_scale_of(in
 
 // a block = filter_steps16(d) pieces of 64 lanes x 16 bytes, lane (v = l & 31, h = l >> 5) of piece j holding elements
 // 16 j + 8 h .. + 7 of vector v as fp16(s_y * value) (zero beyond d); yn as in the fp32 form (from the fp32 values)
-__global__ __launch_bounds__(64) void frag16_from_f32_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
-                                                             int d, int dpad, int metric, const uint32_t* info, float* out, float* yn) {
-    const uint64_t blk = blockIdx.x;
+// (one wave: block `blk` of the copy; the whole-copy kernel and the block-list kernel below share it)
+__device__ __forceinline__ void frag16_from_f32_block(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                             int d, int dpad, int metric, const uint32_t* info, float* out, float* yn, uint64_t blk) {
     const int lane = threadIdx.x, v = lane & 31, h = lane >> 5;
     uint32_t lo = 0, hi = nlist;  // largest l with block_off[l] <= blk
     while (hi - lo > 1) {
@@ -239,10 +253,25 @@ __global__ __launch_bounds__(64) void frag16_from_f32_kernel(const float* codes,
     sq += __shfl_xor(sq, 32);
     if (h == 0) yn[blk * 32 + v] = !ok ? 0.f : metric == METRIC_L2 ? (float)sq : (float)sqrt(sq);
 }
+__global__ __launch_bounds__(64) void frag16_from_f32_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                             int d, int dpad, int metric, const uint32_t* info, float* out, float* yn) {
+    frag16_from_f32_block(codes, list_off, block_off, nlist, d, dpad, metric, info, out, yn, blockIdx.x);
+}
+// the same for the blocks listed in `blocks` (ivf_update.hip: the blocks an update changed)
+__global__ __launch_bounds__(64) void frag16_from_f32_list_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                             int d, int dpad, int metric, const uint32_t* info, float* out, float* yn, const uint64_t* blocks) {
+    frag16_from_f32_block(codes, list_off, block_off, nlist, d, dpad, metric, info, out, yn, blocks[blockIdx.x]);
+}
 void launch_frag16_from_f32(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, uint64_t nblocks, int d,
                             int dpad, int metric, const uint32_t* info, float* out, float* yn, hipStream_t s) {
     if (nblocks == 0) return;
     LAUNCH(frag16_from_f32_kernel, dim3((unsigned)nblocks), dim3(64), 0, s, codes, list_off, block_off, nlist, d, dpad, metric, info, out, yn);
+}
+void launch_frag16_from_f32_list(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, const uint64_t* blocks,
+                                 uint64_t nlisted, int d, int dpad, int metric, const uint32_t* info, float* out, float* yn, hipStream_t s) {
+    if (nlisted == 0) return;
+    LAUNCH(frag16_from_f32_list_kernel, dim3((unsigned)nlisted), dim3(64), 0, s, codes, list_off, block_off, nlist, d, dpad, metric, info, out, yn,
+           blocks);
 }
 
 // FilterParams of a pair of matrices by themselves (the approximate coarse ranking on fp16 operands: coarse_gemm16_kernel): pad =

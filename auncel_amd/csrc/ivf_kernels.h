@@ -672,4 +672,28 @@ void launch_range_collect(const float* dist, uint32_t n, float radius, int metri
 void launch_fill_f32(float* p, size_t n, float v, hipStream_t s);
 void launch_fill_i64(int64_t* p, size_t n, int64_t v, hipStream_t s);
 
+// ---------------------------------------------------------------------------- in-place updates (ivf_update.hip)
+// The derived copies again for the blocks listed in `blocks` only (32-vector blocks; the lane copy's 64-vector blocks), with the
+// same device code as the whole-copy launches above: an update re-encodes what it changed and copies the rest.
+void launch_frag_from_f32_list(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, const uint64_t* blocks,
+                               uint64_t nlisted, int d, int dpad, int metric, uint8_t* out, int32_t* cy, hipStream_t s);
+void launch_frag32_from_f32_list(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, const uint64_t* blocks,
+                                 uint64_t nlisted, int d, int dpad, int metric, float* out, float* yn, hipStream_t s);
+void launch_frag16_from_f32_list(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, const uint64_t* blocks,
+                                 uint64_t nlisted, int d, int dpad, int metric, const uint32_t* info, float* out, float* yn, hipStream_t s);
+void launch_lanes_from_f32_list(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, const uint64_t* blocks64,
+                                uint64_t nlisted, int dpad, float* out, hipStream_t s);
+// rows (stride dpad) and ids of the new layout: entry p of list l comes from entry p of the old layout where p < its old size, else
+// it is zeroed (the scatter below writes it)
+void launch_relayout_rows(const float* old_codes, const int64_t* old_ids, const uint64_t* old_off, const uint64_t* new_off, uint32_t nlist,
+                          uint64_t nt_new, int dpad, float* codes, int64_t* ids, hipStream_t s);
+// the written entries from one staged block: rows[i] (a row of the new layout), ids[i], vals[i * dpad .. + dpad)
+void launch_scatter_rows(const uint64_t* rows, const int64_t* wids, const float* vals, uint64_t nw, int dpad, float* codes, int64_t* ids,
+                         hipStream_t s);
+// a block copy in its new layout: block b of list l is block b of the old layout where the list had one (the changed blocks are
+// re-encoded afterwards); `shift` 0 for 32-vector blocks, 1 for 64-vector blocks (block_off / 2); main: block_bytes a block,
+// side (or null): side_bytes a block (cy, yn)
+void launch_relayout_blocks(const void* old_main, void* new_main, uint64_t block_bytes, const void* old_side, void* new_side, uint64_t side_bytes,
+                            const uint64_t* old_boff, const uint64_t* new_boff, uint32_t nlist, uint64_t nblk_new, int shift, hipStream_t s);
+
 }  // namespace amdivf

@@ -409,9 +409,9 @@ __global__ __launch_bounds__(ScanShape<QG>::NT) void scan_lanes_kernel(ScanArgs 
 }
 
 // one wave per (64-vector block, run of pieces): lane l copies vector 64 b + l's elements, 16 bytes a piece
-__global__ __launch_bounds__(64) void lanes_from_f32_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
-                                                            int dpad, float* out) {
-    const uint64_t blk = blockIdx.x;
+// (one wave: block `blk` of the copy; the whole-copy kernel and the block-list kernel below share it)
+__device__ __forceinline__ void lanes_from_f32_block(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                            int dpad, float* out, uint64_t blk) {
     const int lane = threadIdx.x;
     uint32_t lo = 0, hi = nlist;  // largest l with block_off[l] / 2 <= blk
     while (hi - lo > 1) {
@@ -426,11 +426,25 @@ __global__ __launch_bounds__(64) void lanes_from_f32_kernel(const float* codes, 
     float4* dst = reinterpret_cast<float4*>(out) + blk * (uint64_t)nsteps * 64 + lane;
     for (int s = 0; s < nsteps; s++) dst[(size_t)s * 64] = ok ? src[s] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
+__global__ __launch_bounds__(64) void lanes_from_f32_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                            int dpad, float* out) {
+    lanes_from_f32_block(codes, list_off, block_off, nlist, dpad, out, blockIdx.x);
+}
+// the same for the blocks listed in `blocks` (ivf_update.hip: the blocks an update changed)
+__global__ __launch_bounds__(64) void lanes_from_f32_list_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                            int dpad, float* out, const uint64_t* blocks) {
+    lanes_from_f32_block(codes, list_off, block_off, nlist, dpad, out, blocks[blockIdx.x]);
+}
 
 void launch_lanes_from_f32(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, uint64_t nblocks64, int dpad,
                            float* out, hipStream_t s) {
     if (nblocks64 == 0) return;
     LAUNCH(lanes_from_f32_kernel, dim3((unsigned)nblocks64), dim3(64), 0, s, codes, list_off, block_off, nlist, dpad, out);
+}
+void launch_lanes_from_f32_list(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, const uint64_t* blocks64,
+                                uint64_t nlisted, int dpad, float* out, hipStream_t s) {
+    if (nlisted == 0) return;
+    LAUNCH(lanes_from_f32_list_kernel, dim3((unsigned)nlisted), dim3(64), 0, s, codes, list_off, block_off, nlist, dpad, out, blocks64);
 }
 
 __global__ __launch_bounds__(256) void pack_queries_kernel(const float* queries, const uint32_t* pair_query, const uint32_t* group_p0,
@@ -1346,9 +1360,9 @@ void launch_scan_mfma(const MfmaScanArgs& a, hipStream_t s) {
 }
 
 // fp32 lists -> fragment order (one wave per 32-vector block; the block's list by bisection over block_off)
-__global__ __launch_bounds__(64) void frag_from_f32_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
-                                                           int d, int dpad, int metric, uint8_t* out, int32_t* cy) {
-    const uint64_t blk = blockIdx.x;
+// (one wave: block `blk` of the copy; the whole-copy kernel and the block-list kernel below share it)
+__device__ __forceinline__ void frag_from_f32_block(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                           int d, int dpad, int metric, uint8_t* out, int32_t* cy, uint64_t blk) {
     const int lane = threadIdx.x, v = lane & 31, h = lane >> 5;
     uint32_t lo = 0, hi = nlist;  // largest l with block_off[l] <= blk
     while (hi - lo > 1) {
@@ -1387,11 +1401,25 @@ __global__ __launch_bounds__(64) void frag_from_f32_kernel(const float* codes, c
     sum += __shfl_xor(sum, 32);
     if (h == 0) cy[blk * 32 + v] = !ok ? 0 : metric == METRIC_L2 ? sq : 128 * sum;
 }
+__global__ __launch_bounds__(64) void frag_from_f32_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                           int d, int dpad, int metric, uint8_t* out, int32_t* cy) {
+    frag_from_f32_block(codes, list_off, block_off, nlist, d, dpad, metric, out, cy, blockIdx.x);
+}
+// the same for the blocks listed in `blocks` (ivf_update.hip: the blocks an update changed)
+__global__ __launch_bounds__(64) void frag_from_f32_list_kernel(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                                                           int d, int dpad, int metric, uint8_t* out, int32_t* cy, const uint64_t* blocks) {
+    frag_from_f32_block(codes, list_off, block_off, nlist, d, dpad, metric, out, cy, blocks[blockIdx.x]);
+}
 
 void launch_frag_from_f32(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, uint64_t nblocks, int d,
                           int dpad, int metric, uint8_t* out, int32_t* cy, hipStream_t s) {
     if (nblocks == 0) return;
     LAUNCH(frag_from_f32_kernel, dim3((unsigned)nblocks), dim3(64), 0, s, codes, list_off, block_off, nlist, d, dpad, metric, out, cy);
+}
+void launch_frag_from_f32_list(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, const uint64_t* blocks,
+                               uint64_t nlisted, int d, int dpad, int metric, uint8_t* out, int32_t* cy, hipStream_t s) {
+    if (nlisted == 0) return;
+    LAUNCH(frag_from_f32_list_kernel, dim3((unsigned)nlisted), dim3(64), 0, s, codes, list_off, block_off, nlist, d, dpad, metric, out, cy, blocks);
 }
 
 // fp32 query rows -> signed byte rows (stride 32 ks, zero padded) + cx; one wave per row

@@ -76,6 +76,27 @@ int amd_ivf_list_size(const amd_ivf_t* h, size_t list_no, size_t* size);
 /* InvertedLists::get_codes / get_ids: copy one list back to the host */
 int amd_ivf_get_list(const amd_ivf_t* h, size_t list_no, float* codes, int64_t* ids);
 
+/* ---- changes of the lists in place ------------------------------------------------------
+ * amd_ivf_add, amd_ivf_update_lists and amd_ivf_remove_ids keep a journal of the entries they write; the next refresh of the device
+ * lists (the next search; these two entry points at once) builds the new layout in HBM from the old one and the written entries
+ * instead of sending every list again (option "incremental").  Either way the device then holds exactly what amd_ivf_set_lists of
+ * the same lists would have made.  With tickets out (amd_ivf_submit_*), these entry points, and an amd_ivf_add that would move the
+ * device layout, return -2 and leave the index as it was.  Owner only.
+ *
+ * entries changed since the last refresh: sizes = the nlist new list sizes; nw written entries at where[i] = list << 32 | offset
+ * (offset < sizes[list]), with ids[i] and the row codes[i*d .. i*d+d).  Every entry at or past its list's old size must be
+ * written; the others keep their value. */
+int amd_ivf_update_lists(amd_ivf_t* h, const size_t* sizes, size_t nw, const uint64_t* where, const int64_t* ids, const float* codes);
+/* IndexIVF::remove_ids with an IDSelectorBatch: the list's last entry takes a removed entry's place  [IndexIVF.cpp:955-987] */
+int amd_ivf_remove_ids(amd_ivf_t* h, size_t n, const int64_t* ids, size_t* nremoved);
+/* the last refresh of the device lists: {0 none / 1 incremental / 2 full, host-to-device bytes, entries written, 32-vector blocks
+ * re-encoded (per copy)} */
+int amd_ivf_last_update(amd_ivf_t* h, uint64_t out[4]);
+/* 64-bit digests of the device layout over its logical extent, padding included: offsets + block tables, rows, ids, byte
+ * fragments + cy, fp16 copy + yn + its range, fp32 copy + yn, lane copy, flags (0 for a copy that does not exist).  Refreshes the
+ * device lists first.  A test aid: it reads every buffer back. */
+int amd_ivf_layout_digest(amd_ivf_t* h, uint64_t out[8]);
+
 /* ---- search ---------------------------------------------------------------------------- */
 
 /* quantizer->search(n, x, nprobe, coarse_dis, keys)  [IndexFlat.cpp:42-56].
@@ -408,6 +429,10 @@ int amd_ivf_set_byte_codes(amd_ivf_t* h, int enable);
  *                     bound by the list stream, not by the queries probing it, so two queued 5000-query batches cost
  *                     little more than one; every query's result is what its own call would have returned.  Only
  *                     tickets already waiting are joined: a ticket alone in the queue runs alone
+ *   "incremental"     changes of the lists (amd_ivf_add, amd_ivf_update_lists, amd_ivf_remove_ids) reach the device as   1
+ *                     an in-place relayout in HBM that re-encodes only the blocks they touched (1), or as a full
+ *                     upload of every list (0); a journal that writes more than a quarter of the entries, or an
+ *                     allocation that fails, takes the full upload either way
  * amd_ivf_set_option(h, key, NAN) returns the key to "unset".  May be called while search contexts of the index are searching: a
  * search reads what shapes its launches once, when it starts, so the change takes effect with the searches that start after it. */
 int amd_ivf_set_option(amd_ivf_t* h, const char* key, double value);
