@@ -9,6 +9,7 @@ import numpy as np
 from . import build as _build
 
 METRIC_IP, METRIC_L2 = 0, 1
+SUBSET_ID_RANGE, SUBSET_ID_MOD, SUBSET_SLICE, SUBSET_ID_BITS, SUBSET_ID_BATCH = 0, 1, 2, 5, 6
 
 _f32p = C.POINTER(C.c_float)
 _i64p = C.POINTER(C.c_int64)
@@ -31,6 +32,7 @@ SYMBOLS = [
     "amd_ivf_range_search_preassigned", "amd_ivf_range_search", "amd_ivf_range_results",
     "amd_ivf_scan_arith",
     "amd_ivf_update_lists", "amd_ivf_remove_ids", "amd_ivf_last_update", "amd_ivf_layout_digest",
+    "amd_ivf_subset", "amd_ivf_last_subset",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -327,6 +329,27 @@ class Handle:
         """digests of the device layout: offsets, rows, ids, byte fragments, fp16 copy, fp32 copy, lane copy, flags"""
         out = (C.c_uint64 * 8)()
         _chk(lib().amd_ivf_layout_digest(self._h, out))
+        return tuple(int(v) for v in out)
+
+    # ---- a subset cut on the device (include/auncel_amd.h: amd_ivf_subset)
+    def subset(self, kind, a1=0, a2=0, sel=None):
+        """a read-only Handle over the members of every list, in order: SUBSET_ID_RANGE a1 <= id < a2, SUBSET_ID_MOD id % a1 == a2,
+        SUBSET_SLICE entries [a1, a2) of the running count, SUBSET_ID_BITS sel = uint64 words (bit id set), SUBSET_ID_BATCH sel = ids"""
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.uint64 if kind == SUBSET_ID_BITS else np.int64)
+        c = Handle.__new__(Handle)
+        c.d, c.nlist, c.metric, c.device = self.d, self.nlist, self.metric, self.device
+        c._h = C.c_void_p()
+        if hasattr(self, "max_topk"):
+            c.max_topk = self.max_topk
+        _chk(lib().amd_ivf_subset(self._h, int(kind), C.c_int64(int(a1)), C.c_int64(int(a2)), sel.ctypes.data_as(C.c_void_p) if sel is not None else None,
+                                  C.c_size_t(0 if sel is None else sel.shape[0]), C.byref(c._h)))
+        return c
+
+    def last_subset(self):
+        """(entries looked at, entries kept, host-to-device bytes, device-to-host bytes) of the call that made this subset"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_last_subset(self._h, out))
         return tuple(int(v) for v in out)
 
     # ---- search

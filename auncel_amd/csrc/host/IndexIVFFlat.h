@@ -42,4 +42,34 @@ struct IndexIVFFlatDedup : IndexIVFFlat {
     void expand_instances(idx_t n, idx_t k, float* distances, idx_t* labels) const;
 };
 
+/// A part of an IndexIVFFlat as an index of its own, cut ON THE DEVICE from the lists that are resident there (include/auncel_amd.h:
+/// amd_ivf_subset): list l holds the members of src's list l in src's order, as IndexIVF::copy_subset_to would fill a host index,
+/// but no row travels.  subset_type / a1 / a2 as copy_subset_to's types 0, 1, 2; an IDSelectorRange is type 0, an IDSelectorBatch
+/// goes as its ids, any other selector is "not implemented".  The quantizer, interdis_cem and the tuner's traces are taken as src's
+/// engine holds them.  Read-only: add / train / reset throw.  src may be destroyed first.  An IndexIVFFlatDedup is refused (its
+/// `instances` map is host state a subset would have to filter too).
+struct IndexIVFFlatSubset : Index {
+    size_t nlist;
+    size_t nprobe;
+    int coarse_mode;
+
+    IndexIVFFlatSubset(const IndexIVFFlat& src, int subset_type, idx_t a1, idx_t a2);
+    IndexIVFFlatSubset(const IndexIVFFlat& src, const IDSelector& sel);
+    IndexIVFFlatSubset(const IndexIVFFlatSubset&) = delete;
+    IndexIVFFlatSubset& operator=(const IndexIVFFlatSubset&) = delete;
+    ~IndexIVFFlatSubset() override;
+
+    void train(idx_t n, const float* x) override;
+    void add(idx_t n, const float* x) override;
+    void reset() override;
+    void search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const override;
+    void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result) const override;
+    bool device_bound() const override { return true; }
+    amd_ivf* engine() const { return gpu_; }
+
+   private:
+    amd_ivf* gpu_ = nullptr;
+    void cut(const IndexIVFFlat& src, int subset_type, idx_t a1, idx_t a2, const void* sel, size_t nsel);
+};
+
 }  // namespace faiss

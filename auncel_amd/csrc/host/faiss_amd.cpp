@@ -1274,6 +1274,59 @@ void IndexIVF::copy_subset_to(IndexIVF& other, int subset_type, idx_t a1, idx_t 
     FAISS_THROW_IF_NOT(seen == (size_t)ntotal);
 }
 
+// ------------------------------------------------------------------------------------- IndexIVFFlatSubset
+void IndexIVFFlatSubset::cut(const IndexIVFFlat& src, int subset_type, idx_t a1, idx_t a2, const void* sel, size_t nsel) {
+    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(&src) == nullptr, "a subset of an IndexIVFFlatDedup is not implemented");
+    FAISS_THROW_IF_NOT_MSG(src.is_trained, "the source index is not trained");
+    d = src.d;
+    metric_type = src.metric_type;
+    is_trained = true;
+    amd_device = src.amd_device;
+    nlist = src.nlist;
+    nprobe = src.nprobe;
+    coarse_mode = src.coarse_mode;
+    amd_ivf* parent = src.engine();  // (syncs src's engine: centroids, lists or their journal, interdis_cem)
+    AMD(amd_ivf_subset(parent, subset_type, (int64_t)a1, (int64_t)a2, sel, nsel, &gpu_));
+    size_t nt = 0;
+    AMD(amd_ivf_ntotal(gpu_, &nt));
+    ntotal = (idx_t)nt;
+}
+
+IndexIVFFlatSubset::IndexIVFFlatSubset(const IndexIVFFlat& src, int subset_type, idx_t a1, idx_t a2) : Index(src.d, src.metric_type) {
+    FAISS_THROW_IF_NOT_FMT(subset_type >= 0 && subset_type <= 2, "subset type %d not implemented on the device", subset_type);
+    cut(src, subset_type, a1, a2, nullptr, 0);
+}
+
+IndexIVFFlatSubset::IndexIVFFlatSubset(const IndexIVFFlat& src, const IDSelector& sel) : Index(src.d, src.metric_type) {
+    if (const IDSelectorRange* r = dynamic_cast<const IDSelectorRange*>(&sel)) {
+        cut(src, AMD_IVF_SUBSET_ID_RANGE, r->imin, r->imax, nullptr, 0);
+    } else if (const IDSelectorBatch* b = dynamic_cast<const IDSelectorBatch*>(&sel)) {
+        const std::vector<int64_t> ids(b->set.begin(), b->set.end());
+        cut(src, AMD_IVF_SUBSET_ID_BATCH, 0, 0, ids.data(), ids.size());
+    } else {
+        FAISS_THROW_MSG("a subset by this kind of IDSelector is not implemented");
+    }
+}
+
+IndexIVFFlatSubset::~IndexIVFFlatSubset() {
+    if (gpu_) amd_ivf_destroy(gpu_);
+}
+
+void IndexIVFFlatSubset::train(idx_t, const float*) { FAISS_THROW_MSG("a subset index is read-only: train its source"); }
+void IndexIVFFlatSubset::add(idx_t, const float*) { FAISS_THROW_MSG("a subset index is read-only: add to its source and cut again"); }
+void IndexIVFFlatSubset::reset() { FAISS_THROW_MSG("a subset index is read-only"); }
+
+void IndexIVFFlatSubset::search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const {
+    AMD(amd_ivf_search(gpu_, (size_t)n, x, (size_t)k, nprobe, coarse_mode, distances, i64(labels)));
+}
+
+void IndexIVFFlatSubset::range_search(idx_t nx, const float* x, float radius, RangeSearchResult* result) const {
+    AMD(amd_ivf_range_search(gpu_, (size_t)nx, x, radius, nprobe, coarse_mode, result->lims));
+    for (idx_t i = 0; i < nx; i++) result->lims[i] = result->lims[i + 1] - result->lims[i];  // (the engine's offsets -> counts)
+    result->do_allocation();
+    AMD(amd_ivf_range_results(gpu_, i64(result->labels), result->distances));
+}
+
 IndexShardsByList::IndexShardsByList(const IndexIVFFlat& index, int nshard, bool threaded_, const int* devices)
     : IndexShards((idx_t)index.d, threaded_, false) {
     FAISS_THROW_IF_NOT(nshard > 0 && index.is_trained);

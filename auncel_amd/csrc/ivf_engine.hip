@@ -338,6 +338,10 @@ struct amd_ivf {
     std::vector<uint64_t> journal;
     std::vector<IntRange> list_range;
     uint64_t last_update[4] = {0, 0, 0, 0};  // amd_ivf_last_update
+    // made by amd_ivf_subset (ivf_subset.hip): an index of its own whose lists were cut from another's on the device.  Read-only: it
+    // keeps no host copy of the rows (h_codes / h_ids stay empty; sizes come from h_list_off, amd_ivf_get_list reads the device)
+    bool is_subset = false;
+    uint64_t last_subset[4] = {0, 0, 0, 0};  // amd_ivf_last_subset
     PinnedBuf p_upd;
     DevBuf d_upd;
     DevBuf d_codes, d_ids, d_list_off, d_centroids, d_centroid_norms;
@@ -426,7 +430,7 @@ struct amd_ivf {
     DevBuf d_interdis;
     bool have_interdis = false;
     DevBuf d_arcos, d_trace_off, d_trace_x, d_trace_y, d_trace_std;
-    size_t tuner_max_topk = 0, tuner_ntraces = 0, tuner_trace_cap = 0;
+    size_t tuner_max_topk = 0, tuner_ntraces = 0, tuner_trace_cap = 0, tuner_trace_total = 0;
     bool have_tuner = false;
 
     // workspaces (grow only)
@@ -3398,6 +3402,9 @@ int amd_ivf_create(int d, size_t nlist, int metric, int device, amd_ivf_t** out)
 // Entry points that change or read back index data are for the owning handle only.
 #define OWNER_ONLY(h) \
     if ((h)->is_clone) throw EngineError("not available on a search context made by amd_ivf_clone: use the owning handle")
+// ... and those that change it are not for an index made by amd_ivf_subset
+#define NOT_A_SUBSET(h) \
+    if (ix(h)->is_subset) throw EngineError("the index is a read-only subset (amd_ivf_subset): make the change on its parent and cut again")
 
 int amd_ivf_clone(amd_ivf_t* h, amd_ivf_t** out) {
     API_BEGIN
@@ -3435,6 +3442,7 @@ int amd_ivf_destroy(amd_ivf_t* h) {
 int amd_ivf_set_centroids(amd_ivf_t* h, const float* centroids) {
     API_BEGIN
     OWNER_ONLY(h);
+    NOT_A_SUBSET(h);
     use_device(h);
     h->h_centroids.assign(h->nlist * h->dpad, 0.f);
     for (size_t i = 0; i < h->nlist; i++) memcpy(&h->h_centroids[i * h->dpad], centroids + i * h->d, h->d * sizeof(float));
@@ -3466,6 +3474,7 @@ int amd_ivf_set_centroids(amd_ivf_t* h, const float* centroids) {
 int amd_ivf_set_lists(amd_ivf_t* h, const size_t* sizes, const float* const* codes, const int64_t* const* ids) {
     API_BEGIN
     OWNER_ONLY(h);
+    NOT_A_SUBSET(h);
     size_t nt = 0;
     h->db_range = IntRange();
     for (size_t l = 0; l < h->nlist; l++) {
@@ -3489,6 +3498,7 @@ int amd_ivf_set_lists(amd_ivf_t* h, const size_t* sizes, const float* const* cod
 int amd_ivf_add(amd_ivf_t* h, size_t n, const float* x, const int64_t* xids, const int64_t* precomputed_idx) {
     API_BEGIN
     OWNER_ONLY(h);
+    NOT_A_SUBSET(h);
     use_device(h);
     // (the device layout moves at the next search: not under searches that are still running)
     const bool journal = !h->lists_dirty && opt(h, OPT_INCREMENTAL, 1) != 0;
@@ -3546,7 +3556,8 @@ int amd_ivf_ntotal(const amd_ivf_t* h, size_t* ntotal) {
 int amd_ivf_list_size(const amd_ivf_t* h, size_t list_no, size_t* size) {
     API_BEGIN
     if (list_no >= h->nlist) throw EngineError("Invalid list number");
-    *size = ix(h)->h_ids[list_no].size();
+    const amd_ivf* o = ix(h);
+    *size = o->is_subset ? o->h_list_off[list_no + 1] - o->h_list_off[list_no] : o->h_ids[list_no].size();
     API_END
 }
 
@@ -4141,6 +4152,7 @@ int amd_ivf_set_tuner(amd_ivf_t* h, size_t max_topk, size_t ntraces, const size_
     h->tuner_max_topk = max_topk;
     h->tuner_ntraces = ntraces;
     h->tuner_trace_cap = 0;
+    h->tuner_trace_total = x.size();
     for (size_t i = 0; i < ntraces; i++) h->tuner_trace_cap = std::max(h->tuner_trace_cap, trace_len[i]);
     h->have_tuner = true;
     API_END
@@ -5601,6 +5613,7 @@ int amd_ivf_update_lists(amd_ivf_t* h, const size_t* sizes, size_t nw, const uin
     API_BEGIN
     if (!h) throw EngineError("null handle");
     OWNER_ONLY(h);
+    NOT_A_SUBSET(h);
     if (!sizes || (nw && (!where || !ids || !codes))) throw EngineError("null argument");
     const size_t nlist = h->nlist, dpad = h->dpad, d = h->d;
     // every check before anything changes: places inside the new sizes, every entry past a list's old size written
@@ -5653,6 +5666,7 @@ int amd_ivf_remove_ids(amd_ivf_t* h, size_t n, const int64_t* ids, size_t* nremo
     API_BEGIN
     if (!h) throw EngineError("null handle");
     OWNER_ONLY(h);
+    NOT_A_SUBSET(h);
     if (!nremoved || (n && !ids)) throw EngineError("null argument");
     *nremoved = 0;
     refuse_with_tickets(h);
@@ -5741,6 +5755,203 @@ int amd_ivf_layout_digest(amd_ivf_t* h, uint64_t out[8]) {
     out[7] = digest_bytes(&pl, sizeof(pl), digest_bytes(flags, sizeof(flags)));
     for (int i = 0; i < 8; i++)
         if (out[i] == 0 && (i == 0 || i == 7)) out[i] = 1;
+    API_END
+}
+
+// ------------------------------------------------------------------------------------ subset of a resident index
+// A new index on h's device whose list l holds the members of h's list l in h's order, cut in HBM (ivf_subset.hip): the device then
+// holds what amd_ivf_set_lists of the filtered lists would have made.  What crosses PCIe: the selector in, the SLICE runs in, the
+// offsets and the block table out, 16 bytes of value range each way.
+int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const void* sel, size_t nsel, amd_ivf_t** out) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("null argument");
+    *out = nullptr;
+    OWNER_ONLY(h);
+    const bool by_sel = subset_type == SUBSET_ID_BITS || subset_type == SUBSET_ID_BATCH;
+    if (subset_type != SUBSET_ID_RANGE && subset_type != SUBSET_ID_MOD && subset_type != SUBSET_SLICE && !by_sel)
+        throw EngineError("subset: unknown subset type (by-list subsets are made on the host)");
+    if (subset_type == SUBSET_ID_MOD && a1 <= 0) throw EngineError("subset: ID_MOD wants a1 > 0");
+    if (subset_type == SUBSET_SLICE && (a1 < 0 || a1 > a2 || (uint64_t)a2 > (uint64_t)h->ntotal))
+        throw EngineError("subset: SLICE wants 0 <= a1 <= a2 <= ntotal");
+    if (by_sel && !sel && nsel) throw EngineError("subset: null selector");
+    if (tickets_out(h)) throw EngineError("tickets are still out: wait for them before cutting a subset");
+    use_device(h);
+    upload_lists(h);  // (a pending journal or dirty lists: the subset sees every amd_ivf_add made before the call)
+    std::lock_guard<std::mutex> lock(h->upload_mu);
+    const size_t nlist = h->nlist;
+    const int d = h->d, dpad = h->dpad;
+    const uint64_t nt = h->h_list_off[nlist];
+    for (size_t l = 0; l < nlist; l++)
+        if ((h->h_list_off[l + 1] - h->h_list_off[l]) >> 32) throw EngineError("subset: list too long");
+    std::unique_ptr<amd_ivf> s(new amd_ivf);
+    s->is_subset = true;
+    s->d = d;
+    s->dpad = dpad;
+    s->nlist = nlist;
+    s->metric = h->metric;
+    s->device = h->device;
+    s->dist_budget_floats = h->dist_budget_floats;
+    s->allow_fused = h->allow_fused;
+    s->allow_bytes = h->allow_bytes;
+    s->allow_filter = h->allow_filter;
+    for (int i = 0; i < N_OPT; i++) s->opt.v[i].store(h->opt.v[i].load(std::memory_order_relaxed), std::memory_order_relaxed);
+    s->stream = make_main_stream();
+    ensure_context_streams(s.get());
+    s->h_codes.resize(nlist);
+    s->h_ids.resize(nlist);
+    s->list_range.resize(nlist);
+    s->h_list_off.assign(nlist + 1, 0);
+    hipStream_t st = s->stream;
+    uint64_t h2d = 0, d2h = 0;
+    auto d2d = [&](DevBuf& dst, const DevBuf& src, size_t bytes) {
+        if (!src.p || !bytes) return;
+        dst.ensure(bytes);
+        HIP_CHECK(hipMemcpyAsync(dst.p, src.p, bytes, hipMemcpyDeviceToDevice, st));
+    };
+    // the quantizer and the Auncel state: device to device, the small host mirrors host to host
+    if (h->have_centroids) {
+        d2d(s->d_centroids, h->d_centroids, nlist * dpad * sizeof(float));
+        d2d(s->d_centroid_norms, h->d_centroid_norms, nlist * sizeof(float));
+        d2d(s->d_cinfo, h->d_cinfo, 16);
+        s->h_centroids = h->h_centroids;
+        s->centroid_norm_max = h->centroid_norm_max;
+        s->centroid_range = h->centroid_range;
+        s->have_centroids = true;
+    }
+    if (h->have_interdis) {
+        d2d(s->d_interdis, h->d_interdis, std::max<size_t>(nlist * (nlist - 1) / 2, 1) * 4);
+        s->have_interdis = true;
+    }
+    if (h->have_tuner) {
+        d2d(s->d_trace_off, h->d_trace_off, (h->tuner_ntraces + 1) * 4);
+        d2d(s->d_trace_x, h->d_trace_x, h->tuner_trace_total * 4);
+        d2d(s->d_trace_y, h->d_trace_y, h->tuner_trace_total * 4);
+        d2d(s->d_trace_std, h->d_trace_std, h->tuner_trace_total * 4);
+        d2d(s->d_arcos, h->d_arcos, 500 * 4);
+        s->tuner_max_topk = h->tuner_max_topk;
+        s->tuner_ntraces = h->tuner_ntraces;
+        s->tuner_trace_cap = h->tuner_trace_cap;
+        s->tuner_trace_total = h->tuner_trace_total;
+        s->have_tuner = true;
+    }
+    uint64_t kept = 0;
+    if (nt > 0) {
+        const uint64_t nwords = h->h_block_off[nlist] / 2;
+        DevBuf b_sel, b_mask, b_cnt, b_rank, b_tot, b_range;
+        SubsetSel ss{subset_type, a1, a2, nullptr, nullptr, nullptr, 0};
+        std::vector<uint64_t> runs;
+        std::vector<int64_t> batch;
+        if (subset_type == SUBSET_SLICE) {
+            // IndexIVF::copy_subset_to, type 2: the run of every list from the running count
+            runs.assign(2 * nlist, 0);
+            uint64_t cut1 = 0, cut2 = 0;
+            for (size_t l = 0; l < nlist; l++) {
+                const uint64_t next = h->h_list_off[l + 1], n1 = next * (uint64_t)a1 / nt, n2 = next * (uint64_t)a2 / nt;
+                runs[2 * l] = n1 - cut1;
+                runs[2 * l + 1] = n2 - cut2;
+                cut1 = n1;
+                cut2 = n2;
+            }
+            b_sel.ensure(runs.size() * 8);
+            HIP_CHECK(hipMemcpyAsync(b_sel.p, runs.data(), runs.size() * 8, hipMemcpyHostToDevice, st));
+            h2d += runs.size() * 8;
+            ss.runs = b_sel.as<uint64_t>();
+        } else if (subset_type == SUBSET_ID_BATCH) {
+            const int64_t* p = static_cast<const int64_t*>(sel);
+            batch.assign(p, p + nsel);
+            std::sort(batch.begin(), batch.end());
+            batch.erase(std::unique(batch.begin(), batch.end()), batch.end());
+            b_sel.ensure(std::max<size_t>(batch.size(), 1) * 8);
+            if (!batch.empty()) HIP_CHECK(hipMemcpyAsync(b_sel.p, batch.data(), batch.size() * 8, hipMemcpyHostToDevice, st));
+            h2d += batch.size() * 8;
+            ss.batch = b_sel.as<int64_t>();
+            ss.nsel = batch.size();
+        } else if (subset_type == SUBSET_ID_BITS) {
+            b_sel.ensure(std::max<size_t>(nsel, 1) * 8);
+            if (nsel) HIP_CHECK(hipMemcpyAsync(b_sel.p, sel, nsel * 8, hipMemcpyHostToDevice, st));
+            h2d += nsel * 8;
+            ss.bits = b_sel.as<uint64_t>();
+            ss.nsel = nsel;
+        }
+        b_mask.ensure(nwords * 8);
+        b_cnt.ensure(nwords * 4);
+        b_rank.ensure(nwords * 4);
+        b_tot.ensure(nlist * 8);
+        s->d_list_off.ensure((nlist + 1) * 8);
+        s->d_block_off.ensure((nlist + 1) * 8);
+        const uint64_t* p_off = h->d_list_off.as<uint64_t>();
+        const uint64_t* p_boff = h->d_block_off.as<uint64_t>();
+        launch_subset_member(h->d_ids.as<int64_t>(), p_off, p_boff, (uint32_t)nlist, nwords, ss, b_mask.as<uint64_t>(), b_cnt.as<uint32_t>(), st);
+        launch_subset_offsets(b_cnt.as<uint32_t>(), p_boff, (uint32_t)nlist, b_rank.as<uint32_t>(), b_tot.as<uint64_t>(), s->d_list_off.as<uint64_t>(),
+                              s->d_block_off.as<uint64_t>(), st);
+        s->h_block_off.assign(nlist + 1, 0);
+        HIP_CHECK(hipMemcpyAsync(s->h_list_off.data(), s->d_list_off.p, (nlist + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(s->h_block_off.data(), s->d_block_off.p, (nlist + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(stream_sync(st));
+        d2h += 2 * (nlist + 1) * 8;
+        kept = s->h_list_off[nlist];
+        if (kept > nt) throw std::runtime_error("subset: more entries kept than looked at");
+        if (kept) {
+            s->d_codes.ensure(kept * dpad * sizeof(float));
+            s->d_ids.ensure(kept * sizeof(int64_t));
+            uint32_t rg[4] = {0, subset_range_key(0.f), subset_range_key(0.f), 0};
+            b_range.ensure(16);
+            HIP_CHECK(hipMemcpyAsync(b_range.p, rg, 16, hipMemcpyHostToDevice, st));
+            launch_subset_compact(h->d_codes.as<float>(), h->d_ids.as<int64_t>(), p_off, p_boff, (uint32_t)nlist, nwords, b_mask.as<uint64_t>(),
+                                  b_rank.as<uint32_t>(), s->d_list_off.as<uint64_t>(), dpad, s->d_codes.as<float>(), s->d_ids.as<int64_t>(),
+                                  b_range.as<uint32_t>(), st);
+            HIP_CHECK(hipMemcpyAsync(rg, b_range.p, 16, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(stream_sync(st));
+            h2d += 16;
+            d2h += 16;
+            // byte eligibility over the KEPT values: a subset can qualify where its parent does not
+            s->db_range.ok = rg[0] == 0;
+            s->db_range.lo = subset_range_value(rg[1]);
+            s->db_range.hi = subset_range_value(rg[2]);
+        }
+    }
+    if (kept == 0) {  // an index with empty lists, as amd_ivf_set_lists of none
+        s->h_list_off.assign(nlist + 1, 0);
+        s->d_block_off.release();
+        s->db_range = IntRange();
+        s->ntotal = 0;
+        s->lists_dirty = true;
+        upload_lists(s.get());
+        h2d += (nlist + 1) * 8;
+    } else {  // (what upload_lists derives from the lists)
+        s->ntotal = kept;
+        s->have_codes8 = s->allow_bytes && s->db_range.bytes() && (double)d * 255.0 * 255.0 < 2147483648.0;
+        s->frag32_possible = s->allow_filter && kept < 0xffffffffull;
+        double s1 = 0, s2 = 0;
+        for (size_t l = 0; l < nlist; l++) {
+            const double len = (double)(s->h_list_off[l + 1] - s->h_list_off[l]);
+            s1 += len;
+            s2 += len * len;
+        }
+        s->probed_len = s1 > 0 ? s2 / s1 : 0.0;
+        if (s->have_codes8) {
+            const uint64_t nblk = s->h_block_off[nlist];
+            s->d_frag.ensure(nblk * mfma_ksteps(d) * 1024);
+            s->d_cy.ensure(nblk * 32 * sizeof(int32_t));
+            launch_frag_from_f32(s->d_codes.as<float>(), s->d_list_off.as<uint64_t>(), s->d_block_off.as<uint64_t>(), (uint32_t)nlist, nblk, d, dpad,
+                                 s->metric, s->d_frag.as<uint8_t>(), s->d_cy.as<int32_t>(), st);
+        }
+        HIP_CHECK(stream_sync(st));
+        s->lists_dirty = false;
+    }
+    HIP_CHECK(stream_sync(st));
+    s->last_subset[0] = nt;
+    s->last_subset[1] = kept;
+    s->last_subset[2] = h2d;
+    s->last_subset[3] = d2h;
+    *out = s.release();
+    API_END
+}
+
+int amd_ivf_last_subset(amd_ivf_t* sub, uint64_t out[4]) {
+    API_BEGIN
+    if (!sub || !out) throw EngineError("null argument");
+    for (int i = 0; i < 4; i++) out[i] = ix(sub)->last_subset[i];
     API_END
 }
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <stdexcept>
 #include <string>
@@ -695,5 +696,41 @@ void launch_scatter_rows(const uint64_t* rows, const int64_t* wids, const float*
 // side (or null): side_bytes a block (cy, yn)
 void launch_relayout_blocks(const void* old_main, void* new_main, uint64_t block_bytes, const void* old_side, void* new_side, uint64_t side_bytes,
                             const uint64_t* old_boff, const uint64_t* new_boff, uint32_t nlist, uint64_t nblk_new, int shift, hipStream_t s);
+
+// ---------------------------------------------------------------------------- subset of a resident index (ivf_subset.hip)
+// Which entries a subset keeps (include/auncel_amd.h: amd_ivf_subset).  Every array is device memory.
+constexpr int SUBSET_ID_RANGE = 0, SUBSET_ID_MOD = 1, SUBSET_SLICE = 2, SUBSET_ID_BITS = 5, SUBSET_ID_BATCH = 6;
+struct SubsetSel {
+    int type;
+    int64_t a1, a2;          // ID_RANGE: a1 <= id < a2; ID_MOD: id % a1 == a2
+    const uint64_t* runs;    // SLICE: entries [runs[2 l], runs[2 l + 1]) of list l
+    const uint64_t* bits;    // ID_BITS: nsel words
+    const int64_t* batch;    // ID_BATCH: nsel ids, ascending, each once
+    uint64_t nsel;
+};
+// The keep-mask of the parent's entries: word w covers 64 consecutive entries of ONE list (list l owns words block_off[l] / 2 ..
+// block_off[l + 1] / 2: the 64-vector blocks of the padded copies), bit i of it entry 64 (w - first word) + i; count[w] = its set bits.
+void launch_subset_member(const int64_t* ids, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, uint64_t nwords,
+                          const SubsetSel& sel, uint64_t* mask, uint32_t* count, hipStream_t s);
+// rank_base[w] = kept entries of w's list before word w; then the kept lists' offsets and block table (nlist + 1 each)
+void launch_subset_offsets(const uint32_t* count, const uint64_t* block_off, uint32_t nlist, uint32_t* rank_base, uint64_t* list_total,
+                           uint64_t* new_off, uint64_t* new_block_off, hipStream_t s);
+// kept rows (stride dpad) and ids to their places, in the parent's order; range = {some value is not an integer of magnitude <= 4095,
+// order key of the smallest value, of the largest, -} over the kept rows, started by the caller at {0, key(0), key(0), 0}
+// (subset_range_key / subset_range_value)
+void launch_subset_compact(const float* old_codes, const int64_t* old_ids, const uint64_t* old_off, const uint64_t* old_block_off, uint32_t nlist,
+                           uint64_t nwords, const uint64_t* mask, const uint32_t* rank_base, const uint64_t* new_off, int dpad, float* codes,
+                           int64_t* ids, uint32_t* range, hipStream_t s);
+inline uint32_t subset_range_key(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
+}
+inline float subset_range_value(uint32_t key) {
+    const uint32_t u = (key & 0x80000000u) ? key ^ 0x80000000u : ~key;
+    float x;
+    memcpy(&x, &u, 4);
+    return x;
+}
 
 }  // namespace amdivf

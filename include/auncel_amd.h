@@ -97,6 +97,28 @@ int amd_ivf_last_update(amd_ivf_t* h, uint64_t out[4]);
  * device lists first.  A test aid: it reads every buffer back. */
 int amd_ivf_layout_digest(amd_ivf_t* h, uint64_t out[8]);
 
+/* ---- a subset index, cut on the device -------------------------------------------------
+ * IndexIVF::copy_subset_to  [IndexIVF.cpp, subset types 0, 1, 2] and selectors of ids, applied to the index that is resident in
+ * HBM: *out is an index of its own on h's device -- same d, nlist, metric -- whose list l holds the members of h's list l, in h's
+ * order, with their ids.  No list row crosses PCIe: a keep-mask, the kept lists' offsets and a stable compaction of rows and ids are
+ * made by three passes over the device lists, and the device then holds exactly what amd_ivf_set_lists of the
+ * filtered lists would have made (byte eligibility is taken over the kept values: a subset can qualify where its parent does not).
+ * Centroids, the centroid table of amd_ivf_set_interdis, the tuner and the options are copied from h; the subset borrows nothing,
+ * so h may be destroyed first.  A pending amd_ivf_add of h is applied first; h itself is not changed.
+ * The subset is read-only: every search entry point, amd_ivf_clone, tickets, range search, the scanner calls, amd_ivf_get_list,
+ * sizes, options and amd_ivf_subset of it work; amd_ivf_add, amd_ivf_set_lists, amd_ivf_update_lists, amd_ivf_remove_ids and
+ * amd_ivf_set_centroids return -2.  Returns -2 before the device is touched for: a null h / out, h a clone, tickets out on h, an
+ * unknown type, a1 <= 0 (ID_MOD), a1 > a2 or a2 > ntotal (SLICE), sel == NULL with nsel > 0.  An empty result is a valid index
+ * of ntotal 0.  (Types 3 and 4, the by-list subsets of the class mirror, stay on the host.) */
+#define AMD_IVF_SUBSET_ID_RANGE 0 /* a1 <= id < a2                           copy_subset_to type 0 */
+#define AMD_IVF_SUBSET_ID_MOD 1   /* id % a1 == a2 (C++ %, as the reference) copy_subset_to type 1 */
+#define AMD_IVF_SUBSET_SLICE 2    /* entries [n1, n2) of the running count,  copy_subset_to type 2 */
+#define AMD_IVF_SUBSET_ID_BITS 5  /* sel = uint64 words, nsel of them: id is a member iff 0 <= id < 64 nsel and bit id is set */
+#define AMD_IVF_SUBSET_ID_BATCH 6 /* sel = nsel int64 ids in any order, repeats allowed (IDSelectorBatch) */
+int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const void* sel, size_t nsel, amd_ivf_t** out);
+/* {entries looked at, entries kept, host-to-device bytes, device-to-host bytes} of the call that made `sub` */
+int amd_ivf_last_subset(amd_ivf_t* sub, uint64_t out[4]);
+
 /* ---- search ---------------------------------------------------------------------------- */
 
 /* quantizer->search(n, x, nprobe, coarse_dis, keys)  [IndexFlat.cpp:42-56].
