@@ -176,9 +176,11 @@ struct IntRange {
         if (metric == METRIC_L2) return h - l <= 4096.f;
         return h <= 4095.f && l >= -4095.f;
     }
-    // Byte-code scan (scan_tiles_kernel, ARITH 2): both sides hold integers 0..255 and no sum of d products can pass
-    // 2^24, so the reference's fp32 partial sums are exact integers in any order and integer arithmetic gives the
-    // same fp32 distance bit for bit.
+    // Byte-code scan (the MFMA kernels of ivf_kernels.hip: scan_mfma_thr_kernel / scan_mfma_pair_kernel up to four K-steps,
+    // scan_mfma_kernel<.., 0> for any d; scan_arith 2): both sides hold integers 0..255 and no sum of d products can pass
+    // 2^24 (m = the largest value over lists AND queries: 255 up to d = 258, 132 at d = 960, 64 at d = 4096), so the
+    // reference's fp32 partial sums are exact integers in any order and integer arithmetic gives the same fp32 distance
+    // bit for bit.  tests/test_gpu_wide_bytes.py holds both sides of this rule.
     bool bytes() const { return ok && lo >= 0.f && hi <= 255.f; }
     bool bytes_with(const IntRange& o, size_t d) const {
         const double m = std::max(hi, o.hi);

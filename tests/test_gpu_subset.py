@@ -5,11 +5,11 @@ over them.  Every comparison is of bits or of integers."""
 import numpy as np
 import pytest
 
-from test_gpu_update import K, NPROBE, NQ, Model, bits, handle, make_case, new_rows, warm
+from test_gpu_update import BYTE_CASES, K, NPROBE, NQ, Model, bits, handle, make_case, new_rows, warm
 
 pytestmark = pytest.mark.gpu
 
-CASES = ["sift_l2", "l2_96", "ip_96", "odd_30", "ragged"]
+CASES = ["sift_l2", "l2_96", "ip_96", "odd_30", "ragged", "bytes_200", "bytes_960"]
 SELECTORS = ["range_third", "mod_3_1", "slice_mid", "bits_half", "bits_1pct", "bits_all", "bits_none", "batch_200", "bits_lists"]
 
 
@@ -153,11 +153,13 @@ def test_subset_equals_set_lists_of_the_filtered_lists(capi, oracle, name, sel_n
     ref = from_lists(capi, metric, cen, want)
     dg = check_subset(capi, sub, ref, want, xq, len(xb), sel)
     if sub.ntotal:
-        if name == "sift_l2":
+        if name in BYTE_CASES:
             assert dg[3], "no byte fragments"
         else:
             assert dg[4] and dg[5] and dg[6], "the warm-up did not build every fp32 copy"
     eD, eI = check_searches(oracle, sub, metric, cen, want, xq)
+    if sub.ntotal and name in BYTE_CASES:
+        assert sub.scan_arith() == 2
     if sel_name == "mod_3_1":  # one case per metric (and shape) also through a clone and through a ticket
         c = sub.clone()
         D, I = c.search(xq, K, NPROBE)
@@ -245,6 +247,30 @@ def test_byte_eligibility_is_taken_over_the_kept_values(capi, oracle):
     assert odd.ntotal == 20 and odd.layout_digest()[3] == 0
     for h in (odd, sub, ref, parent):
         h.close()
+    # the same by magnitude at d = 960 (960 * 132^2 <= 2^24 < 960 * 133^2): three rows holding 133 keep the parent's searches in fp32;
+    # a subset without them searches its byte codes, one with them does not -- each as a handle that uploaded the kept lists in full
+    metric, cen, assign, xb, xq = make_case("bytes_960")
+    nlist, d = cen.shape
+    parent = handle(capi, metric, cen, xb, assign, 1)
+    model = Model(nlist, d, xb, assign)
+    x = xb[20:23].copy()
+    x[:, 0] = 133.0
+    lists, ids = np.array([2, 2, 11]), np.arange(100000, 100003, dtype=np.int64)
+    parent.add(x, ids, lists)
+    model.add(x, ids, lists)
+    check_searches(oracle, parent, metric, cen, model, xq)
+    assert parent.scan_arith() == 1
+    for a1, a2, arith in ((0, len(xb), 2), (len(xb) // 2, 100003, 1), (100000, 100003, 1)):
+        want = filtered(model, lambda i, l, seen: (i >= a1) & (i < a2))
+        sub = parent.subset(capi.SUBSET_ID_RANGE, a1, a2)
+        ref = from_lists(capi, metric, cen, want)
+        dg = check_subset(capi, sub, ref, want, xq, len(xb) + 3, None)
+        assert dg[3] != 0
+        for h in (sub, ref):
+            check_searches(oracle, h, metric, cen, want, xq)
+            assert h.scan_arith() == arith, (a1, a2, h.scan_arith())
+            h.close()
+    parent.close()
 
 
 @pytest.mark.parametrize("name", ["sift_l2", "ip_96"])

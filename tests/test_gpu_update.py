@@ -8,6 +8,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 K, NPROBE, NQ = 10, 8, 256
+# byte-valued cases: name -> (d, metric, largest value m, half-width of the noise around a centre).  The wide ones sit at the edge of
+# the byte-code rule d m^2 <= 2^24 and are scanned by the any-d form of the MFMA kernel (more than four K-steps)
+BYTE_CASES = {"sift_l2": (128, 1, 255, 25), "bytes_200": (200, 1, 255, 25), "bytes_960": (960, 0, 132, 12)}
 
 
 @pytest.fixture(scope="module")
@@ -30,6 +33,14 @@ def make_case(name, seed=3, nlist=16):
         assign = rs.randint(0, nlist, size=nb)
         xb = np.clip(cen[assign] + rs.randint(-25, 26, size=(nb, d)), 0, 255).astype(np.float32)
         xq = np.clip(cen[rs.randint(0, nlist, size=NQ)] + rs.randint(-25, 26, size=(NQ, d)), 0, 255).astype(np.float32)
+        return metric, cen, assign, xb, xq
+    if name in BYTE_CASES:
+        d, metric, m, w = BYTE_CASES[name]
+        cen = rs.randint(m // 25, m - m // 5, size=(nlist, d)).astype(np.float32)
+        assign = rs.randint(0, nlist, size=nb)
+        xb = np.clip(cen[assign] + rs.randint(-w, w + 1, size=(nb, d)), 0, m).astype(np.float32)
+        xq = np.clip(cen[rs.randint(0, nlist, size=NQ)] + rs.randint(-w, w + 1, size=(NQ, d)), 0, m).astype(np.float32)
+        xb[0], xq[0] = m, m  # the largest value is met on both sides
         return metric, cen, assign, xb, xq
     d, metric = {"l2_96": (96, 1), "ip_96": (96, 0), "odd_30": (30, 1), "ragged": (64, 1)}[name]
     cen = rs.randn(nlist, d).astype(np.float32)
@@ -141,10 +152,13 @@ def oracle_check(oracle, h, metric, cen, model, xq):
 def new_rows(rs, name, cen, lists):
     if name == "sift_l2":
         return np.clip(cen[lists] + rs.randint(-25, 26, size=(len(lists), cen.shape[1])), 0, 255).astype(np.float32)
+    if name in BYTE_CASES:
+        _, _, m, w = BYTE_CASES[name]
+        return np.clip(cen[lists] + rs.randint(-w, w + 1, size=(len(lists), cen.shape[1])), 0, m).astype(np.float32)
     return (cen[lists] + 0.3 * rs.randn(len(lists), cen.shape[1])).astype(np.float32)
 
 
-@pytest.mark.parametrize("name", ["sift_l2", "l2_96", "ip_96", "odd_30", "ragged"])
+@pytest.mark.parametrize("name", ["sift_l2", "l2_96", "ip_96", "odd_30", "ragged", "bytes_200", "bytes_960"])
 def test_layout_equals_full_upload(capi, oracle, name):
     metric, cen, assign, xb, xq = make_case(name)
     nlist, d = cen.shape
@@ -155,11 +169,13 @@ def test_layout_equals_full_upload(capi, oracle, name):
     warm(A, xq)
     warm(B, xq)
     assert A.layout_digest() == B.layout_digest()
-    if name != "sift_l2":
+    if name not in BYTE_CASES:
         dg = A.layout_digest()
         assert dg[4] and dg[5] and dg[6], "the warm-up did not build every fp32 copy"
     else:
         assert A.layout_digest()[3], "no byte fragments"
+        A.search(xq, K, NPROBE)
+        assert A.scan_arith() == 2
     next_id = [len(xb) + 1000]
 
     def add(lists):
@@ -199,6 +215,8 @@ def test_layout_equals_full_upload(capi, oracle, name):
     add(list(range(nlist)))
     check_step(A, B, model, xq, "add again")
     eD, eI = oracle_check(oracle, A, metric, cen, model, xq)
+    if name in BYTE_CASES:
+        assert A.scan_arith() == 2
     D, I = B.search(xq, K, NPROBE)
     assert np.array_equal(I, eI) and np.array_equal(bits(D), bits(eD))
     c = A.clone()
@@ -234,6 +252,57 @@ def test_byte_eligibility_flips_as_the_full_path(capi, oracle):
     A.search(xq, K, NPROBE)
     assert A.scan_arith() == 2 and A.layout_digest()[3] != 0
     oracle_check(oracle, A, metric, cen, model, xq)
+    for h in (A, B):
+        h.close()
+    # the same by magnitude at d = 960 (960 * 132^2 <= 2^24 < 960 * 133^2): a row holding 133 still has byte codes, but no search may
+    # use them; without it they are used again.  After each step: scan_arith, the layout and the results of a full upload.
+    metric, cen, assign, xb, xq = make_case("bytes_960")
+    nlist, d = cen.shape
+    A = handle(capi, metric, cen, xb, assign, 1)
+    B = handle(capi, metric, cen, xb, assign, 0)
+    model = Model(nlist, d, xb, assign)
+
+    def fresh():
+        fb, fa, fi = model.flat()
+        h = capi.Handle(d, nlist, metric, 0)
+        h.set_centroids(cen)
+        h.set_lists_from_assign(fb, fa, fi)
+        return h
+
+    def same_as_full_upload(what, want):
+        C = fresh()
+        check_step(A, B, model, xq, what)
+        warm(C, xq)
+        assert A.layout_digest() == C.layout_digest(), what
+        for h in (A, B, C):
+            oracle_check(oracle, h, metric, cen, model, xq)
+            assert h.scan_arith() == want, (what, h.scan_arith())
+        C.close()
+
+    A.search(xq, K, NPROBE)
+    assert A.scan_arith() == 2
+    v = xb[7:8].copy()
+    v[0, d - 1] = 133.0
+    for h in (A, B):
+        h.add(v, np.array([99999]), np.array([5]))
+    model.add(v, [99999], [5])
+    same_as_full_upload("a row holding 133", 1)
+    assert A.layout_digest()[3] != 0  # (byte codes are kept while every value fits the type; the search decides by magnitude)
+    for h in (A, B):
+        assert h.remove_ids(np.array([99999])) == 1
+    model.remove_ids([99999])
+    same_as_full_upload("its removal", 2)
+    # ... and through update_lists: the value written over an entry, then overwritten again
+    sizes = [len(i) for i in model.ids]
+    w = np.array([(6 << 32) | 2], np.uint64)
+    for h in (A, B):
+        h.update_lists(sizes, w, np.array([88888]), v)
+    model.update(sizes, w, [88888], v)
+    same_as_full_upload("133 written over an entry", 1)
+    for h in (A, B):
+        h.update_lists(sizes, w, np.array([88889]), xb[9:10])
+    model.update(sizes, w, [88889], xb[9:10])
+    same_as_full_upload("overwritten again", 2)
 
 
 def test_fp16_scale_change(capi, oracle):
