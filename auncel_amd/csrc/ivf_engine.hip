@@ -471,7 +471,7 @@ struct amd_ivf {
     DevBuf c_pair_query, c_pair_out, c_items, c_group_p0, c_group_cnt;  // the coarse quantiser's work list (coarse_dev), kept
     uint64_t coarse_sig = 0;                                             // while its signature (chunk, queries, nlist) repeats
     bool coarse_sig_valid = false;
-    PinnedBuf p_items, p_pair_query, p_pair_out, p_seg_off, p_seg_list, p_seg_count, p_qsel, p_seg_begin;
+    PinnedBuf p_items, p_pair_query, p_pair_out, p_seg_off, p_seg_list, p_seg_count;
     DevBuf w_seg_begin;
     DevBuf w_log, w_log_cnt, w_amb, w_tie_flag;  // sorted-array selection: admission logs, ambiguity marks, tie_fix flags
     DevBuf w_qstat;     // per query: lists scanned, heap updates (what a query searched again takes out of the statistics)
@@ -1230,17 +1230,11 @@ std::vector<uint32_t> pack_query_tiles(amd_ivf* h, const float* d_queries, const
 }
 
 // ------------------------------------------------------------------------------------ rounds
+// What a search hands to run_rounds_device: the queries and their coarse ranking on the device, and what the rounds do with them.
 struct RoundSpec {
-    // participating query slots and, for each, the probes [p0, p0+cnt) to run this round
-    std::vector<uint32_t> slot;
-    std::vector<uint32_t> p0, cnt;
-    const int64_t* keys = nullptr;  // host, [.. x key_stride], row = slot
-    size_t key_stride = 0;
     int k = 0;
     int store_pairs = 0;
     size_t max_codes = 0;
-    int finalize_all = 0;
-    uint32_t total_nprobe = 0;
     uint64_t id_offset = 0;
     const float* d_x = nullptr;  // device queries, row = slot
     bool bytes = false;          // scan the byte copies (ws->w_x8 / w_xnorm8 hold these queries)
@@ -1251,17 +1245,8 @@ struct RoundSpec {
     const float* d_cdis = nullptr;     // device coarse arrays for set_online (row = slot)
     const int64_t* d_ckeys = nullptr;
     uint32_t coarse_stride = 0;
-    int raw_heap_out = 0;
+    int raw_heap_out = 0;  // leave the heap un-reordered (no search sets it: run_rounds_device keeps the sorted selection off it)
     int fused = 0;
-    // scanner API over a part of a list (amd_ivf_scan_codes_at / _range; exec_round only, one query, one probe, key 0): the round sees
-    // an index of ONE list whose vectors are [sub_base, sub_base + sub_n) of the packed matrix -- positions count from sub_base, as
-    // the reference's scanner counts from the pointer it is handed (IndexIVFFlat.cpp:117-137)
-    uint64_t sub_base = 0;
-    size_t sub_n = (size_t)-1;
-    long long pair_list = -1;  // store_pairs labels of a list part carry this list number
-    // ... and, instead of the heap replay, the row's entries inside `collect_radius` in position order (scan_codes_range)
-    bool collect = false;
-    float collect_radius = 0.f;
     // time-bounded search: budgets in ms (device, by absolute id) and the host clock (us) the budgets count from
     const float* d_budget_ms = nullptr;
     double t_start_us = 0;
@@ -1327,214 +1312,67 @@ static void print_replay_dbg(amd_ivf* h, size_t mb, hipStream_t s) {
     }
 }
 
-void exec_round(amd_ivf* h, const RoundSpec& r) {
-    const size_t m = r.slot.size();
-    if (m == 0) return;
-    const uint32_t qblock = scan_qblock(r.bytes);
-    const double t_enter = now_us();
-    const bool sub = r.sub_n != (size_t)-1;
-    const std::vector<uint64_t> sub_off{r.sub_base, r.sub_base + (sub ? r.sub_n : 0)};
-    const size_t nlist = sub ? 1 : h->nlist;
-    const std::vector<uint64_t>& off = sub ? sub_off : ix(h)->h_list_off;
-    if (sub) {
-        if (m != 1 || r.cnt[0] != 1 || r.bytes) throw EngineError("a list part is scanned for one query, in fp32");
+// ------------------------------------------------------------------------------------ one-list scan (the scanner API)
+// One query (row 0 of w_x) against a whole list, or against a part of one (amd_ivf_scan_codes / _at / _range).
+struct ListScan {
+    size_t list_no = 0;
+    // a part of the list: the selection sees an index of ONE list whose vectors are [base, base + n) of the packed matrix --
+    // positions count from base, as the reference's scanner counts from the pointer it is handed (IndexIVFFlat.cpp:117-137) --
+    // and store_pairs labels carry list_no
+    bool part = false;
+    uint64_t base = 0;  // first vector in the packed matrix, and how many
+    size_t n = 0;
+    int k = 1;
+    int store_pairs = 0;
+    int fused = 0;
+    // instead of the heap replay, the row's entries inside `radius` in position order (scan_codes_range)
+    bool collect = false;
+    float radius = 0.f;
+};
+
+// The distances of the run into w_dist (one tile of the narrowest workgroup shape per 128 vectors), then either the reference's
+// heap over them, starting from the heap that w_heap_val / w_heap_ref hold (-> w_D / w_I, unsorted; statistics in w_stats), or
+// the entries inside the radius (-> count in word 4 of w_sub_off, positions in w_I, distances in w_D).  Synchronises the stream.
+void scan_list_run(amd_ivf* h, const ListScan& r) {
+    hipStream_t s = h->stream;
+    const float* d_x = h->w_x.as<float>();
+    auto put = [&](DevBuf& b, const void* src, size_t bytes) {  // (the sources live until the synchronisation below)
+        b.ensure(bytes);
+        HIP_CHECK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
+    };
+    const uint64_t sub_off[2] = {r.base, r.base + r.n};
+    if (r.part) {
         h->w_sub_off.ensure(32);  // (two offsets; the third word: scan_codes_range's count)
-        HIP_CHECK(hipMemcpyAsync(h->w_sub_off.p, sub_off.data(), 16, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->w_sub_off.p, sub_off, 16, hipMemcpyHostToDevice, s));
     }
-    size_t q0 = 0;
-    std::vector<uint32_t> lcount(nlist + 1);
-    while (q0 < m) {
-        // ---- sub-batch [q0, q1) bounded by the distance-buffer budget
-        size_t q1 = q0, total = 0;
-        uint32_t rp = 0;
-        while (q1 < m) {
-            size_t need = 0;
-            for (uint32_t p = 0; p < r.cnt[q1]; p++) {
-                int64_t key = r.keys[(size_t)r.slot[q1] * r.key_stride + r.p0[q1] + p];
-                if (key < 0) continue;
-                if ((size_t)key >= nlist) throw EngineError("Invalid key=" + std::to_string(key) + " nlist=" + std::to_string(nlist));
-                need += off[key + 1] - off[key];
-            }
-            if (q1 > q0 && total + need > h->dist_budget_floats) break;
-            total += need;
-            rp = std::max(rp, r.cnt[q1]);
-            q1++;
-        }
-        const size_t mb = q1 - q0;
-        (void)rp;
-        // ---- segments (query-major distance rows, CSR over the queries) and pairs grouped by list
-        size_t nseg = 0;
-        for (size_t i = 0; i < mb; i++) nseg += r.cnt[q0 + i];
-        h->p_seg_off.ensure(std::max<size_t>(nseg, 1) * 8);
-        h->p_seg_list.ensure(std::max<size_t>(nseg, 1) * 4);
-        h->p_seg_count.ensure(mb * 4);
-        h->p_seg_begin.ensure(mb * 4);
-        h->p_qsel.ensure(mb * 4);
-        uint64_t* seg_off = h->p_seg_off.as<uint64_t>();
-        int32_t* seg_list = h->p_seg_list.as<int32_t>();
-        uint32_t* seg_count = h->p_seg_count.as<uint32_t>();
-        uint32_t* seg_begin = h->p_seg_begin.as<uint32_t>();
-        uint32_t* qsel = h->p_qsel.as<uint32_t>();
-        std::fill(lcount.begin(), lcount.end(), 0u);
-        size_t npairs = 0;
-        uint64_t cursor = 0;
-        double bytes = 0;
-        {
-            uint32_t sp = 0;
-            for (size_t i = 0; i < mb; i++) {
-                const size_t qi = q0 + i;
-                seg_count[i] = r.cnt[qi];
-                seg_begin[i] = sp;
-                qsel[i] = r.slot[qi];
-                const int64_t* kq = r.keys + (size_t)r.slot[qi] * r.key_stride + r.p0[qi];
-                for (uint32_t p = 0; p < r.cnt[qi]; p++, sp++) {
-                    const int64_t key = kq[p];
-                    seg_list[sp] = (int32_t)key;
-                    seg_off[sp] = cursor;
-                    if (key >= 0) {
-                        const size_t sz = off[key + 1] - off[key];
-                        if (sz) {
-                            lcount[key + 1]++;
-                            npairs++;
-                            cursor += sz;
-                            bytes += (double)sz * h->d * 4.0;
-                        }
-                    }
-                }
-            }
-        }
-        h->scan_bytes += bytes;
-        for (size_t l = 0; l < nlist; l++) lcount[l + 1] += lcount[l];
-        h->p_pair_query.ensure(std::max<size_t>(npairs, 1) * 4);
-        h->p_pair_out.ensure(std::max<size_t>(npairs, 1) * 8);
-        uint32_t* pair_query = h->p_pair_query.as<uint32_t>();
-        uint64_t* pair_out = h->p_pair_out.as<uint64_t>();
-        {
-            std::vector<uint32_t> fill(lcount.begin(), lcount.end() - 1);
-            for (size_t i = 0; i < mb; i++) {
-                const size_t qi = q0 + i;
-                const uint32_t sb = seg_begin[i];
-                for (uint32_t p = 0; p < r.cnt[qi]; p++) {
-                    int32_t key = seg_list[sb + p];
-                    if (key < 0 || off[key + 1] == off[key]) continue;
-                    uint32_t pos = fill[key]++;
-                    pair_query[pos] = r.slot[qi];
-                    pair_out[pos] = seg_off[sb + p];
-                }
-            }
-        }
-        // ---- tiles, grouped by workgroup shape (qg 1 | 2 | 4 | 8) so that each shape gets its own launch.  The c queries
-        // of a list go into blocks of 64 (qg 8: 8 waves x 8 queries over one 128-vector tile); the remainder block takes
-        // the narrowest shape that holds it, so that no wave runs without queries.
-        size_t n_qg[4] = {0, 0, 0, 0};
-        std::vector<uint32_t> gbase(nlist, 0);
-        std::vector<std::pair<uint32_t, uint32_t>> qranges;
-        {
-            uint32_t g = 0;
-            for (size_t l = 0; l < nlist; l++) {
-                uint32_t c = lcount[l + 1] - lcount[l];
-                if (!c) continue;
-                gbase[l] = g;
-                g += (c + SCAN_RQ - 1) / SCAN_RQ;
-                qranges.emplace_back(lcount[l], c);
-            }
-        }
-        for (size_t l = 0; l < nlist; l++) {
-            uint32_t c = lcount[l + 1] - lcount[l];
-            if (!c) continue;
-            const size_t sz = off[l + 1] - off[l];
-            if (r.bytes) {  // scan_mfma_kernel items: (chunk of the list) x (block of 32 queries)
-                n_qg[3] += (size_t)((c + MFMA_QBLOCK - 1) / MFMA_QBLOCK) * ((sz + mfma_chunk() - 1) / mfma_chunk());
-                continue;
-            }
-            const uint32_t full = c / qblock, rem = c % qblock;
-            if (full) {
-                const uint32_t qg = scan_shape_of(qblock);
-                const size_t tv = scan_tile_vecs(qg);
-                n_qg[scan_qg_class(qg)] += (size_t)full * ((sz + tv - 1) / tv);
-            }
-            if (rem) {
-                uint32_t qg = scan_shape_of(rem);
-                size_t tv = scan_tile_vecs(qg);
-                n_qg[scan_qg_class(qg)] += (sz + tv - 1) / tv;
-            }
-        }
-        const size_t nitems = n_qg[0] + n_qg[1] + n_qg[2] + n_qg[3];
-        h->p_items.ensure(std::max<size_t>(nitems, 1) * sizeof(ScanItem));
+    // ---- the one segment of the one query, and (unless the run is empty) its one pair
+    const uint32_t zero = 0, one = 1;
+    const uint64_t zero64 = 0;
+    const int32_t key = r.part ? 0 : (int32_t)r.list_no;
+    put(h->w_seg_off, &zero64, 8);
+    put(h->w_seg_list, &key, 4);
+    put(h->w_seg_count, &one, 4);
+    put(h->w_seg_begin, &zero, 4);
+    put(h->w_qsel, &zero, 4);
+    h->w_dist.ensure(std::max<size_t>(r.n, 1) * sizeof(float));
+    if (r.n) {
+        const uint32_t n = (uint32_t)r.n, tv = scan_tile_vecs(1);
+        const size_t n_qg[4] = {(r.n + tv - 1) / tv, 0, 0, 0};
+        h->p_items.ensure(n_qg[0] * sizeof(ScanItem));
         ScanItem* items = h->p_items.as<ScanItem>();
-        size_t cur[4] = {0, n_qg[0], n_qg[0] + n_qg[1], n_qg[0] + n_qg[1] + n_qg[2]};
-        for (size_t l = 0; l < nlist; l++) {
-            uint32_t c = lcount[l + 1] - lcount[l];
-            if (!c) continue;
-            const uint32_t sz = (uint32_t)(off[l + 1] - off[l]);
-            if (r.bytes) {
-                size_t& ni = cur[3];
-                for (uint32_t vb = 0; vb < sz; vb += mfma_chunk())
-                    for (uint32_t qb = 0; qb < c; qb += MFMA_QBLOCK) {
-                        ScanItem& it = items[ni++];
-                        it.vec_base = ix(h)->h_block_off[l] + vb / MFMA_BLOCK;
-                        it.nvec = std::min<uint32_t>(mfma_chunk(), sz - vb);
-                        it.vec_off = vb;
-                        it.pair_begin = lcount[l] + qb;
-                        it.npair = std::min<uint32_t>(MFMA_QBLOCK, c - qb);
-                        it.qg = 0;
-                        it.qgroup = 0;
-                        h->scan_slots += (double)MFMA_QBLOCK * (((it.nvec + 63) / 64) * 64);
-                        h->scan_useful += (double)it.npair * it.nvec;
-                    }
-                continue;
-            }
-            for (uint32_t qb = 0; qb < c; qb += qblock) {
-                const uint32_t nq_blk = std::min<uint32_t>(qblock, c - qb);
-                const uint32_t qg = scan_shape_of(nq_blk);
-                const uint32_t tv = scan_tile_vecs(qg);
-                size_t& ni = cur[scan_qg_class(qg)];
-                for (uint32_t vb = 0; vb < sz; vb += tv) {
-                    ScanItem& it = items[ni++];
-                    // (a list part starts anywhere: no block of the lane-ordered copy belongs to it, the tiles read the rows)
-                    it.vec_base = sub ? off[l] + vb : scan_vec_base(off[l] + vb, ix(h)->h_block_off.empty() ? 0ull : ix(h)->h_block_off[l], vb);
-                    it.nvec = std::min(tv, sz - vb);
-                    it.vec_off = vb;
-                    it.pair_begin = lcount[l] + qb;
-                    it.npair = nq_blk;
-                    it.qg = qg;
-                    it.qgroup = gbase[l] + qb / SCAN_RQ;
-                    // bookkeeping: (query, vector) slots the waves that run will compute vs pairs wanted
-                    h->scan_slots += (double)((nq_blk + SCAN_RQ - 1) / SCAN_RQ) * SCAN_RQ * tv;
-                    h->scan_useful += (double)nq_blk * it.nvec;
-                }
-            }
-        }
-        // ---- upload + launch
-        h->w_dist.ensure(std::max<uint64_t>(cursor, 1) * sizeof(float));
-        h->w_seg_off.ensure(std::max<size_t>(nseg, 1) * 8);
-        h->w_seg_list.ensure(std::max<size_t>(nseg, 1) * 4);
-        h->w_seg_count.ensure(mb * 4);
-        h->w_seg_begin.ensure(mb * 4);
-        h->w_qsel.ensure(mb * 4);
-        h->w_pair_query.ensure(std::max<size_t>(npairs, 1) * 4);
-        h->w_pair_out.ensure(std::max<size_t>(npairs, 1) * 8);
-        h->w_items.ensure(std::max<size_t>(nitems, 1) * sizeof(ScanItem));
-        hipStream_t s = h->stream;
-        if (nseg) {
-            HIP_CHECK(hipMemcpyAsync(h->w_seg_off.p, seg_off, nseg * 8, hipMemcpyHostToDevice, s));
-            HIP_CHECK(hipMemcpyAsync(h->w_seg_list.p, seg_list, nseg * 4, hipMemcpyHostToDevice, s));
-        }
-        HIP_CHECK(hipMemcpyAsync(h->w_seg_count.p, seg_count, mb * 4, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(h->w_seg_begin.p, seg_begin, mb * 4, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(h->w_qsel.p, qsel, mb * 4, hipMemcpyHostToDevice, s));
-        if (npairs) {
-            HIP_CHECK(hipMemcpyAsync(h->w_pair_query.p, pair_query, npairs * 4, hipMemcpyHostToDevice, s));
-            HIP_CHECK(hipMemcpyAsync(h->w_pair_out.p, pair_out, npairs * 8, hipMemcpyHostToDevice, s));
-            HIP_CHECK(hipMemcpyAsync(h->w_items.p, items, nitems * sizeof(ScanItem), hipMemcpyHostToDevice, s));
-        }
-        const double t_prep = now_us();
-        if (npairs && !r.bytes) pack_query_tiles(h, r.d_x, qranges);
+        const uint64_t block0 = ix(h)->h_block_off.empty() ? 0ull : ix(h)->h_block_off[r.list_no];
+        for (uint32_t vb = 0; vb < n; vb += tv)
+            // (a list part starts anywhere: no block of the lane-ordered copy belongs to it, the tiles read the rows)
+            *items++ = ScanItem{r.part ? r.base + vb : scan_vec_base(r.base + vb, block0, vb), std::min(tv, n - vb), vb, 0, 1, 1, 0};
+        put(h->w_pair_query, &zero, 4);
+        put(h->w_pair_out, &zero64, 8);
+        put(h->w_items, h->p_items.p, n_qg[0] * sizeof(ScanItem));
+        pack_query_tiles(h, d_x, {{0u, 1u}});
         ScanArgs sa{};
         sa.qtile = h->w_qtile.as<float>();
         sa.codes = ix(h)->d_codes.as<float>();
-        sa.lanes = r.bytes || sub ? nullptr : ensure_lanes(ix(h));
-        sa.queries = r.d_x;
+        sa.lanes = r.part ? nullptr : ensure_lanes(ix(h));
+        sa.queries = d_x;
         sa.items = h->w_items.as<ScanItem>();
         sa.pair_query = h->w_pair_query.as<uint32_t>();
         sa.pair_out = h->w_pair_out.as<uint64_t>();
@@ -1542,108 +1380,59 @@ void exec_round(amd_ivf* h, const RoundSpec& r) {
         sa.d = h->dpad;
         sa.metric = h->metric;
         sa.fused = r.fused;
-        MfmaScanArgs ma{};
-        ma.codes_frag = ix(h)->d_frag.as<uint8_t>();
-        ma.code_cy = ix(h)->d_cy.as<int32_t>();
-        ma.queries8 = h->w_x8.as<int8_t>();
-        ma.query_cx = h->w_xnorm8.as<int32_t>();
-        ma.items = h->w_items.as<ScanItem>();
-        ma.pair_query = h->w_pair_query.as<uint32_t>();
-        ma.pair_out = h->w_pair_out.as<uint64_t>();
-        ma.dist = h->w_dist.as<float>();
-        ma.d = h->d;
-        ma.metric = h->metric;
-        ma.nitems = (uint32_t)nitems;
-        if (nitems && r.bytes) {
-            size_t t = h->timer.begin(CAT_SCAN, s);
-            launch_scan_mfma(ma, s);
-            h->timer.end(t, s);
-        } else if (nitems) {
-            ensure_aux(h, 3, 3);
-            size_t t = h->timer.begin(CAT_SCAN, s);
-            const bool fork = true;  // the shapes on the side stream (see make_main_stream; one stream: run_rounds_device's note)
-            if (fork) {
-                HIP_CHECK(hipEventRecord(h->ev_fork, s));
-                HIP_CHECK(hipStreamWaitEvent(h->aux[3], h->ev_fork, 0));
-                launch_scan(sa, n_qg, h->aux[3], h->aux[3], h->aux[3], h->aux[3]);
-                HIP_CHECK(hipEventRecord(h->ev_join[3], h->aux[3]));
-                HIP_CHECK(hipStreamWaitEvent(s, h->ev_join[3], 0));
-            } else {
-                launch_scan(sa, n_qg, s);
-            }
-            h->timer.end(t, s);
-        }
-        if (r.collect) {
-            // scan_codes_range: the row's entries inside the radius, in position order (count, positions, distances: w_D / w_I hold them)
-            h->w_D.ensure(std::max<uint64_t>(cursor, 1) * sizeof(float));
-            h->w_I.ensure(std::max<uint64_t>(cursor, 1) * sizeof(uint32_t));
-            if (!sub) throw EngineError("collect is the scanner API's (a list part)");
-            launch_range_collect(h->w_dist.as<float>(), (uint32_t)cursor, r.collect_radius, h->metric, h->w_sub_off.as<uint32_t>() + 4,
-                                 h->w_I.as<uint32_t>(), h->w_D.as<float>(), s);
-            HIP_CHECK(stream_sync(s));
-            q0 = q1;
-            continue;
-        }
-        ReplayArgs ra{};
-        ra.metric = h->metric;
-        ra.k = r.k;
-        ra.nlist = (uint32_t)nlist;
-        ra.nq = (uint32_t)mb;
-        ra.qsel = h->w_qsel.as<uint32_t>();
-        ra.total_nprobe = r.total_nprobe;
-        ra.round_probes = 0;
-        ra.seg_begin = h->w_seg_begin.as<uint32_t>();
-        ra.id_offset = r.id_offset;
-        ra.dist = h->w_dist.as<float>();
-        ra.seg_off = h->w_seg_off.as<uint64_t>();
-        ra.seg_list = h->w_seg_list.as<int32_t>();
-        ra.seg_count = h->w_seg_count.as<uint32_t>();
-        ra.list_off = sub ? h->w_sub_off.as<uint64_t>() : ix(h)->d_list_off.as<uint64_t>();
-        ra.ids = ix(h)->d_ids.as<int64_t>();
-        ra.store_pairs = r.store_pairs;
-        ra.identity_ids = 0;
-        ra.max_codes = r.max_codes;
-        ra.finalize_all = r.finalize_all;
-        ra.heap_val = h->w_heap_val.as<float>();
-        ra.heap_ref = h->w_heap_ref.as<int64_t>();
-        ra.stage = h->w_stage.as<uint32_t>();
-        ra.nscan = h->w_nscan.as<unsigned long long>();
-        ra.done = h->w_done.as<uint32_t>();
-        ra.pre_val = h->w_pre_val.as<float>();
-        ra.stoped = h->w_stoped.as<uint32_t>();
-        ra.dtb = h->w_dtb.as<float>();
-        ra.coarse_dis = r.d_cdis;
-        ra.coarse_keys = r.d_ckeys;
-        ra.coarse_stride = r.coarse_stride;
-        ra.trace_cap = (uint32_t)ix(h)->tuner_trace_cap;
-        ra.D = h->w_D.as<float>();
-        ra.I = h->w_I.as<int64_t>();
-        ra.stats = h->w_stats.as<unsigned long long>();
-        ra.error = h->w_error.as<uint32_t>();
-        ra.raw_heap_out = r.raw_heap_out;
-        ra.pair_list = r.pair_list;
-        ra.tuner = r.tuner;
-        ra.train = r.train;
-        static const bool dbg_replay = getenv("AUNCEL_AMD_DEBUG_REPLAY") != nullptr;
-        if (dbg_replay) {
-            h->w_misc.ensure(mb * 64);
-            HIP_CHECK(hipMemsetAsync(h->w_misc.p, 0, mb * 64, s));
-            ra.dbg = h->w_misc.as<unsigned long long>();
-        }
-        {
-            size_t t = h->timer.begin(CAT_SELECT, s);
-            launch_replay(ra, s);
-            h->timer.end(t, s);
-        }
-        if (dbg_replay) print_replay_dbg(h, mb, s);
-        // the pinned staging buffers are reused by the next sub-batch
-        const double t_launched = now_us();
-        HIP_CHECK(stream_sync(s));
-        if (dbg_timing())
-            fprintf(stderr, "[round] queries %zu pairs %zu items %zu: host prep %.0f us, launch %.0f us, gpu wait %.0f us\n", mb, npairs, nitems,
-                    t_prep - t_enter, t_launched - t_prep, now_us() - t_launched);
-        q0 = q1;
+        ensure_aux(h, 3, 3);
+        size_t t = h->timer.begin(CAT_SCAN, s);
+        // on the side stream (see make_main_stream; one stream: run_rounds_device's note)
+        HIP_CHECK(hipEventRecord(h->ev_fork, s));
+        HIP_CHECK(hipStreamWaitEvent(h->aux[3], h->ev_fork, 0));
+        launch_scan(sa, n_qg, h->aux[3], h->aux[3], h->aux[3], h->aux[3]);
+        HIP_CHECK(hipEventRecord(h->ev_join[3], h->aux[3]));
+        HIP_CHECK(hipStreamWaitEvent(s, h->ev_join[3], 0));
+        h->timer.end(t, s);
     }
+    if (r.collect) {
+        if (!r.part) throw EngineError("collect is the scanner API's (a list part)");
+        h->w_D.ensure(std::max<size_t>(r.n, 1) * sizeof(float));
+        h->w_I.ensure(std::max<size_t>(r.n, 1) * sizeof(uint32_t));
+        launch_range_collect(h->w_dist.as<float>(), (uint32_t)r.n, r.radius, h->metric, h->w_sub_off.as<uint32_t>() + 4,
+                             h->w_I.as<uint32_t>(), h->w_D.as<float>(), s);
+        HIP_CHECK(stream_sync(s));
+        return;
+    }
+    ReplayArgs ra{};
+    ra.metric = h->metric;
+    ra.k = r.k;
+    ra.nlist = r.part ? 1u : (uint32_t)h->nlist;
+    ra.nq = 1;
+    ra.qsel = h->w_qsel.as<uint32_t>();
+    ra.seg_begin = h->w_seg_begin.as<uint32_t>();
+    ra.dist = h->w_dist.as<float>();
+    ra.seg_off = h->w_seg_off.as<uint64_t>();
+    ra.seg_list = h->w_seg_list.as<int32_t>();
+    ra.seg_count = h->w_seg_count.as<uint32_t>();
+    ra.list_off = r.part ? h->w_sub_off.as<uint64_t>() : ix(h)->d_list_off.as<uint64_t>();
+    ra.ids = ix(h)->d_ids.as<int64_t>();
+    ra.store_pairs = r.store_pairs;
+    ra.finalize_all = 1;
+    ra.heap_val = h->w_heap_val.as<float>();
+    ra.heap_ref = h->w_heap_ref.as<int64_t>();
+    ra.stage = h->w_stage.as<uint32_t>();
+    ra.nscan = h->w_nscan.as<unsigned long long>();
+    ra.done = h->w_done.as<uint32_t>();
+    ra.pre_val = h->w_pre_val.as<float>();
+    ra.stoped = h->w_stoped.as<uint32_t>();
+    ra.dtb = h->w_dtb.as<float>();
+    ra.trace_cap = (uint32_t)ix(h)->tuner_trace_cap;
+    ra.D = h->w_D.as<float>();
+    ra.I = h->w_I.as<int64_t>();
+    ra.stats = h->w_stats.as<unsigned long long>();
+    ra.error = h->w_error.as<uint32_t>();
+    ra.raw_heap_out = 1;
+    ra.pair_list = r.part ? (long long)r.list_no : -1;
+    size_t t = h->timer.begin(CAT_SELECT, s);
+    launch_replay(ra, s);
+    h->timer.end(t, s);
+    HIP_CHECK(stream_sync(s));
 }
 
 static bool pinned_io(const amd_ivf* h) { return opt(h, OPT_PINNED_IO, 1) != 0; }
@@ -1923,6 +1712,11 @@ void finish_timing(amd_ivf* h, double wall_ms) {
     h->timing[5] = h->scan_bytes;
     h->last_min_bytes = h->scan_min_bytes;
     h->timing[6] = h->scan_slots > 0 ? h->scan_useful / h->scan_slots : 0;
+}
+// ... and what every call that ends in finish_timing starts with
+static inline void reset_scan_counters(amd_ivf* h) {
+    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
+    h->scan_slots = h->scan_useful = 0;
 }
 
 struct WallClock {
@@ -2232,103 +2026,6 @@ void coarse_dev(amd_ivf* h, const float* d_x, size_t n, size_t nprobe, int mode,
 }
 
 // ------------------------------------------------------------------------------------ searches
-void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first_round, size_t total_nprobe,
-                       const unsigned long long* d_np_abs);
-
-// Fixed nprobe, planned on the device from keys that are already there (n x nprobe).  From 16 probes on they are split
-// in two rounds: the first nprobe / 8 fill the heap, the rest run in threshold mode (the scan stores and the selection
-// reads only what can still enter it; a dense round is bound by those 8 bytes per distance).  Below that one dense
-// round is cheaper than a second pass over the lists (5000 queries, 10M x 128, nprobe 8: 2.7 vs 2.1 M queries/s;
-// nprobe 32: 1.1 vs 1.3).
-void search_fixed_device(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, const int64_t* d_keys, float* D,
-                         int64_t* I, int store_pairs, size_t max_codes, const IntRange& qr) {
-    CallScope call_scope(h);
-    upload_lists(h);
-    init_state(h, n, k, false);
-    RoundSpec base;
-    base.k = (int)k;
-    base.store_pairs = store_pairs;
-    base.max_codes = max_codes;
-    base.d_x = d_x;
-    base.d_ckeys = d_keys;
-    base.coarse_stride = (uint32_t)nprobe;
-    base.fused = h->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
-    base.bytes = byte_queries(h, ix(h), d_x, n, qr);
-    ix(h)->last_arith = base.bytes ? 2 : base.fused ? 1 : 0;
-    const int two_env = (int)opt(h, OPT_FIXED_ROUNDS, 0);
-    // a handful of queries: the second round's planning + synchronisation costs more than threshold mode saves
-    // (fp32 lists with the matrix-core filter: a threshold round costs its list bytes, not its distances -- one dense probe gives
-    // the thresholds, everything else goes through the filter)
-    const bool filt = filter_available(h, ix(h), base.bytes);
-    const bool two = two_env ? two_env == 2 : filt ? (nprobe >= 4 && n * nprobe >= 1024) : (nprobe >= 16 && n * nprobe >= 4096);
-    base.fixed_two = two;
-    const size_t first = two ? (filt ? filter_first_probes(ix(h), k, nprobe) : std::max<size_t>(1, nprobe / 8)) : nprobe;
-    base.caller_checks_error = true;
-    with_select_fallback(h, [&] {
-        if (h->force_heap_select) init_state(h, n, k, false);
-        DirectOut direct(h, D, I);
-        run_rounds_device(h, base, n, first, nprobe, nullptr);
-        finish_results(h, n, k, D, I);
-    });
-}
-
-void search_fixed_core(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, const int64_t* keys, float* D,
-                       int64_t* I, int store_pairs, size_t max_codes, const IntRange& qr) {
-    upload_lists(h);
-    init_state(h, n, k, false);
-    RoundSpec r;
-    r.slot.resize(n);
-    r.p0.assign(n, 0);
-    r.cnt.assign(n, (uint32_t)nprobe);
-    for (size_t i = 0; i < n; i++) r.slot[i] = (uint32_t)i;
-    if (max_codes) {
-        // the probe loop stops after the list that brings the visited codes to max_codes (IndexIVF.cpp:541)
-        for (size_t i = 0; i < n; i++) {
-            size_t nscan = 0;
-            for (size_t p = 0; p < nprobe; p++) {
-                int64_t key = keys[i * nprobe + p];
-                if (key >= 0 && (size_t)key < h->nlist) nscan += ix(h)->h_list_off[key + 1] - ix(h)->h_list_off[key];
-                if (nscan >= max_codes) {
-                    r.cnt[i] = (uint32_t)(p + 1);
-                    break;
-                }
-            }
-        }
-    }
-    r.keys = keys;
-    r.key_stride = nprobe;
-    r.k = (int)k;
-    r.store_pairs = store_pairs;
-    r.max_codes = max_codes;
-    r.finalize_all = 1;
-    r.d_x = d_x;
-    r.fused = h->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
-    r.bytes = byte_queries(h, ix(h), d_x, n, qr);
-    ix(h)->last_arith = r.bytes ? 2 : r.fused ? 1 : 0;
-    exec_round(h, r);
-    check_device_error(h);
-    HIP_CHECK(hipMemcpyAsync(D, h->w_D.p, n * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipMemcpyAsync(I, h->w_I.p, n * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(stream_sync(h->stream));
-    fold_stats(h, n);
-}
-
-void search_full(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I, const IntRange& qr) {
-    h->w_cdis.ensure(n * nprobe * 4);
-    h->w_ckeys.ensure(n * nprobe * 8);
-    coarse_dev(h, d_x, n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
-               h->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric));
-    static const bool host_plan = getenv("AUNCEL_AMD_HOST_PLAN") != nullptr;
-    if (!host_plan) {
-        search_fixed_device(h, d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, qr);
-        return;
-    }
-    std::vector<int64_t> keys(n * nprobe);
-    HIP_CHECK(hipMemcpyAsync(keys.data(), h->w_ckeys.p, n * nprobe * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(stream_sync(h->stream));
-    search_fixed_core(h, d_x, n, k, nprobe, keys.data(), D, I, 0, 0, qr);
-}
-
 TunerDev make_tuner(amd_ivf* h, size_t query_topk, float multipler, float std_m, const float* d_req, const float* d_gt,
                     unsigned long long* d_np, float* d_tr, int profile) {
     TunerDev t{};
@@ -3218,71 +2915,50 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
     }
 }
 
-// multi-round driver shared by the adaptive search and the trace training (host-side planning: kept for reference /
-// AUNCEL_AMD_HOST_PLAN=1)
-void run_rounds(amd_ivf* h, RoundSpec& base, size_t n, size_t first_round, size_t total_nprobe,
-                const unsigned long long* d_np_abs /* may be null */, size_t start) {
-    // keys for probes [0, have) of every slot are kept on the host and extended on demand
-    size_t have = 0;
-    std::vector<int64_t> hkeys;
-    size_t stride = 0;
-    std::vector<uint32_t> stage(n, 0), done(n, 0);
-    std::vector<unsigned long long> np(n, 0);
-    size_t round_len = first_round;
-    for (;;) {
-        const double t_plan0 = now_us();
-        // plan: every unfinished query runs either up to its known my_nprobe or one more block of round_len
-        std::vector<uint32_t> slot, p0, cnt;
-        size_t need_cols = 0;
-        for (size_t i = 0; i < n; i++) {
-            if (done[i]) continue;
-            size_t target = stage[i] + round_len;
-            if (base.tuner.enabled) {
-                // an unfired query at stage s cannot stop before floor((s+1) * multipler): that many probes
-                // are waste-free; beyond it allow growth-1 of over-scan to keep the number of rounds small
-                static const double grow_env = getenv("AUNCEL_AMD_ROUND_GROW") ? atof(getenv("AUNCEL_AMD_ROUND_GROW")) : 3.5;
-                const double grow = std::max<double>(base.tuner.multipler, grow_env);
-                const size_t safe = (size_t)((float)(stage[i] + 1) * base.tuner.multipler);
-                target = std::max<size_t>({safe, (size_t)(stage[i] * grow), stage[i] + first_round});
-            }
-            if (np[i] != 0) target = std::max<size_t>(np[i], stage[i] + 1);
-            target = std::min(target, total_nprobe);
-            if (target <= stage[i]) target = std::min<size_t>(stage[i] + 1, total_nprobe);
-            slot.push_back((uint32_t)i);
-            p0.push_back(stage[i]);
-            cnt.push_back((uint32_t)(target - stage[i]));
-            need_cols = std::max(need_cols, target);
-        }
-        if (slot.empty()) break;
-        if (need_cols > have) {
-            size_t new_have = std::min(total_nprobe, std::max(need_cols, have * 2));
-            std::vector<int64_t> nk(n * new_have);
-            HIP_CHECK(hipMemcpy2DAsync(nk.data(), new_have * 8, base.d_ckeys, (size_t)base.coarse_stride * 8, new_have * 8, n,
-                                       hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(stream_sync(h->stream));
-            hkeys.swap(nk);
-            have = new_have;
-            stride = new_have;
-        }
-        const double t_plan1 = now_us();
-        RoundSpec r = base;
-        r.slot = slot;
-        r.p0 = p0;
-        r.cnt = cnt;
-        r.keys = hkeys.data();
-        r.key_stride = stride;
-        r.total_nprobe = (uint32_t)total_nprobe;
-        exec_round(h, r);
-        const double t_rb0 = now_us();
-        check_device_error(h);
-        HIP_CHECK(hipMemcpyAsync(stage.data(), h->w_stage.p, n * 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipMemcpyAsync(done.data(), h->w_done.p, n * 4, hipMemcpyDeviceToHost, h->stream));
-        if (d_np_abs)
-            HIP_CHECK(hipMemcpyAsync(np.data(), d_np_abs + start, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(stream_sync(h->stream));
-        if (dbg_timing()) fprintf(stderr, "[rounds] plan+keys %.0f us, readback %.0f us\n", t_plan1 - t_plan0, now_us() - t_rb0);
-        round_len = std::min<size_t>(round_len * 2, 64);
-    }
+// ------------------------------------------------------------------------------------ fixed nprobe
+// Fixed nprobe, planned on the device from keys that are already there (n x nprobe).  From 16 probes on they are split
+// in two rounds: the first nprobe / 8 fill the heap, the rest run in threshold mode (the scan stores and the selection
+// reads only what can still enter it; a dense round is bound by those 8 bytes per distance).  Below that one dense
+// round is cheaper than a second pass over the lists (5000 queries, 10M x 128, nprobe 8: 2.7 vs 2.1 M queries/s;
+// nprobe 32: 1.1 vs 1.3).
+void search_fixed_device(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, const int64_t* d_keys, float* D,
+                         int64_t* I, int store_pairs, size_t max_codes, const IntRange& qr) {
+    CallScope call_scope(h);
+    upload_lists(h);
+    init_state(h, n, k, false);
+    RoundSpec base;
+    base.k = (int)k;
+    base.store_pairs = store_pairs;
+    base.max_codes = max_codes;
+    base.d_x = d_x;
+    base.d_ckeys = d_keys;
+    base.coarse_stride = (uint32_t)nprobe;
+    base.fused = h->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
+    base.bytes = byte_queries(h, ix(h), d_x, n, qr);
+    ix(h)->last_arith = base.bytes ? 2 : base.fused ? 1 : 0;
+    const int two_env = (int)opt(h, OPT_FIXED_ROUNDS, 0);
+    // a handful of queries: the second round's planning + synchronisation costs more than threshold mode saves
+    // (fp32 lists with the matrix-core filter: a threshold round costs its list bytes, not its distances -- one dense probe gives
+    // the thresholds, everything else goes through the filter)
+    const bool filt = filter_available(h, ix(h), base.bytes);
+    const bool two = two_env ? two_env == 2 : filt ? (nprobe >= 4 && n * nprobe >= 1024) : (nprobe >= 16 && n * nprobe >= 4096);
+    base.fixed_two = two;
+    const size_t first = two ? (filt ? filter_first_probes(ix(h), k, nprobe) : std::max<size_t>(1, nprobe / 8)) : nprobe;
+    base.caller_checks_error = true;
+    with_select_fallback(h, [&] {
+        if (h->force_heap_select) init_state(h, n, k, false);
+        DirectOut direct(h, D, I);
+        run_rounds_device(h, base, n, first, nprobe, nullptr);
+        finish_results(h, n, k, D, I);
+    });
+}
+
+void search_full(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I, const IntRange& qr) {
+    h->w_cdis.ensure(n * nprobe * 4);
+    h->w_ckeys.ensure(n * nprobe * 8);
+    coarse_dev(h, d_x, n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
+               h->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric));
+    search_fixed_device(h, d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, qr);
 }
 
 }  // namespace
@@ -3586,8 +3262,7 @@ int amd_ivf_coarse(amd_ivf_t* h, size_t n, const float* x, size_t nprobe, float*
     use_device(h);
     if (n == 0) return 0;
     WallClock wc(h->stream);
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     h->w_x.ensure(n * h->dpad * sizeof(float));
     upload_rows(h, h->w_x.as<float>(), x, n);
     h->w_cdis.ensure(n * nprobe * 4);
@@ -3611,8 +3286,7 @@ int amd_ivf_coarse_resident(amd_ivf_t* h, size_t start, size_t n, size_t nprobe,
     if (start + n > src->n_resident) throw EngineError("resident query range out of bounds");
     if (n == 0) return 0;
     WallClock wc(h->stream);
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     h->w_cdis.ensure(n * nprobe * 4);
     h->w_ckeys.ensure(n * nprobe * 8);
     coarse_dev(h, src->d_resident.as<float>() + start * h->dpad, n, nprobe, mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
@@ -3631,20 +3305,14 @@ int amd_ivf_search_preassigned(amd_ivf_t* h, size_t n, const float* x, size_t k,
     use_device(h);
     if (n == 0 || k == 0) return 0;
     WallClock wc(h->stream);
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     h->w_x.ensure(n * h->dpad * sizeof(float));
     upload_rows(h, h->w_x.as<float>(), x, n);
     IntRange qr;
     qr.add(x, n * (size_t)h->d);
-    static const bool host_plan = getenv("AUNCEL_AMD_HOST_PLAN") != nullptr;
-    if (host_plan) {
-        search_fixed_core(h, h->w_x.as<float>(), n, k, nprobe, keys, D, I, store_pairs, max_codes, qr);
-    } else {
-        h->w_ckeys.ensure(n * nprobe * 8);
-        HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, keys, n * nprobe * 8, hipMemcpyHostToDevice, h->stream));
-        search_fixed_device(h, h->w_x.as<float>(), n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, store_pairs, max_codes, qr);
-    }
+    h->w_ckeys.ensure(n * nprobe * 8);
+    HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, keys, n * nprobe * 8, hipMemcpyHostToDevice, h->stream));
+    search_fixed_device(h, h->w_x.as<float>(), n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, store_pairs, max_codes, qr);
     finish_timing(h, wc.stop());
     API_END
 }
@@ -3654,8 +3322,7 @@ int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t npro
     use_device(h);
     if (n == 0 || k == 0) return 0;
     WallClock wc(h->stream);
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     h->w_x.ensure(n * h->dpad * sizeof(float));
     upload_rows(h, h->w_x.as<float>(), x, n);
     IntRange qr;
@@ -3721,8 +3388,7 @@ int amd_ivf_range_search_preassigned(amd_ivf_t* h, size_t n, const float* x, flo
         lims[0] = 0;
         return 0;
     }
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     range_core(h, h->w_x.as<float>(), n, radius, nprobe, h->w_ckeys.as<int64_t>(), qr, lims);
     finish_timing(h, wc.stop());
     API_END
@@ -3749,8 +3415,7 @@ int amd_ivf_range_search(amd_ivf_t* h, size_t n, const float* x, float radius, s
     h->w_ckeys.ensure(n * nprobe * 8);
     coarse_dev(h, h->w_x.as<float>(), n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
                h->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric));
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     range_core(h, h->w_x.as<float>(), n, radius, nprobe, h->w_ckeys.as<int64_t>(), qr, lims);
     finish_timing(h, wc.stop());
     API_END
@@ -3774,8 +3439,7 @@ int amd_ivf_search_resident_preassigned(amd_ivf_t* h, size_t start, size_t n, si
     if (n == 0 || k == 0) return 0;
     if (!keys) throw EngineError("keys are required");
     WallClock wc(h->stream);
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     h->w_ckeys.ensure(n * nprobe * 8);
     HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, keys, n * nprobe * 8, hipMemcpyHostToDevice, h->stream));
     search_fixed_device(h, src->d_resident.as<float>() + start * h->dpad, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, src->resident_range);
@@ -3791,8 +3455,7 @@ int amd_ivf_search_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, size
     if (start + n > src->n_resident) throw EngineError("resident query range out of bounds");
     if (n == 0 || k == 0) return 0;
     WallClock wc(h->stream);
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     search_full(h, src->d_resident.as<float>() + start * h->dpad, n, k, nprobe, coarse_mode, D, I, src->resident_range);
     finish_timing(h, wc.stop());
     API_END
@@ -3847,8 +3510,7 @@ int amd_ivf_search_timed(amd_ivf_t* h, size_t start, size_t n, size_t k, size_t 
     if (start + n > h->n_resident) throw EngineError("resident query range out of bounds");
     if (n == 0 || k == 0 || nprobe == 0) return 0;
     WallClock wc(h->stream);
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     timed_core(h, h->d_resident.as<float>() + start * h->dpad, start, n, k, nprobe, budget_ms, coarse_mode, nprobe_used, D, I,
                h->resident_range);
     finish_timing(h, wc.stop());
@@ -3861,8 +3523,7 @@ int amd_ivf_search_timed_x(amd_ivf_t* h, size_t n, const float* x, size_t id_off
     use_device(h);
     if (n == 0 || k == 0) return 0;
     WallClock wc(h->stream);
-    h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
-    h->scan_slots = h->scan_useful = 0;
+    reset_scan_counters(h);
     h->w_x.ensure(n * h->dpad * sizeof(float));
     upload_rows(h, h->w_x.as<float>(), x, n);
     IntRange qr;
@@ -3872,37 +3533,39 @@ int amd_ivf_search_timed_x(amd_ivf_t* h, size_t n, const float* x, size_t id_off
     API_END
 }
 
-int amd_ivf_scan_codes(amd_ivf_t* h, const float* query, size_t list_no, int store_pairs, size_t k, float* simi,
-                       int64_t* idxi, size_t* nup) {
-    API_BEGIN
-    OWNER_ONLY(h);
-    use_device(h);
+// one query against list `list_no`: checks, the lists and the query on the device (row 0 of w_x)
+static ListScan list_scan(amd_ivf* h, const float* query, size_t list_no) {
     if (list_no >= h->nlist) throw EngineError("Invalid key");
     upload_lists(h);
     h->w_x.ensure(h->dpad * sizeof(float));
     upload_rows(h, h->w_x.as<float>(), query, 1);
+    const std::vector<uint64_t>& off = ix(h)->h_list_off;
+    ListScan r;
+    r.list_no = list_no;
+    r.base = off[list_no];
+    r.n = off[list_no + 1] - off[list_no];
+    IntRange qr;
+    qr.add(query, (size_t)h->d);
+    r.fused = h->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
+    return r;
+}
+// ... against vectors [offset, offset + n) of it
+static ListScan list_part_scan(amd_ivf* h, const float* query, size_t list_no, size_t offset, size_t n) {
+    ListScan r = list_scan(h, query, list_no);
+    if (offset + n > r.n) throw EngineError("codes beyond the end of the list");
+    r.part = true;
+    r.base += offset;
+    r.n = n;
+    return r;
+}
+// the scan with the caller's heap (simi, idxi: k entries) as the starting state; nup: the heap updates
+static void scan_into_heap(amd_ivf* h, ListScan& r, int store_pairs, size_t k, float* simi, int64_t* idxi, size_t* nup) {
     init_state(h, 1, k, false);
-    // import the caller's heap as the starting state
     HIP_CHECK(hipMemcpyAsync(h->w_heap_val.p, simi, k * 4, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipMemcpyAsync(h->w_heap_ref.p, idxi, k * 8, hipMemcpyHostToDevice, h->stream));
-    int64_t key = (int64_t)list_no;
-    RoundSpec r;
-    r.slot = {0};
-    r.p0 = {0};
-    r.cnt = {1};
-    r.keys = &key;
-    r.key_stride = 1;
     r.k = (int)k;
     r.store_pairs = store_pairs;
-    r.finalize_all = 1;
-    r.raw_heap_out = 1;
-    r.d_x = h->w_x.as<float>();
-    {
-        IntRange qr;
-        qr.add(query, (size_t)h->d);
-        r.fused = h->allow_fused && h->db_range.fusable_with(qr, h->metric);
-    }
-    exec_round(h, r);
+    scan_list_run(h, r);
     check_device_error(h);
     HIP_CHECK(hipMemcpyAsync(simi, h->w_D.p, k * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipMemcpyAsync(idxi, h->w_I.p, k * 8, hipMemcpyDeviceToHost, h->stream));
@@ -3913,6 +3576,15 @@ int amd_ivf_scan_codes(amd_ivf_t* h, const float* query, size_t list_no, int sto
     if (nup) *nup = st[2];
     double ms[NCAT], ln[NCAT];
     h->timer.collect(ms, NCAT, ln);
+}
+
+int amd_ivf_scan_codes(amd_ivf_t* h, const float* query, size_t list_no, int store_pairs, size_t k, float* simi,
+                       int64_t* idxi, size_t* nup) {
+    API_BEGIN
+    OWNER_ONLY(h);
+    use_device(h);
+    ListScan r = list_scan(h, query, list_no);
+    scan_into_heap(h, r, store_pairs, k, simi, idxi, nup);
     API_END
 }
 
@@ -3945,56 +3617,14 @@ int amd_ivf_distance_to_code(amd_ivf_t* h, const float* query, size_t list_no, s
     API_END
 }
 
-// one query against vectors [offset, offset + n) of a list: the round of exec_round over that part
-static RoundSpec list_part_round(amd_ivf* h, const float* query, size_t list_no, size_t offset, size_t n, const int64_t* key0) {
-    if (list_no >= h->nlist) throw EngineError("Invalid key");
-    upload_lists(h);
-    const std::vector<uint64_t>& off = ix(h)->h_list_off;
-    if (offset + n > off[list_no + 1] - off[list_no]) throw EngineError("codes beyond the end of the list");
-    h->w_x.ensure(h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), query, 1);
-    RoundSpec r;
-    r.slot = {0};
-    r.p0 = {0};
-    r.cnt = {1};
-    r.keys = key0;
-    r.key_stride = 1;
-    r.finalize_all = 1;
-    r.d_x = h->w_x.as<float>();
-    r.sub_base = off[list_no] + offset;
-    r.sub_n = n;
-    IntRange qr;
-    qr.add(query, (size_t)h->d);
-    r.fused = h->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
-    return r;
-}
-
 int amd_ivf_scan_codes_at(amd_ivf_t* h, const float* query, size_t list_no, size_t offset, size_t n, int store_pairs, size_t k, float* simi,
                           int64_t* idxi, size_t* nup) {
     API_BEGIN
     use_device(h);
     if (nup) *nup = 0;
-    const int64_t key0 = 0;
-    RoundSpec r = list_part_round(h, query, list_no, offset, n, &key0);
+    ListScan r = list_part_scan(h, query, list_no, offset, n);
     if (n == 0 || k == 0) return 0;
-    init_state(h, 1, k, false);
-    HIP_CHECK(hipMemcpyAsync(h->w_heap_val.p, simi, k * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipMemcpyAsync(h->w_heap_ref.p, idxi, k * 8, hipMemcpyHostToDevice, h->stream));
-    r.k = (int)k;
-    r.store_pairs = store_pairs;
-    r.pair_list = (long long)list_no;
-    r.raw_heap_out = 1;
-    exec_round(h, r);
-    check_device_error(h);
-    HIP_CHECK(hipMemcpyAsync(simi, h->w_D.p, k * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipMemcpyAsync(idxi, h->w_I.p, k * 8, hipMemcpyDeviceToHost, h->stream));
-    unsigned long long rows[4 * STATS_ROWS], st[4];
-    HIP_CHECK(hipMemcpyAsync(rows, h->w_stats.p, sizeof rows, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(stream_sync(h->stream));
-    sum_stat_rows(rows, st);
-    if (nup) *nup = st[2];
-    double ms[NCAT], ln[NCAT];
-    h->timer.collect(ms, NCAT, ln);
+    scan_into_heap(h, r, store_pairs, k, simi, idxi, nup);
     API_END
 }
 
@@ -4004,14 +3634,12 @@ int amd_ivf_scan_codes_range(amd_ivf_t* h, const float* query, size_t list_no, s
     *count = 0;
     h->r_part_pos.clear();
     h->r_part_dis.clear();
-    const int64_t key0 = 0;
-    RoundSpec r = list_part_round(h, query, list_no, offset, n, &key0);
+    ListScan r = list_part_scan(h, query, list_no, offset, n);
     if (n == 0) return 0;
     init_state(h, 1, 1, false);
-    r.k = 1;
     r.collect = true;
-    r.collect_radius = radius;
-    exec_round(h, r);
+    r.radius = radius;
+    scan_list_run(h, r);
     uint32_t cnt = 0;
     HIP_CHECK(hipMemcpyAsync(&cnt, h->w_sub_off.as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(stream_sync(h->stream));
@@ -4252,9 +3880,7 @@ static void adaptive_slice(amd_ivf_t* L, const float* d_x, size_t id0, size_t n,
             // takes whole runs into a round, so the scan does not depend on it).  With the level-parallel filling and the pipelined
             // heap sort (nlist a power of two) the heap takes ~1.5 ms a row, about what coarse ranking -> planning -> scan of
             // round 0 take among other searches; the literal heap (12 ms a row) stays under the pass and feeds a second one.
-            // (only run_rounds_device calls RoundSpec::before_first_select: with the host-planned rounds of AUNCEL_AMD_HOST_PLAN the
-            // heap's order feeds the second pass instead, as for an nlist that is not a power of two)
-            static const bool no_patch = getenv("AUNCEL_AMD_NO_TIE_PATCH") != nullptr || getenv("AUNCEL_AMD_HOST_PLAN") != nullptr;
+            static const bool no_patch = getenv("AUNCEL_AMD_NO_TIE_PATCH") != nullptr;
             L->spec_inline = !no_patch && (nlist & (nlist - 1)) == 0 && nlist >= 64;
         }
     }
@@ -4381,15 +4007,6 @@ static void adaptive_slice(amd_ivf_t* L, const float* d_x, size_t id0, size_t n,
     // round but the ones in which equal distances met, whose result is the reference's heap replayed over ~500 admissions, 0.3 ms on
     // one wave; profiles/r05_latency_batch1.txt)
     const size_t first_env = std::max<size_t>(1, (size_t)opt(L, OPT_ROUND_FIRST, 12));
-    static const bool host_plan = getenv("AUNCEL_AMD_HOST_PLAN") != nullptr;
-    if (host_plan) {
-        run_rounds(L, base, n, first_env, np_row, dnp, id0);
-        HIP_CHECK(hipMemcpyAsync(D, L->w_D.p, n * K * 4, hipMemcpyDeviceToHost, L->stream));
-        HIP_CHECK(hipMemcpyAsync(I, L->w_I.p, n * K * 8, hipMemcpyDeviceToHost, L->stream));
-        HIP_CHECK(stream_sync(L->stream));
-        fold_stats(L, n);
-        return;
-    }
     base.caller_checks_error = true;
     DirectOut direct(L, D, I);
     host_stamp("state");
@@ -4489,8 +4106,7 @@ static void adaptive_core_once(amd_ivf_t* h, const float* d_x, size_t start, siz
     }
     for (amd_ivf* L : lanes) {
         L->force_heap_select = h->force_heap_select;
-        L->scan_bytes = L->scan_min_bytes = L->scan_min_bytes_thr = 0;
-        L->scan_slots = L->scan_useful = 0;
+        reset_scan_counters(L);
     }
     // what this function reads back once the slices are done (one lane: queued together with the slice's own read-backs, or --
     // a few queries -- with the look after the first round)
@@ -4845,8 +4461,7 @@ static void train_core(amd_ivf_t* h, const float* d_x, size_t start, size_t n, s
     base.train.arcos = h->d_arcos.as<float>();
     base.train.gt_D = h->w_misc2.as<float>();
     base.train.raw = reinterpret_cast<float* const*>(h->w_rawptrs.p);
-    if (getenv("AUNCEL_AMD_HOST_PLAN")) run_rounds(h, base, n, 32, np_row, nullptr, start);
-    else run_rounds_device(h, base, n, 32, np_row, nullptr);
+    run_rounds_device(h, base, n, 32, np_row, nullptr);
     HIP_CHECK(hipMemcpyAsync(D, h->w_D.p, n * K * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipMemcpyAsync(I, h->w_I.p, n * K * 8, hipMemcpyDeviceToHost, h->stream));
     for (size_t i = 0; i < ntr; i++)

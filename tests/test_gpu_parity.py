@@ -159,6 +159,68 @@ def test_scanner_over_list_parts(capi, oracle, name):
         assert len(pos0) == 0
 
 
+@pytest.mark.parametrize("metric", [1, 0])
+@pytest.mark.parametrize("d", [30, 128])
+def test_scanner_over_several_tiles(capi, oracle, d, metric):
+    """The scanner API over a list longer than one 128-vector scan tile (the golden cases' lists are shorter): 300 vectors, two
+    full tiles and a partial one, beside an empty list.  The whole list, runs cut at the tile edges and one vector either side
+    of them (one-vector runs, runs that start inside a tile), and a range scan across both edges leave the heap, the update
+    counts, the store_pairs labels and the (position, distance) pairs of the pinned oracle's scanner, bit for bit."""
+    n, k = 300, 10
+    is_l2 = metric == 1
+    rs = np.random.RandomState(100 * d + metric)
+    xq = rs.randn(d).astype(np.float32)
+    xb = rs.randn(n, d).astype(np.float32)
+    # the better vectors tend to come later, so that every tile and most runs admit some of theirs and turn others away
+    od = oracle.knn(metric, xb, xq[None, :], 1)[0][:, 0]
+    good = -od if is_l2 else od
+    xb = xb[np.argsort(good + rs.randn(n).astype(np.float32) * good.std())]
+    ids = rs.permutation(100000)[:n].astype(np.int64)
+    h = capi.Handle(d, 2, metric, 0)
+    h.set_centroids(rs.randn(2, d).astype(np.float32))
+    h.set_lists_from_assign(xb, np.zeros(n, dtype=np.int64), ids=ids)
+    assert [h.list_size(0), h.list_size(1)] == [n, 0]
+    fmax = np.finfo(np.float32).max
+
+    def fresh():
+        return np.full(k, fmax if is_l2 else -fmax, dtype=np.float32), np.full(k, -1, dtype=np.int64)
+
+    cuts = [0, 1, 127, 128, 129, 256, 299, 300]
+    for pairs in (False, True):
+        simi, idxi = fresh()
+        want_simi, want_idxi = fresh()
+        nup = h.scan_codes(xq, 0, simi, idxi, store_pairs=pairs)
+        want_nup = oracle.scan_codes(metric, xq, xb, ids, 0, pairs, want_simi, want_idxi)
+        assert nup == want_nup and nup > k
+        assert np.array_equal(bits(simi), bits(want_simi))
+        assert np.array_equal(idxi, want_idxi)
+        # the empty list leaves a heap as it finds it
+        assert h.scan_codes(xq, 1, simi, idxi, store_pairs=pairs) == 0
+        assert np.array_equal(bits(simi), bits(want_simi))
+        assert np.array_equal(idxi, want_idxi)
+        # in runs: one heap carried from run to run (store_pairs labels count from each run's first vector)
+        run_simi, run_idxi = fresh()
+        want_run_simi, want_run_idxi = fresh()
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            nup = h.scan_codes_at(xq, 0, a, b - a, run_simi, run_idxi, store_pairs=pairs)
+            want_nup = oracle.scan_codes(metric, xq, xb[a:b], ids[a:b], 0, pairs, want_run_simi, want_run_idxi)
+            assert nup == want_nup, (a, b)
+            assert np.array_equal(bits(run_simi), bits(want_run_simi)), (a, b)
+            assert np.array_equal(run_idxi, want_run_idxi), (a, b)
+        assert np.array_equal(bits(run_simi), bits(want_simi))
+        if not pairs:
+            assert np.array_equal(run_idxi, want_idxi)
+    # range scan of [127, 257): the oracle's per-pair distances, filtered at a radius that keeps about a third
+    a, b = 127, 257
+    od = oracle.knn(metric, xb[a:b], xq[None, :], 1)[0][:, 0]
+    radius = float(np.sort(od)[(b - a) // 3 if is_l2 else (b - a) - (b - a) // 3])
+    pos, dis = h.scan_codes_range(xq, 0, a, b - a, radius)
+    want = np.nonzero(od < radius if is_l2 else od > radius)[0]
+    assert 0 < len(want) < b - a
+    assert np.array_equal(pos, want.astype(np.uint32))
+    assert np.array_equal(bits(dis), bits(od[want]))
+
+
 @pytest.mark.parametrize("name", ["fixed_sift_l2", "fixed_ragged", "fixed_dups"])
 def test_add_builds_reference_lists(capi, name):
     """IndexIVFFlat::add_core: nearest-centroid assignment + append in input order"""
