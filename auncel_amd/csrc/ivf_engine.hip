@@ -372,7 +372,7 @@ struct amd_ivf {
     size_t stage_used = 0;
     CopySegs h2d_pending{};
     std::vector<std::function<void()>> after_flush;  // run by sync_and_flush behind the synchronisation (deferred epilogues)
-    bool want_first_tie = false;        // adaptive_slice: also leave the start of each ranking's first run of equal distances
+    bool want_first_tie = false;        // adaptive_core_once: also leave the start of each ranking's first run of equal distances
     size_t first_tie_nreal = 0;
     DevBuf w_first_tie;
     std::vector<uint32_t> first_tie_host;
@@ -380,14 +380,14 @@ struct amd_ivf {
     // the window a query can read in its first two rounds) are set aside and re-ranked on a side stream WHILE the first pass
     // searches; the second pass takes its rankings from those slots instead of running the heap (2.75 ms at nlist 4096) itself
     DevBuf w_spec_full, w_spec_dis, w_spec_keys, w_spec_count, w_spec_slot, w_spec_pick, w_redo_idx, w_spec_query, w_spec_scratch, w_split;
-    uint32_t spec_cap = 512;        // slots of this search (adaptive_slice)
+    uint32_t spec_cap = 512;        // slots of this search (adaptive_core_once)
     bool spec_inline = false;       // the heap's order was applied to the first pass itself (launch_tie_patch): only what it could not fix is searched again
     uint32_t tie_patched_host = 0;  // rankings of the last first pass that the heap's order changed
     hipStream_t spec_stream = nullptr;  // (= bg_stream)
     hipEvent_t ev_spec_go = nullptr, ev_spec_done = nullptr;
     bool spec_wanted = false;  // set by adaptive_redo_ties around its first pass (small calls repeat as a whole: no slots)
     bool spec_done = false;   // run_rounds_device: the search ended at its first look and the caller's read-backs came with it
-    // a call of at most four queries: init_state / byte_queries record their launches here instead of making them, and adaptive_slice
+    // a call of at most four queries: init_state / byte_queries record their launches here instead of making them, and adaptive_core_once
     // makes them as one (launch_small_state)
     struct SmallFuse {
         bool active = false, have_init = false, have_bytes = false;
@@ -522,24 +522,20 @@ struct amd_ivf {
     double scan_bytes = 0, scan_slots = 0, scan_useful = 0, scan_min_bytes = 0, scan_min_bytes_thr = 0;
     EventTimer timer;
 
-    // Query lanes: a large adaptive batch is cut into slices that run their rounds concurrently, each on
-    // its own stream with its own workspaces (kids borrow the index data of `parent`), so that one
-    // slice's latency-bound selection and host-side round planning overlap another slice's VALU-bound scan.
     struct AsyncPool* async = nullptr;  // owner only: internal search contexts + worker threads of amd_ivf_submit_* (below)
     std::vector<amd_ivf*> async_ctx;    // those contexts (statistics and settings of the owner cover them)
     int async_depth = 4;
+    // Set exactly on a handle made by amd_ivf_clone: a search context with a stream and workspaces of its own over the index data
+    // (lists, centroids, tuner, options) of `parent`, the owning handle.  ix() / opt() reach that data from either kind of handle.
     amd_ivf* parent = nullptr;
-    bool is_clone = false;  // made by amd_ivf_clone: a search context of its own over the parent's index data
     std::mutex upload_mu;   // owner only: serialises the first upload of the lists
     std::mutex async_mu;    // owner only: serialises the creation of the asynchronous pool
-    std::vector<std::unique_ptr<amd_ivf>> kids;
     // side streams for the sparse tile shapes of a round (fork / join around the dense launch)
     hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
 
     ~amd_ivf() {
         async_shutdown(this);
-        kids.clear();
         for (int i = 0; i < 4; i++) {
             if (aux[i]) (void)hipStreamDestroy(aux[i]);
             if (ev_join[i]) (void)hipEventDestroy(ev_join[i]);
@@ -1124,6 +1120,29 @@ void upload_rows(amd_ivf* h, float* dst, const float* src, size_t n) {
     }
 }
 
+// The query rows of a search on the device, and the range of their values (what decides between exact, fused and byte arithmetic)
+struct QueryRows {
+    const float* d_x;
+    IntRange range;
+};
+// n x d rows from the host, into w_x
+QueryRows host_rows(amd_ivf* h, const float* x, size_t n) {
+    h->w_x.ensure(n * h->dpad * sizeof(float));
+    upload_rows(h, h->w_x.as<float>(), x, n);
+    QueryRows r{h->w_x.as<float>(), IntRange()};
+    r.range.add(x, n * (size_t)h->d);
+    return r;
+}
+// whose resident queries h searches: a search context that was never given any of its own searches its owner's (the contexts of
+// amd_ivf_submit_*)
+const amd_ivf* resident_owner(const amd_ivf* h) { return h->parent && h->n_resident == 0 ? h->parent : h; }
+// resident rows [start, start + n)
+QueryRows resident_rows(const amd_ivf* h, size_t start, size_t n) {
+    const amd_ivf* src = resident_owner(h);
+    if (start + n > src->n_resident) throw EngineError("resident query range out of bounds");
+    return {src->d_resident.as<float>() + start * h->dpad, src->resident_range};
+}
+
 // ------------------------------------------------------------------------------------ state
 struct State {  // per query slot
     float* heap_val;
@@ -1254,7 +1273,7 @@ struct RoundSpec {
     // a call of a few queries: queues the caller's own read-backs (results, statistics, error word) so that the look after the first
     // round can bring them along -- three calls in four end there, and then end with that one synchronisation
     std::function<void()> spec_finish;
-    // AUNCEL_AMD_COARSE_TIES=redo with the heap's order arriving while the first round is scanned (adaptive_slice): enqueued between
+    // AUNCEL_AMD_COARSE_TIES=redo with the heap's order arriving while the first round is scanned (adaptive_core_once): enqueued between
     // the scan and the selection of round 0 -- waits for the heap, patches the ranking and the round's rows (launch_tie_patch),
     // then derives the stop rule's boundary distances from the patched ranking.  run_ties: rounds take whole runs of equal
     // coarse distances (PlanArgs::run_dis).
@@ -1577,6 +1596,22 @@ struct SmallCopies {
         h->small.clear();
         h->small_used = 0;
         h->after_flush.clear();
+    }
+};
+
+// The coarse tie-order regime of a search, as its caller sets it on the handle (ties_override, want_first_tie, spec_wanted,
+// spec_use): back to the default when the scope is left, by return or by exception.  (spec_valid is not part of it:
+// adaptive_redo_ties reads it after its first pass.)
+struct TieRegime {
+    amd_ivf* h;
+    explicit TieRegime(amd_ivf* hh) : h(hh) {}
+    TieRegime(const TieRegime&) = delete;
+    TieRegime& operator=(const TieRegime&) = delete;
+    ~TieRegime() {
+        h->ties_override = -1;
+        h->want_first_tie = false;
+        h->spec_wanted = false;
+        h->spec_use = false;
     }
 };
 
@@ -3079,7 +3114,7 @@ int amd_ivf_create(int d, size_t nlist, int metric, int device, amd_ivf_t** out)
 
 // Entry points that change or read back index data are for the owning handle only.
 #define OWNER_ONLY(h) \
-    if ((h)->is_clone) throw EngineError("not available on a search context made by amd_ivf_clone: use the owning handle")
+    if ((h)->parent) throw EngineError("not available on a search context made by amd_ivf_clone: use the owning handle")
 // ... and those that change it are not for an index made by amd_ivf_subset
 #define NOT_A_SUBSET(h) \
     if (ix(h)->is_subset) throw EngineError("the index is a read-only subset (amd_ivf_subset): make the change on its parent and cut again")
@@ -3091,7 +3126,6 @@ int amd_ivf_clone(amd_ivf_t* h, amd_ivf_t** out) {
     upload_lists(owner);
     std::unique_ptr<amd_ivf> c(new amd_ivf);
     c->parent = owner;
-    c->is_clone = true;
     c->d = owner->d;
     c->dpad = owner->dpad;
     c->nlist = owner->nlist;
@@ -3111,7 +3145,7 @@ int amd_ivf_destroy(amd_ivf_t* h) {
     API_BEGIN
     if (h) {
         use_device(h);
-        if (h->is_clone && h->parent) h->parent->live_contexts.fetch_sub(1);
+        if (h->parent) h->parent->live_contexts.fetch_sub(1);
         delete h;
     }
     API_END
@@ -3263,14 +3297,11 @@ int amd_ivf_coarse(amd_ivf_t* h, size_t n, const float* x, size_t nprobe, float*
     if (n == 0) return 0;
     WallClock wc(h->stream);
     reset_scan_counters(h);
-    h->w_x.ensure(n * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
+    const QueryRows q = host_rows(h, x, n);
     h->w_cdis.ensure(n * nprobe * 4);
     h->w_ckeys.ensure(n * nprobe * 8);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
-    coarse_dev(h, h->w_x.as<float>(), n, nprobe, mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
-               h->allow_fused && h->centroid_range.fusable_with(qr, h->metric));
+    coarse_dev(h, q.d_x, n, nprobe, mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
+               h->allow_fused && h->centroid_range.fusable_with(q.range, h->metric));
     HIP_CHECK(hipMemcpyAsync(coarse_dis, h->w_cdis.p, n * nprobe * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipMemcpyAsync(keys, h->w_ckeys.p, n * nprobe * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(stream_sync(h->stream));
@@ -3281,16 +3312,14 @@ int amd_ivf_coarse(amd_ivf_t* h, size_t n, const float* x, size_t nprobe, float*
 int amd_ivf_coarse_resident(amd_ivf_t* h, size_t start, size_t n, size_t nprobe, float* coarse_dis, int64_t* keys, int mode) {
     API_BEGIN
     use_device(h);
-    // (a search context without resident queries of its own ranks its owner's: amd_ivf_submit_coarse_resident's contexts)
-    const amd_ivf* src = h->is_clone && h->n_resident == 0 && h->parent ? h->parent : h;
-    if (start + n > src->n_resident) throw EngineError("resident query range out of bounds");
+    const QueryRows q = resident_rows(h, start, n);
     if (n == 0) return 0;
     WallClock wc(h->stream);
     reset_scan_counters(h);
     h->w_cdis.ensure(n * nprobe * 4);
     h->w_ckeys.ensure(n * nprobe * 8);
-    coarse_dev(h, src->d_resident.as<float>() + start * h->dpad, n, nprobe, mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
-               h->allow_fused && ix(h)->centroid_range.fusable_with(src->resident_range, h->metric));
+    coarse_dev(h, q.d_x, n, nprobe, mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
+               h->allow_fused && ix(h)->centroid_range.fusable_with(q.range, h->metric));
     if (coarse_dis) HIP_CHECK(hipMemcpyAsync(coarse_dis, h->w_cdis.p, n * nprobe * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipMemcpyAsync(keys, h->w_ckeys.p, n * nprobe * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(stream_sync(h->stream));
@@ -3306,13 +3335,10 @@ int amd_ivf_search_preassigned(amd_ivf_t* h, size_t n, const float* x, size_t k,
     if (n == 0 || k == 0) return 0;
     WallClock wc(h->stream);
     reset_scan_counters(h);
-    h->w_x.ensure(n * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
+    const QueryRows q = host_rows(h, x, n);
     h->w_ckeys.ensure(n * nprobe * 8);
     HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, keys, n * nprobe * 8, hipMemcpyHostToDevice, h->stream));
-    search_fixed_device(h, h->w_x.as<float>(), n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, store_pairs, max_codes, qr);
+    search_fixed_device(h, q.d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, store_pairs, max_codes, q.range);
     finish_timing(h, wc.stop());
     API_END
 }
@@ -3323,11 +3349,8 @@ int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t npro
     if (n == 0 || k == 0) return 0;
     WallClock wc(h->stream);
     reset_scan_counters(h);
-    h->w_x.ensure(n * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
-    search_full(h, h->w_x.as<float>(), n, k, nprobe, coarse_mode, D, I, qr);
+    const QueryRows q = host_rows(h, x, n);
+    search_full(h, q.d_x, n, k, nprobe, coarse_mode, D, I, q.range);
     finish_timing(h, wc.stop());
     API_END
 }
@@ -3375,10 +3398,7 @@ int amd_ivf_range_search_preassigned(amd_ivf_t* h, size_t n, const float* x, flo
     use_device(h);
     if (nprobe == 0) throw EngineError("nprobe must be positive");
     WallClock wc(h->stream);
-    h->w_x.ensure(std::max<size_t>(n, 1) * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
+    const QueryRows q = host_rows(h, x, n);
     h->w_ckeys.ensure(std::max<size_t>(n, 1) * nprobe * 8);
     if (n) HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, keys, n * nprobe * 8, hipMemcpyHostToDevice, h->stream));
     if (n == 0) {
@@ -3389,7 +3409,7 @@ int amd_ivf_range_search_preassigned(amd_ivf_t* h, size_t n, const float* x, flo
         return 0;
     }
     reset_scan_counters(h);
-    range_core(h, h->w_x.as<float>(), n, radius, nprobe, h->w_ckeys.as<int64_t>(), qr, lims);
+    range_core(h, q.d_x, n, radius, nprobe, h->w_ckeys.as<int64_t>(), q.range, lims);
     finish_timing(h, wc.stop());
     API_END
 }
@@ -3406,17 +3426,14 @@ int amd_ivf_range_search(amd_ivf_t* h, size_t n, const float* x, float radius, s
         lims[0] = 0;
         return 0;
     }
-    h->w_x.ensure(n * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
+    const QueryRows q = host_rows(h, x, n);
     upload_lists(h);
     h->w_cdis.ensure(n * nprobe * 4);
     h->w_ckeys.ensure(n * nprobe * 8);
-    coarse_dev(h, h->w_x.as<float>(), n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
-               h->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric));
+    coarse_dev(h, q.d_x, n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
+               h->allow_fused && ix(h)->centroid_range.fusable_with(q.range, h->metric));
     reset_scan_counters(h);
-    range_core(h, h->w_x.as<float>(), n, radius, nprobe, h->w_ckeys.as<int64_t>(), qr, lims);
+    range_core(h, q.d_x, n, radius, nprobe, h->w_ckeys.as<int64_t>(), q.range, lims);
     finish_timing(h, wc.stop());
     API_END
 }
@@ -3434,15 +3451,14 @@ int amd_ivf_search_resident_preassigned(amd_ivf_t* h, size_t start, size_t n, si
                                         int64_t* I) {
     API_BEGIN
     use_device(h);
-    const amd_ivf* src = h->is_clone && h->n_resident == 0 && h->parent ? h->parent : h;  // (as amd_ivf_search_resident)
-    if (start + n > src->n_resident) throw EngineError("resident query range out of bounds");
+    const QueryRows q = resident_rows(h, start, n);
     if (n == 0 || k == 0) return 0;
     if (!keys) throw EngineError("keys are required");
     WallClock wc(h->stream);
     reset_scan_counters(h);
     h->w_ckeys.ensure(n * nprobe * 8);
     HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, keys, n * nprobe * 8, hipMemcpyHostToDevice, h->stream));
-    search_fixed_device(h, src->d_resident.as<float>() + start * h->dpad, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, src->resident_range);
+    search_fixed_device(h, q.d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, q.range);
     finish_timing(h, wc.stop());
     API_END
 }
@@ -3450,13 +3466,11 @@ int amd_ivf_search_resident_preassigned(amd_ivf_t* h, size_t start, size_t n, si
 int amd_ivf_search_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I) {
     API_BEGIN
     use_device(h);
-    // (a search context without resident queries of its own searches its owner's: amd_ivf_submit_search_resident's contexts)
-    const amd_ivf* src = h->is_clone && h->n_resident == 0 && h->parent ? h->parent : h;
-    if (start + n > src->n_resident) throw EngineError("resident query range out of bounds");
+    const QueryRows q = resident_rows(h, start, n);
     if (n == 0 || k == 0) return 0;
     WallClock wc(h->stream);
     reset_scan_counters(h);
-    search_full(h, src->d_resident.as<float>() + start * h->dpad, n, k, nprobe, coarse_mode, D, I, src->resident_range);
+    search_full(h, q.d_x, n, k, nprobe, coarse_mode, D, I, q.range);
     finish_timing(h, wc.stop());
     API_END
 }
@@ -3476,10 +3490,12 @@ static void timed_core(amd_ivf* h, const float* d_x, size_t start, size_t n, siz
     // Runs of equal coarse distances stay in centroid-number order here unless AUNCEL_AMD_COARSE_TIES=heap: where the
     // clock decides how deep a query goes, which of two equidistant lists comes first is immaterial, and re-running the
     // reference's heap over all nlist entries (2.8 ms at 4096) would cost more than most budgets.
-    h->ties_override = (int)opt(h, OPT_COARSE_TIES, -1) == 1 ? 1 : 0;
-    coarse_dev(h, d_x, n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
-               h->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric));
-    h->ties_override = -1;
+    {
+        TieRegime regime(h);
+        h->ties_override = (int)opt(h, OPT_COARSE_TIES, -1) == 1 ? 1 : 0;
+        coarse_dev(h, d_x, n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
+                   h->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric));
+    }
     init_state(h, n, k, false);
     RoundSpec base;
     base.k = (int)k;
@@ -3524,11 +3540,8 @@ int amd_ivf_search_timed_x(amd_ivf_t* h, size_t n, const float* x, size_t id_off
     if (n == 0 || k == 0) return 0;
     WallClock wc(h->stream);
     reset_scan_counters(h);
-    h->w_x.ensure(n * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
-    timed_core(h, h->w_x.as<float>(), id_offset, n, k, nprobe, budget_ms, coarse_mode, nprobe_used, D, I, qr);
+    const QueryRows q = host_rows(h, x, n);
+    timed_core(h, q.d_x, id_offset, n, k, nprobe, budget_ms, coarse_mode, nprobe_used, D, I, q.range);
     finish_timing(h, wc.stop());
     API_END
 }
@@ -3537,16 +3550,13 @@ int amd_ivf_search_timed_x(amd_ivf_t* h, size_t n, const float* x, size_t id_off
 static ListScan list_scan(amd_ivf* h, const float* query, size_t list_no) {
     if (list_no >= h->nlist) throw EngineError("Invalid key");
     upload_lists(h);
-    h->w_x.ensure(h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), query, 1);
+    const QueryRows q = host_rows(h, query, 1);
     const std::vector<uint64_t>& off = ix(h)->h_list_off;
     ListScan r;
     r.list_no = list_no;
     r.base = off[list_no];
     r.n = off[list_no + 1] - off[list_no];
-    IntRange qr;
-    qr.add(query, (size_t)h->d);
-    r.fused = h->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
+    r.fused = h->allow_fused && ix(h)->db_range.fusable_with(q.range, h->metric);
     return r;
 }
 // ... against vectors [offset, offset + n) of it
@@ -3788,247 +3798,45 @@ int amd_ivf_set_tuner(amd_ivf_t* h, size_t max_topk, size_t ntraces, const size_
     API_END
 }
 
-// one slice of an adaptive batch: queries [q0, q0+n) of the call, on lane `L` (L == h or one of h's kids)
 // The coarse ranking of a tune / train search into w_cdis / w_ckeys: the engine's own over all nlist centroids (what
 // Error_sys::search asks its quantizer for, profile.cpp:220), or the rows the caller handed to search_preassigned
 // (Auncel/IndexIVF.cpp:382-386).  Returns the row length = the length of the probe loop.
-static size_t coarse_or_given(amd_ivf_t* L, const float* d_x, size_t n, int coarse_mode, bool fused_ok, size_t coarse_prefix) {
-    const size_t nlist = L->nlist;
-    if (L->spec_use) {  // second pass of the "redo" regime: these queries' rankings were re-ranked while the first pass ran
-        L->w_cdis.ensure(n * nlist * 4);
-        L->w_ckeys.ensure(n * nlist * 8);
-        HIP_CHECK(hipStreamWaitEvent(L->stream, L->ev_spec_done, 0));
-        launch_spec_gather(L->w_spec_pick.as<int32_t>(), (uint32_t)n, (uint32_t)nlist, (uint32_t)L->spec_ncopy, L->w_spec_dis.as<float>(),
-                           L->w_spec_keys.as<int64_t>(), L->w_cdis.as<float>(), L->w_ckeys.as<int64_t>(), L->stream);
-        L->tie_rows_host += n;
+static size_t coarse_or_given(amd_ivf_t* h, const float* d_x, size_t n, int coarse_mode, bool fused_ok, size_t coarse_prefix) {
+    const size_t nlist = h->nlist;
+    if (h->spec_use) {  // second pass of the "redo" regime: these queries' rankings were re-ranked while the first pass ran
+        h->w_cdis.ensure(n * nlist * 4);
+        h->w_ckeys.ensure(n * nlist * 8);
+        HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_spec_done, 0));
+        launch_spec_gather(h->w_spec_pick.as<int32_t>(), (uint32_t)n, (uint32_t)nlist, (uint32_t)h->spec_ncopy, h->w_spec_dis.as<float>(),
+                           h->w_spec_keys.as<int64_t>(), h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(), h->stream);
+        h->tie_rows_host += n;
         return nlist;
     }
-    if (!L->given_keys) {
-        L->w_cdis.ensure(n * nlist * 4);
-        L->w_ckeys.ensure(n * nlist * 8);
-        coarse_dev(L, d_x, n, nlist, coarse_mode, L->w_cdis.as<float>(), L->w_ckeys.as<int64_t>(), fused_ok, coarse_prefix);
+    if (!h->given_keys) {
+        h->w_cdis.ensure(n * nlist * 4);
+        h->w_ckeys.ensure(n * nlist * 8);
+        coarse_dev(h, d_x, n, nlist, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(), fused_ok, coarse_prefix);
         return nlist;
     }
-    const size_t np = L->given_nprobe;
+    const size_t np = h->given_nprobe;
     if (np <= nlist / 8 + 20) throw EngineError("tune / train mode reads coarse entries 0 .. nlist/8 + 20: nprobe too small");
-    L->w_cdis.ensure(n * np * 4);
-    L->w_ckeys.ensure(n * np * 8);
-    HIP_CHECK(hipMemcpyAsync(L->w_cdis.p, L->given_dis, n * np * 4, hipMemcpyHostToDevice, L->stream));
-    HIP_CHECK(hipMemcpyAsync(L->w_ckeys.p, L->given_keys, n * np * 8, hipMemcpyHostToDevice, L->stream));
+    h->w_cdis.ensure(n * np * 4);
+    h->w_ckeys.ensure(n * np * 8);
+    HIP_CHECK(hipMemcpyAsync(h->w_cdis.p, h->given_dis, n * np * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, h->given_keys, n * np * 8, hipMemcpyHostToDevice, h->stream));
     return np;
 }
 
-static void adaptive_slice(amd_ivf_t* L, const float* d_x, size_t id0, size_t n, size_t query_topk, float multipler, float std_m,
-                           const float* dreq, const float* dgt, unsigned long long* dnp, float* dtr, int profile, int coarse_mode,
-                           float* D, int64_t* I, const IntRange& qr, size_t coarse_prefix, bool defer_finish,
-                           const std::function<void()>* tail_gathers = nullptr) {
-    use_device(L);
-    const size_t K = ix(L)->tuner_max_topk, nlist = L->nlist;
-    // full coarse ranking (Error_sys::search sets nprobe = nlist, profile.cpp:220), or the caller's
-    const size_t np_row = coarse_or_given(L, d_x, n, coarse_mode, ix(L)->allow_fused && ix(L)->centroid_range.fusable_with(qr, L->metric), coarse_prefix);
-    host_stamp("coarse");
-    // (at most four queries: the four small launches between the coarse ranking and the first round are made as one)
-    const bool fuse_small = n <= 4 && !L->spec_wanted;
-    if (L->want_first_tie) {
-        L->w_first_tie.ensure(n * 4);
-        // Which queries will have to be searched again is known only when this pass ends (first run < 2 my_nprobe + 14), but the
-        // expensive part of searching them again -- the reference's heap over all nlist centroids, a serial 4096-element heap
-        // sort per query -- needs nothing from this pass.  Every query that could qualify with the probes of the first two
-        // rounds gets its rows set aside now (the distance table lives in w_dist, which round 0 overwrites) and the heap runs on
-        // a side stream under this pass.
-        static const bool no_spec = getenv("AUNCEL_AMD_NO_TIE_SPECULATION") != nullptr;
-        // (slots for the rankings whose first run is in reach: 512 for calls of up to 5000 queries -- about 400 of the bench workload's
-        // 5000 rankings take one -- and an eighth of the call beyond, so that larger calls, e.g. queued tickets served together, do not
-        // send what overflows through the second pass)
-        const uint32_t SPEC_CAP = n <= 5120 ? 512u : (uint32_t)(((n / 8 + 63) / 64) * 64);
-        constexpr uint32_t SPEC_NEAR = 64, SPEC_WINDOW = 2 * (12 + 144) + 14;
-        L->spec_cap = SPEC_CAP;
-        L->spec_valid = false;
-        const bool can_spec = !no_spec && L->spec_wanted && !L->given_keys && np_row == nlist && n <= L->dist_budget_floats / std::max<size_t>(nlist, 1) &&
-                              heap_tie_order_lds((uint32_t)nlist, (uint32_t)nlist) <= 160 * 1024;
-        if (!can_spec && !fuse_small)
-            launch_first_tie(L->w_cdis.as<float>(), (uint32_t)n, (uint32_t)nlist, (uint32_t)L->first_tie_nreal, L->w_first_tie.as<uint32_t>(), L->stream);
-        if (can_spec) {
-            const size_t ncopy = std::min(L->first_tie_nreal, nlist);
-            L->w_spec_full.ensure((size_t)SPEC_CAP * nlist * 4);
-            L->w_spec_dis.ensure((size_t)SPEC_CAP * nlist * 4);
-            L->w_spec_keys.ensure((size_t)SPEC_CAP * nlist * 8);
-            L->w_spec_count.ensure(32);  // count | rankings the patch changed | rows the heap re-ranked (u64; not reported: most are never used) | scratch cursor (u64)
-            L->w_spec_slot.ensure(n * 4);
-            L->w_spec_query.ensure((size_t)SPEC_CAP * 4);
-            ensure_context_streams(L);
-            HIP_CHECK(hipStreamWaitEvent(L->stream, L->ev_spec_done, 0));  // (the previous search's slots are no longer being written)
-            HIP_CHECK(hipMemsetAsync(L->w_spec_count.p, 0, 32, L->stream));
-            // (the first run of every ranking and the slots of the rankings to re-rank in one launch: the heap starts right behind the
-            // coarse ranking; slots go to the waves in the order they arrive -- a ranking that finds none is searched again at the end)
-            (void)SPEC_NEAR;
-            launch_tie_collect(L->w_cdis.as<float>(), (uint32_t)n, (uint32_t)L->first_tie_nreal, SPEC_WINDOW, SPEC_CAP, (uint32_t)nlist, (uint32_t)ncopy,
-                               L->w_dist.as<float>(), L->w_ckeys.as<int64_t>(), L->w_first_tie.as<uint32_t>(), L->w_spec_count.as<uint32_t>(),
-                               L->w_spec_slot.as<int32_t>(), L->w_spec_full.as<float>(), L->w_spec_dis.as<float>(), L->w_spec_keys.as<int64_t>(),
-                               L->w_spec_query.as<uint32_t>(), L->stream);
-            HIP_CHECK(hipEventRecord(L->ev_spec_go, L->stream));
-            HIP_CHECK(hipStreamWaitEvent(L->spec_stream, L->ev_spec_go, 0));
-            launch_heap_tie_order(L->w_spec_full.as<float>(), SPEC_CAP, (uint32_t)nlist, (uint32_t)nlist, (uint32_t)ncopy, L->metric,
-                                  L->w_spec_dis.as<float>(), L->w_spec_keys.as<int64_t>(),
-                                  reinterpret_cast<unsigned long long*>(L->w_spec_count.as<uint32_t>() + 2), L->spec_stream,
-                                  L->w_spec_count.as<uint32_t>());
-            HIP_CHECK(hipEventRecord(L->ev_spec_done, L->spec_stream));
-            L->spec_valid = true;
-            L->spec_ncopy = ncopy;
-            // The heap's order can be applied to THIS pass when it arrives before anything has read the order inside a run of equal
-            // distances: that is the selection of round 0 (the stop rule's boundary distances and the probe order; the planner
-            // takes whole runs into a round, so the scan does not depend on it).  With the level-parallel filling and the pipelined
-            // heap sort (nlist a power of two) the heap takes ~1.5 ms a row, about what coarse ranking -> planning -> scan of
-            // round 0 take among other searches; the literal heap (12 ms a row) stays under the pass and feeds a second one.
-            static const bool no_patch = getenv("AUNCEL_AMD_NO_TIE_PATCH") != nullptr;
-            L->spec_inline = !no_patch && (nlist & (nlist - 1)) == 0 && nlist >= 64;
-        }
-    }
-    const bool tie_inline = L->want_first_tie && L->spec_valid && L->spec_inline;
-    struct FuseScope {  // (init_state and byte_queries record their launches while this is alive)
-        amd_ivf* h;
-        bool on;
-        FuseScope(amd_ivf* hh, bool o) : h(hh), on(o) {
-            if (on) {
-                h->fuse = amd_ivf::SmallFuse{};
-                h->fuse.active = true;
-            }
-        }
-        ~FuseScope() { h->fuse.active = false; }
-    } fuse_scope(L, fuse_small);
-    init_state(L, n, K, true);
-    auto set_online = [L, nlist, n, np_row](const uint32_t* only = nullptr, const uint32_t* only_count = nullptr, uint32_t cap = 0) {
-        launch_set_online(L->metric, (uint32_t)nlist, only ? cap : (uint32_t)n, L->w_cdis.as<float>(), L->w_ckeys.as<int64_t>(), (uint32_t)np_row,
-                          ix(L)->d_interdis.as<float>(), ix(L)->d_arcos.as<float>(), L->w_dtb.as<float>(), L->w_error.as<uint32_t>(), L->stream,
-                          only, only_count);
-    };
-    if (!fuse_small && !tie_inline) set_online();
-    RoundSpec base;
-    if (tie_inline) {
-        // room for the rows the patch moves: a round's rows of every slot if that is not beyond reason (a query that finds no room is
-        // searched again)
-        size_t maxlist = 0;
-        for (size_t l = 0; l < nlist; l++) maxlist = std::max<size_t>(maxlist, ix(L)->h_list_off[l + 1] - ix(L)->h_list_off[l]);
-        const size_t SCRATCH_FLOATS = std::min<size_t>((size_t)64 << 20, std::max<size_t>((size_t)8 << 20, (size_t)L->spec_cap * 16 * ((maxlist + 1023) & ~(size_t)1023)));
-        L->w_spec_scratch.ensure(SCRATCH_FLOATS * 4);
-        base.run_ties = true;
-        base.before_first_select = [L, nlist, set_online, SCRATCH_FLOATS]() {
-            HIP_CHECK(hipStreamWaitEvent(L->stream, L->ev_spec_done, 0));
-            TiePatchArgs ta{};
-            ta.count = L->w_spec_count.as<uint32_t>();
-            ta.cap = L->spec_cap;
-            ta.nlist = (uint32_t)nlist;
-            ta.ncopy = (uint32_t)L->spec_ncopy;
-            ta.key_stride = (uint32_t)nlist;
-            ta.slot_query = L->w_spec_query.as<uint32_t>();
-            ta.slot_of = L->w_spec_slot.as<int32_t>();
-            ta.s_keys = L->w_spec_keys.as<int64_t>();
-            ta.ckeys = L->w_ckeys.as<int64_t>();
-            ta.seg_count = L->w_pl_cnt.as<uint32_t>();
-            ta.seg_begin = L->w_seg_begin.as<uint32_t>();
-            ta.seg_list = L->w_seg_list.as<int32_t>();
-            ta.seg_off = L->w_seg_off.as<uint64_t>();
-            ta.list_off = ix(L)->d_list_off.as<uint64_t>();
-            ta.dist = L->w_dist.as<float>();
-            ta.row_align = L->row_align_now;
-            ta.scratch = L->w_spec_scratch.as<float>();
-            ta.scratch_floats = SCRATCH_FLOATS;
-            ta.cursor = reinterpret_cast<unsigned long long*>(L->w_spec_count.as<uint32_t>() + 4);
-            ta.patched = L->w_spec_count.as<uint32_t>() + 1;
-            launch_tie_patch(ta, L->stream);
-            set_online();
-        };
-        // the first selection in two launches (chained rounds; AUNCEL_AMD_NO_SPLIT_SELECT: in one, behind the heap)
-        static const bool no_split = getenv("AUNCEL_AMD_NO_SPLIT_SELECT") != nullptr;
-        if (!no_split && n >= 256) {
-            L->w_split.ensure((2 * n + 8) * 4);
-            uint32_t* counts = L->w_split.as<uint32_t>();
-            uint32_t* q_free = counts + 8;
-            uint32_t* q_wait = q_free + n;
-            const auto patch_hook = base.before_first_select;
-            const uint32_t wait_cap = (uint32_t)std::min<size_t>(n, L->spec_cap);  // (tie_collect_kernel hands out at most that many slots)
-            base.split_free = q_free;
-            base.split_wait = q_wait;
-            base.split_counts = counts;
-            base.split_wait_cap = wait_cap;
-            base.split_prepare = [L, n, counts, q_free, q_wait, set_online]() {
-                HIP_CHECK(hipMemsetAsync(counts, 0, 8, L->stream));
-                // (round 0 of an adaptive search: every query of the call is active, in order)
-                launch_partition_qsel(nullptr, nullptr, (uint32_t)n, L->w_spec_slot.as<int32_t>(), q_free, q_wait, counts, L->stream);
-                set_online();
-            };
-            base.split_between = [L, patch_hook, counts, q_wait, wait_cap, set_online]() {
-                (void)set_online;
-                patch_hook();  // (waits for the heap, patches, and derives the boundary distances again -- of every query: the patched
-                               // rankings are a tenth of them and the launch is 0.045 ms)
-            };
-        }
-    }
-    base.fused = ix(L)->allow_fused && ix(L)->db_range.fusable_with(qr, L->metric);
-    base.bytes = byte_queries(L, ix(L), d_x, n, qr);
-    if (fuse_small) {
-        L->fuse.active = false;
-        SmallStateArgs sa{};
-        sa.init = L->fuse.init;
-        sa.metric = L->metric;
-        sa.nlist = (uint32_t)nlist;
-        sa.nq = (uint32_t)n;
-        sa.coarse_dis = L->w_cdis.as<float>();
-        sa.coarse_keys = L->w_ckeys.as<int64_t>();
-        sa.coarse_stride = (uint32_t)np_row;
-        sa.interdis = ix(L)->d_interdis.as<float>();
-        sa.arcos = ix(L)->d_arcos.as<float>();
-        sa.dtb = L->w_dtb.as<float>();
-        if (L->want_first_tie) {
-            sa.ft_sorted_dis = L->w_cdis.as<float>();
-            sa.ft_stride = (uint32_t)nlist;
-            sa.ft_nreal = (uint32_t)L->first_tie_nreal;
-            sa.ft_out = L->w_first_tie.as<uint32_t>();
-        }
-        if (L->fuse.have_bytes) {
-            sa.bx = L->fuse.bx;
-            sa.bout = L->fuse.bout;
-            sa.bcx = L->fuse.bcx;
-        }
-        sa.d = L->d;
-        sa.dpad = L->dpad;
-        launch_small_state(sa, L->stream);
-    }
-    ix(L)->last_arith = base.bytes ? 2 : base.fused ? 1 : 0;
-    base.k = (int)K;
-    base.id_offset = id0;
-    base.d_x = d_x;
-    base.d_cdis = L->w_cdis.as<float>();
-    base.d_ckeys = L->w_ckeys.as<int64_t>();
-    base.coarse_stride = (uint32_t)np_row;
-    base.tuner = make_tuner(L, query_topk, multipler, std_m, dreq, dgt, dnp, dtr, profile);
-    // (one query per call: a first round of 64 probes instead of 12 ends 95 % of the bench workload's queries in it instead of 73 %,
-    // and moved neither the median nor the p90 of the call -- 0.25 / 0.56 ms: the slow tenth are not the queries that need a second
-    // round but the ones in which equal distances met, whose result is the reference's heap replayed over ~500 admissions, 0.3 ms on
-    // one wave; profiles/r05_latency_batch1.txt)
-    const size_t first_env = std::max<size_t>(1, (size_t)opt(L, OPT_ROUND_FIRST, 12));
-    base.caller_checks_error = true;
-    DirectOut direct(L, D, I);
-    host_stamp("state");
-    L->spec_done = false;
-    if (defer_finish && tail_gathers && n < 20)  // (one lane, a few queries: the read-backs may ride with the first look)
-        base.spec_finish = [&]() {
-            finish_results(L, n, K, D, I, nullptr, true);
-            (*tail_gathers)();
-        };
-    run_rounds_device(L, base, n, first_env, np_row, dnp);
-    host_stamp("rounds");
-    if (!L->spec_done) finish_results(L, n, K, D, I, nullptr, defer_finish);
+// How far into its coarse ranking an adaptive search can read: set_online reads entries 0 .. nlist/8 + 20, and the probe loop ends
+// at my_nprobe <= floor((nlist/8) * multipler) (IndexIVF.cpp:615-632) or at the value the caller passed in for the query (my_nprobe:
+// the n entries of the call's queries), plus 16 entries of slack.  May exceed nlist.
+static size_t coarse_read_bound(size_t nlist, float multipler, const uint64_t* my_nprobe, size_t n) {
+    size_t bound = std::max<size_t>(nlist / 8 + 21, (size_t)((double)(nlist / 8) * (double)multipler) + 2);
+    for (size_t i = 0; i < n; i++) bound = std::max<size_t>(bound, (size_t)my_nprobe[i] + 1);
+    return bound + 16;
 }
 
-static size_t lane_count(size_t n) {
-    static const int env = getenv("AUNCEL_AMD_SLICES") ? atoi(getenv("AUNCEL_AMD_SLICES")) : 0;
-    if (env > 0) return (size_t)env;
-    (void)n;
-    return 1;  // measured on MI355X: concurrent slices halve the queries per list and lose more in the
-               // VALU-bound scan than they hide of selection + planning (bench: 1 lane 25 ms/step, 2 lanes 29)
-}
-
+// One adaptive (tune) search of queries [start, start + n) on h, under the tie-order regime its caller has set (TieRegime)
 static void adaptive_core_once(amd_ivf_t* h, const float* d_x, size_t start, size_t n, size_t query_topk, float multipler, float std_m,
                             const float* require_acc, const float* gt_D, int profile, int coarse_mode,
                             uint64_t* my_nprobe, float* t_recalls, float* D, int64_t* I, const IntRange& qr) {
@@ -4054,13 +3862,12 @@ static void adaptive_core_once(amd_ivf_t* h, const float* d_x, size_t start, siz
     upload_lists(h);
     host_stamp("clock+lists");
     const size_t nabs = start + n;
-    // per-absolute-query arrays on the device, shared by all lanes
+    // per-absolute-query arrays on the device
     DevBuf &d_req = h->w_misc2, &d_np = h->w_misc3;
     // (sized for every resident query at once: a caller that walks through slices of its resident queries would otherwise grow
     // these arrays slice by slice -- and a reallocation frees device memory, which waits for every stream of the device: with
     // four searches in flight the first visit of a context to a later slice cost a fifth of a step)
-    const amd_ivf* rsrc = h->is_clone && h->n_resident == 0 && h->parent ? h->parent : h;
-    const size_t ncap = std::max(nabs, rsrc->n_resident);
+    const size_t ncap = std::max(nabs, resident_owner(h)->n_resident);
     d_req.ensure(ncap * 4 * 2 + (gt_D ? ncap * K * 4 : 0) + 64);
     float* dreq = d_req.as<float>();
     float* dtr = dreq + ncap;
@@ -4074,108 +3881,241 @@ static void adaptive_core_once(amd_ivf_t* h, const float* d_x, size_t start, siz
     flush_h2d(h, h->stream);
     host_stamp("inputs");
 
-    // How much of the coarse ranking can be consumed: set_online reads entries 0 .. nlist/8+20, and the probe loop ends at
-    // my_nprobe <= floor((nlist/8) * multipler) (IndexIVF.cpp:615-632) or at a value the caller passed in.  When that is
-    // well short of nlist only this prefix is ranked (launch_sort_rows).
-    size_t coarse_prefix = std::max<size_t>(nlist / 8 + 21, (size_t)((double)(nlist / 8) * (double)multipler) + 2);
-    for (size_t i = start; i < nabs; i++) coarse_prefix = std::max<size_t>(coarse_prefix, (size_t)my_nprobe[i] + 1);
-    coarse_prefix += 16;
+    // when what can be read of the coarse ranking is well short of nlist only this prefix is ranked (launch_sort_rows)
+    size_t coarse_prefix = coarse_read_bound(nlist, multipler, my_nprobe + start, n);
     if (coarse_prefix >= nlist || getenv("AUNCEL_AMD_FULL_COARSE_SORT")) coarse_prefix = 0;
 
-    const size_t nl = std::min(lane_count(n), std::max<size_t>(1, n / 64));
-    while (h->kids.size() + 1 < nl) {
-        std::unique_ptr<amd_ivf> kid(new amd_ivf);
-        kid->parent = ix(h);
-        kid->d = h->d;
-        kid->dpad = h->dpad;
-        kid->nlist = h->nlist;
-        kid->metric = h->metric;
-        kid->device = h->device;
-        kid->dist_budget_floats = h->dist_budget_floats;
-        kid->stream = make_main_stream();
-        h->kids.push_back(std::move(kid));
-    }
-    std::vector<amd_ivf*> lanes(nl);
-    lanes[0] = h;
-    for (size_t i = 1; i < nl; i++) lanes[i] = h->kids[i - 1].get();
-    for (size_t i = 1; i < nl; i++) {  // the slices' rows of a caller-supplied coarse ranking
-        const size_t q0 = n * i / nl;
-        lanes[i]->given_keys = h->given_keys ? h->given_keys + q0 * h->given_nprobe : nullptr;
-        lanes[i]->given_dis = h->given_keys ? h->given_dis + q0 * h->given_nprobe : nullptr;
-        lanes[i]->given_nprobe = h->given_nprobe;
-    }
-    for (amd_ivf* L : lanes) {
-        L->force_heap_select = h->force_heap_select;
-        reset_scan_counters(L);
-    }
-    // what this function reads back once the slices are done (one lane: queued together with the slice's own read-backs, or --
-    // a few queries -- with the look after the first round)
-    const std::function<void()> tail_gathers = [&]() {
-        d2h_small(h, my_nprobe + start, d_np.as<unsigned long long>() + start, n * 8, h->stream);
+    reset_scan_counters(h);
+    unsigned long long* const dnp = d_np.as<unsigned long long>();
+    // what is read back beside the results: queued with them behind the rounds, or -- a few queries -- with the look after the first
+    const auto tail_gathers = [&]() {
+        d2h_small(h, my_nprobe + start, dnp + start, n * 8, h->stream);
         d2h_small(h, t_recalls + start, dtr + start, n * 4, h->stream);
         if (h->want_first_tie) {
             h->first_tie_host.assign(n, 0);
             d2h_small(h, h->first_tie_host.data(), h->w_first_tie.p, n * 4, h->stream);
-            if (h->spec_valid && nl == 1) {
+            if (h->spec_valid) {
                 h->spec_slot_host.assign(n, -1);
                 d2h_small(h, h->spec_slot_host.data(), h->w_spec_slot.p, n * 4, h->stream);
                 h->tie_patched_host = 0;
                 if (h->spec_inline) d2h_small(h, &h->tie_patched_host, h->w_spec_count.as<uint32_t>() + 1, 4, h->stream);
-            } else {
-                h->spec_valid = false;
             }
         }
     };
     h->spec_done = false;
-    std::vector<std::exception_ptr> errs(nl);
-    auto run = [&](size_t i) {
-        const size_t q0 = n * i / nl, q1 = n * (i + 1) / nl;
-        try {
-            // (one lane: the slice's read-back joins this function's own, one synchronisation ends the call)
-            adaptive_slice(lanes[i], d_x + q0 * h->dpad, start + q0, q1 - q0, query_topk, multipler, std_m, dreq, dgt,
-                           d_np.as<unsigned long long>(), dtr, profile, coarse_mode, D + q0 * K, I + q0 * K, qr, coarse_prefix, nl == 1,
-                           nl == 1 ? &tail_gathers : nullptr);
-        } catch (...) {
-            errs[i] = std::current_exception();
-        }
-    };
     SmallCopies pending(h);  // (whatever is still queued when this scope is left by an exception names memory of this call)
-    std::vector<std::thread> th;
-    for (size_t i = 1; i < nl; i++) th.emplace_back(run, i);
-    run(0);
-    for (auto& t : th) t.join();
-    for (auto& e : errs)
-        if (e) std::rethrow_exception(e);
-    if (!(nl == 1 && h->spec_done)) {  // (else the look after the first round brought everything along)
+
+    // full coarse ranking (Error_sys::search sets nprobe = nlist, profile.cpp:220), or the caller's
+    const size_t np_row = coarse_or_given(h, d_x, n, coarse_mode, ix(h)->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric), coarse_prefix);
+    host_stamp("coarse");
+    // (at most four queries: the four small launches between the coarse ranking and the first round are made as one)
+    const bool fuse_small = n <= 4 && !h->spec_wanted;
+    if (h->want_first_tie) {
+        h->w_first_tie.ensure(n * 4);
+        // Which queries will have to be searched again is known only when this pass ends (first run < 2 my_nprobe + 14), but the
+        // expensive part of searching them again -- the reference's heap over all nlist centroids, a serial 4096-element heap
+        // sort per query -- needs nothing from this pass.  Every query that could qualify with the probes of the first two
+        // rounds gets its rows set aside now (the distance table lives in w_dist, which round 0 overwrites) and the heap runs on
+        // a side stream under this pass.
+        static const bool no_spec = getenv("AUNCEL_AMD_NO_TIE_SPECULATION") != nullptr;
+        // (slots for the rankings whose first run is in reach: 512 for calls of up to 5000 queries -- about 400 of the bench workload's
+        // 5000 rankings take one -- and an eighth of the call beyond, so that larger calls, e.g. queued tickets served together, do not
+        // send what overflows through the second pass)
+        const uint32_t SPEC_CAP = n <= 5120 ? 512u : (uint32_t)(((n / 8 + 63) / 64) * 64);
+        constexpr uint32_t SPEC_NEAR = 64, SPEC_WINDOW = 2 * (12 + 144) + 14;
+        h->spec_cap = SPEC_CAP;
+        h->spec_valid = false;
+        const bool can_spec = !no_spec && h->spec_wanted && !h->given_keys && np_row == nlist && n <= h->dist_budget_floats / std::max<size_t>(nlist, 1) &&
+                              heap_tie_order_lds((uint32_t)nlist, (uint32_t)nlist) <= 160 * 1024;
+        if (!can_spec && !fuse_small)
+            launch_first_tie(h->w_cdis.as<float>(), (uint32_t)n, (uint32_t)nlist, (uint32_t)h->first_tie_nreal, h->w_first_tie.as<uint32_t>(), h->stream);
+        if (can_spec) {
+            const size_t ncopy = std::min(h->first_tie_nreal, nlist);
+            h->w_spec_full.ensure((size_t)SPEC_CAP * nlist * 4);
+            h->w_spec_dis.ensure((size_t)SPEC_CAP * nlist * 4);
+            h->w_spec_keys.ensure((size_t)SPEC_CAP * nlist * 8);
+            h->w_spec_count.ensure(32);  // count | rankings the patch changed | rows the heap re-ranked (u64; not reported: most are never used) | scratch cursor (u64)
+            h->w_spec_slot.ensure(n * 4);
+            h->w_spec_query.ensure((size_t)SPEC_CAP * 4);
+            ensure_context_streams(h);
+            HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_spec_done, 0));  // (the previous search's slots are no longer being written)
+            HIP_CHECK(hipMemsetAsync(h->w_spec_count.p, 0, 32, h->stream));
+            // (the first run of every ranking and the slots of the rankings to re-rank in one launch: the heap starts right behind the
+            // coarse ranking; slots go to the waves in the order they arrive -- a ranking that finds none is searched again at the end)
+            (void)SPEC_NEAR;
+            launch_tie_collect(h->w_cdis.as<float>(), (uint32_t)n, (uint32_t)h->first_tie_nreal, SPEC_WINDOW, SPEC_CAP, (uint32_t)nlist, (uint32_t)ncopy,
+                               h->w_dist.as<float>(), h->w_ckeys.as<int64_t>(), h->w_first_tie.as<uint32_t>(), h->w_spec_count.as<uint32_t>(),
+                               h->w_spec_slot.as<int32_t>(), h->w_spec_full.as<float>(), h->w_spec_dis.as<float>(), h->w_spec_keys.as<int64_t>(),
+                               h->w_spec_query.as<uint32_t>(), h->stream);
+            HIP_CHECK(hipEventRecord(h->ev_spec_go, h->stream));
+            HIP_CHECK(hipStreamWaitEvent(h->spec_stream, h->ev_spec_go, 0));
+            launch_heap_tie_order(h->w_spec_full.as<float>(), SPEC_CAP, (uint32_t)nlist, (uint32_t)nlist, (uint32_t)ncopy, h->metric,
+                                  h->w_spec_dis.as<float>(), h->w_spec_keys.as<int64_t>(),
+                                  reinterpret_cast<unsigned long long*>(h->w_spec_count.as<uint32_t>() + 2), h->spec_stream,
+                                  h->w_spec_count.as<uint32_t>());
+            HIP_CHECK(hipEventRecord(h->ev_spec_done, h->spec_stream));
+            h->spec_valid = true;
+            h->spec_ncopy = ncopy;
+            // The heap's order can be applied to THIS pass when it arrives before anything has read the order inside a run of equal
+            // distances: that is the selection of round 0 (the stop rule's boundary distances and the probe order; the planner
+            // takes whole runs into a round, so the scan does not depend on it).  With the level-parallel filling and the pipelined
+            // heap sort (nlist a power of two) the heap takes ~1.5 ms a row, about what coarse ranking -> planning -> scan of
+            // round 0 take among other searches; the literal heap (12 ms a row) stays under the pass and feeds a second one.
+            static const bool no_patch = getenv("AUNCEL_AMD_NO_TIE_PATCH") != nullptr;
+            h->spec_inline = !no_patch && (nlist & (nlist - 1)) == 0 && nlist >= 64;
+        }
+    }
+    const bool tie_inline = h->want_first_tie && h->spec_valid && h->spec_inline;
+    struct FuseScope {  // (init_state and byte_queries record their launches while this is alive)
+        amd_ivf* h;
+        bool on;
+        FuseScope(amd_ivf* hh, bool o) : h(hh), on(o) {
+            if (on) {
+                h->fuse = amd_ivf::SmallFuse{};
+                h->fuse.active = true;
+            }
+        }
+        ~FuseScope() { h->fuse.active = false; }
+    } fuse_scope(h, fuse_small);
+    init_state(h, n, K, true);
+    auto set_online = [h, nlist, n, np_row](const uint32_t* only = nullptr, const uint32_t* only_count = nullptr, uint32_t cap = 0) {
+        launch_set_online(h->metric, (uint32_t)nlist, only ? cap : (uint32_t)n, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(), (uint32_t)np_row,
+                          ix(h)->d_interdis.as<float>(), ix(h)->d_arcos.as<float>(), h->w_dtb.as<float>(), h->w_error.as<uint32_t>(), h->stream,
+                          only, only_count);
+    };
+    if (!fuse_small && !tie_inline) set_online();
+    RoundSpec base;
+    if (tie_inline) {
+        // room for the rows the patch moves: a round's rows of every slot if that is not beyond reason (a query that finds no room is
+        // searched again)
+        size_t maxlist = 0;
+        for (size_t l = 0; l < nlist; l++) maxlist = std::max<size_t>(maxlist, ix(h)->h_list_off[l + 1] - ix(h)->h_list_off[l]);
+        const size_t SCRATCH_FLOATS = std::min<size_t>((size_t)64 << 20, std::max<size_t>((size_t)8 << 20, (size_t)h->spec_cap * 16 * ((maxlist + 1023) & ~(size_t)1023)));
+        h->w_spec_scratch.ensure(SCRATCH_FLOATS * 4);
+        base.run_ties = true;
+        base.before_first_select = [h, nlist, set_online, SCRATCH_FLOATS]() {
+            HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_spec_done, 0));
+            TiePatchArgs ta{};
+            ta.count = h->w_spec_count.as<uint32_t>();
+            ta.cap = h->spec_cap;
+            ta.nlist = (uint32_t)nlist;
+            ta.ncopy = (uint32_t)h->spec_ncopy;
+            ta.key_stride = (uint32_t)nlist;
+            ta.slot_query = h->w_spec_query.as<uint32_t>();
+            ta.slot_of = h->w_spec_slot.as<int32_t>();
+            ta.s_keys = h->w_spec_keys.as<int64_t>();
+            ta.ckeys = h->w_ckeys.as<int64_t>();
+            ta.seg_count = h->w_pl_cnt.as<uint32_t>();
+            ta.seg_begin = h->w_seg_begin.as<uint32_t>();
+            ta.seg_list = h->w_seg_list.as<int32_t>();
+            ta.seg_off = h->w_seg_off.as<uint64_t>();
+            ta.list_off = ix(h)->d_list_off.as<uint64_t>();
+            ta.dist = h->w_dist.as<float>();
+            ta.row_align = h->row_align_now;
+            ta.scratch = h->w_spec_scratch.as<float>();
+            ta.scratch_floats = SCRATCH_FLOATS;
+            ta.cursor = reinterpret_cast<unsigned long long*>(h->w_spec_count.as<uint32_t>() + 4);
+            ta.patched = h->w_spec_count.as<uint32_t>() + 1;
+            launch_tie_patch(ta, h->stream);
+            set_online();
+        };
+        // the first selection in two launches (chained rounds; AUNCEL_AMD_NO_SPLIT_SELECT: in one, behind the heap)
+        static const bool no_split = getenv("AUNCEL_AMD_NO_SPLIT_SELECT") != nullptr;
+        if (!no_split && n >= 256) {
+            h->w_split.ensure((2 * n + 8) * 4);
+            uint32_t* counts = h->w_split.as<uint32_t>();
+            uint32_t* q_free = counts + 8;
+            uint32_t* q_wait = q_free + n;
+            const auto patch_hook = base.before_first_select;
+            const uint32_t wait_cap = (uint32_t)std::min<size_t>(n, h->spec_cap);  // (tie_collect_kernel hands out at most that many slots)
+            base.split_free = q_free;
+            base.split_wait = q_wait;
+            base.split_counts = counts;
+            base.split_wait_cap = wait_cap;
+            base.split_prepare = [h, n, counts, q_free, q_wait, set_online]() {
+                HIP_CHECK(hipMemsetAsync(counts, 0, 8, h->stream));
+                // (round 0 of an adaptive search: every query of the call is active, in order)
+                launch_partition_qsel(nullptr, nullptr, (uint32_t)n, h->w_spec_slot.as<int32_t>(), q_free, q_wait, counts, h->stream);
+                set_online();
+            };
+            base.split_between = [h, patch_hook, counts, q_wait, wait_cap, set_online]() {
+                (void)set_online;
+                patch_hook();  // (waits for the heap, patches, and derives the boundary distances again -- of every query: the patched
+                               // rankings are a tenth of them and the launch is 0.045 ms)
+            };
+        }
+    }
+    base.fused = ix(h)->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
+    base.bytes = byte_queries(h, ix(h), d_x, n, qr);
+    if (fuse_small) {
+        h->fuse.active = false;
+        SmallStateArgs sa{};
+        sa.init = h->fuse.init;
+        sa.metric = h->metric;
+        sa.nlist = (uint32_t)nlist;
+        sa.nq = (uint32_t)n;
+        sa.coarse_dis = h->w_cdis.as<float>();
+        sa.coarse_keys = h->w_ckeys.as<int64_t>();
+        sa.coarse_stride = (uint32_t)np_row;
+        sa.interdis = ix(h)->d_interdis.as<float>();
+        sa.arcos = ix(h)->d_arcos.as<float>();
+        sa.dtb = h->w_dtb.as<float>();
+        if (h->want_first_tie) {
+            sa.ft_sorted_dis = h->w_cdis.as<float>();
+            sa.ft_stride = (uint32_t)nlist;
+            sa.ft_nreal = (uint32_t)h->first_tie_nreal;
+            sa.ft_out = h->w_first_tie.as<uint32_t>();
+        }
+        if (h->fuse.have_bytes) {
+            sa.bx = h->fuse.bx;
+            sa.bout = h->fuse.bout;
+            sa.bcx = h->fuse.bcx;
+        }
+        sa.d = h->d;
+        sa.dpad = h->dpad;
+        launch_small_state(sa, h->stream);
+    }
+    ix(h)->last_arith = base.bytes ? 2 : base.fused ? 1 : 0;
+    base.k = (int)K;
+    base.id_offset = start;
+    base.d_x = d_x;
+    base.d_cdis = h->w_cdis.as<float>();
+    base.d_ckeys = h->w_ckeys.as<int64_t>();
+    base.coarse_stride = (uint32_t)np_row;
+    base.tuner = make_tuner(h, query_topk, multipler, std_m, dreq, dgt, dnp, dtr, profile);
+    // (one query per call: a first round of 64 probes instead of 12 ends 95 % of the bench workload's queries in it instead of 73 %,
+    // and moved neither the median nor the p90 of the call -- 0.25 / 0.56 ms: the slow tenth are not the queries that need a second
+    // round but the ones in which equal distances met, whose result is the reference's heap replayed over ~500 admissions, 0.3 ms on
+    // one wave; profiles/r05_latency_batch1.txt)
+    const size_t first_env = std::max<size_t>(1, (size_t)opt(h, OPT_ROUND_FIRST, 12));
+    base.caller_checks_error = true;
+    DirectOut direct(h, D, I);
+    host_stamp("state");
+    if (n < 20)  // (a few queries: the read-backs may ride with the first look)
+        base.spec_finish = [&]() {
+            finish_results(h, n, K, D, I, nullptr, true);
+            tail_gathers();
+        };
+    run_rounds_device(h, base, n, first_env, np_row, dnp);
+    host_stamp("rounds");
+    if (!h->spec_done) {  // (else the look after the first round brought everything along)
+        finish_results(h, n, K, D, I, nullptr, true);
         tail_gathers();
         sync_and_flush(h, h->stream);
     }
     h->spec_done = false;
     host_stamp("final-sync");
-    // fold the kids' counters and kernel timings into the handle
     const double wall = wc.stop();
     host_stamp("clock");
     print_stamps();
-    double ms[NCAT] = {0}, ln[NCAT] = {0};
-    double bytes = 0, slots = 0, useful = 0, min_bytes = 0;
-    for (amd_ivf* L : lanes) {
-        double m[NCAT], c[NCAT];
-        L->timer.collect(m, NCAT, c);
-        for (int k = 0; k < NCAT; k++) ms[k] += m[k], ln[k] += c[k];
-        bytes += L->scan_bytes;
-        min_bytes += L->scan_min_bytes;
-        slots += L->scan_slots;
-        useful += L->scan_useful;
-        if (L != h) {
-            for (int k = 0; k < 4; k++) h->stats_host[k] += L->stats_host[k], L->stats_host[k] = 0;
-        }
-    }
+    double ms[NCAT], ln[NCAT];
+    h->timer.collect(ms, NCAT, ln);
     fill_timing(h, ms, ln);
     h->timer.off = false;
     h->timing[3] = wall;
-    h->timing[5] = bytes;
-    h->last_min_bytes = min_bytes;
-    h->timing[6] = slots > 0 ? useful / slots : 0;
+    h->timing[5] = h->scan_bytes;
+    h->last_min_bytes = h->scan_min_bytes;
+    h->timing[6] = h->scan_slots > 0 ? h->scan_useful / h->scan_slots : 0;
 }
 
 // A call of n >= 20 queries with the reference's exact-distance tie order: the whole call is searched with runs of equal
@@ -4188,18 +4128,8 @@ static void adaptive_redo_ties(amd_ivf_t* h, const float* d_x, size_t start, siz
     const size_t K = ix(h)->tuner_max_topk, nlist = h->nlist;
     const std::vector<uint64_t> np0(my_nprobe + start, my_nprobe + start + n);
     const std::vector<float> tr0(t_recalls + start, t_recalls + start + n);
-    size_t nreal = std::max<size_t>(nlist / 8 + 21, (size_t)((double)(nlist / 8) * (double)multipler) + 2);
-    for (size_t i = 0; i < n; i++) nreal = std::max<size_t>(nreal, (size_t)np0[i] + 1);
-    nreal = std::min(nreal + 16, nlist);
-    struct Restore {
-        amd_ivf_t* h;
-        ~Restore() {
-            h->ties_override = -1;
-            h->want_first_tie = false;
-            h->spec_use = false;
-            h->spec_wanted = false;
-        }
-    } restore{h};
+    const size_t nreal = std::min(coarse_read_bound(nlist, multipler, np0.data(), n), nlist);
+    TieRegime regime(h);
     h->ties_override = 0;
     h->want_first_tie = true;
     h->first_tie_nreal = nreal;
@@ -4293,7 +4223,7 @@ static void adaptive_core(amd_ivf_t* h, const float* d_x, size_t start, size_t n
                           const float* require_acc, const float* gt_D, int profile, int coarse_mode,
                           uint64_t* my_nprobe, float* t_recalls, float* D, int64_t* I, const IntRange& qr) {
     const int ties_opt = (int)opt(h, OPT_COARSE_TIES, -1);
-    const bool can_speculate = !h->given_keys && n > 0 && h->nlist > 128 && multipler >= 1.f && !(profile & 2) && h->kids.empty();
+    const bool can_speculate = !h->given_keys && n > 0 && h->nlist > 128 && multipler >= 1.f && !(profile & 2);
     const bool speculate = can_speculate && n < 20 && ties_opt < 0;
     // larger calls: "redo" searches again, with the heap's order, exactly the queries whose first run of equal coarse distances
     // lies within what they read (a handful in thousands) -- the reference's exact-distance result for every query of the call
@@ -4312,21 +4242,12 @@ static void adaptive_core(amd_ivf_t* h, const float* d_x, size_t start, size_t n
     const std::vector<float> tr0(t_recalls + start, t_recalls + start + n);
     // the start of the first run of equal distances in every ranking of the call comes back with the results
     // (first_tie_kernel right behind the coarse ranking, over what adaptive_core_once ranks: its coarse_prefix)
-    const size_t nlist = h->nlist;
-    size_t nreal = std::max<size_t>(nlist / 8 + 21, (size_t)((double)(nlist / 8) * (double)multipler) + 2);
-    for (size_t i = 0; i < n; i++) nreal = std::max<size_t>(nreal, (size_t)np0[i] + 1);
-    nreal = std::min(nreal + 16, nlist);
+    const size_t nreal = std::min(coarse_read_bound(h->nlist, multipler, np0.data(), n), h->nlist);
+    TieRegime regime(h);
     h->ties_override = 0;
     h->want_first_tie = true;
     h->first_tie_nreal = nreal;
-    try {
-        with_select_fallback(h, [&] { adaptive_core_once(h, d_x, start, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, D, I, qr); });
-    } catch (...) {
-        h->ties_override = -1;
-        h->want_first_tie = false;
-        throw;
-    }
-    h->ties_override = -1;
+    with_select_fallback(h, [&] { adaptive_core_once(h, d_x, start, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, D, I, qr); });
     h->want_first_tie = false;
     const std::vector<uint32_t>& first = h->first_tie_host;
     bool redo = false;
@@ -4339,13 +4260,7 @@ static void adaptive_core(amd_ivf_t* h, const float* d_x, size_t start, size_t n
     std::copy(np0.begin(), np0.end(), my_nprobe + start);
     std::copy(tr0.begin(), tr0.end(), t_recalls + start);
     h->ties_override = 1;
-    try {
-        with_select_fallback(h, [&] { adaptive_core_once(h, d_x, start, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, D, I, qr); });
-    } catch (...) {
-        h->ties_override = -1;
-        throw;
-    }
-    h->ties_override = -1;
+    with_select_fallback(h, [&] { adaptive_core_once(h, d_x, start, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, D, I, qr); });
 }
 
 int amd_ivf_search_adaptive(amd_ivf_t* h, size_t start, size_t n, size_t query_topk, float multipler, float std_m,
@@ -4353,11 +4268,9 @@ int amd_ivf_search_adaptive(amd_ivf_t* h, size_t start, size_t n, size_t query_t
                             uint64_t* my_nprobe, float* t_recalls, float* D, int64_t* I) {
     API_BEGIN
     use_device(h);
-    // a search context that was never given resident queries of its own searches its owner's (amd_ivf_submit_adaptive's contexts)
-    const amd_ivf* src = h->is_clone && h->n_resident == 0 && h->parent ? h->parent : h;
-    if (start + n > src->n_resident) throw EngineError("resident query range out of bounds");
-    adaptive_core(h, src->d_resident.as<float>() + start * h->dpad, start, n, query_topk, multipler, std_m, require_acc, gt_D,
-                  profile, coarse_mode, my_nprobe, t_recalls, D, I, src->resident_range);
+    const QueryRows q = resident_rows(h, start, n);
+    adaptive_core(h, q.d_x, start, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, D, I,
+                  q.range);
     API_END
 }
 
@@ -4367,12 +4280,9 @@ int amd_ivf_search_adaptive_x(amd_ivf_t* h, size_t n, const float* x, size_t id_
     API_BEGIN
     use_device(h);
     if (n == 0) return 0;
-    h->w_x.ensure(n * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
-    adaptive_core(h, h->w_x.as<float>(), id_offset, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode,
-                  my_nprobe, t_recalls, D, I, qr);
+    const QueryRows q = host_rows(h, x, n);
+    adaptive_core(h, q.d_x, id_offset, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, D, I,
+                  q.range);
     API_END
 }
 
@@ -4398,13 +4308,9 @@ int amd_ivf_search_adaptive_pre(amd_ivf_t* h, size_t n, const float* x, size_t i
     API_BEGIN
     use_device(h);
     if (n == 0) return 0;
-    h->w_x.ensure(n * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
+    const QueryRows q = host_rows(h, x, n);
     GivenCoarse given(h, nprobe, keys, coarse_dis);
-    adaptive_core(h, h->w_x.as<float>(), id_offset, n, query_topk, multipler, std_m, require_acc, gt_D, profile, 0, my_nprobe, t_recalls,
-                  D, I, qr);
+    adaptive_core(h, q.d_x, id_offset, n, query_topk, multipler, std_m, require_acc, gt_D, profile, 0, my_nprobe, t_recalls, D, I, q.range);
     API_END
 }
 
@@ -4438,8 +4344,8 @@ static void train_core(amd_ivf_t* h, const float* d_x, size_t start, size_t n, s
         h->d_arcos.ensure(500 * 4);
         HIP_CHECK(hipMemcpy(h->d_arcos.p, lut.data(), 500 * 4, hipMemcpyHostToDevice));
     }
-    // training stops after stage nlist/8 + 1 (IndexIVF.cpp:640-673); set_online reads entries 0 .. nlist/8+20
-    size_t coarse_prefix = nlist / 8 + 21 + 16;
+    // training stops after stage nlist/8 + 1 (IndexIVF.cpp:640-673): what set_online reads, no multipler and no my_nprobe beyond it
+    size_t coarse_prefix = coarse_read_bound(nlist, 0.f, nullptr, 0);
     if (coarse_prefix >= nlist || getenv("AUNCEL_AMD_FULL_COARSE_SORT")) coarse_prefix = 0;
     const size_t np_row = coarse_or_given(h, d_x, n, coarse_mode, h->allow_fused && h->centroid_range.fusable_with(qr, h->metric), coarse_prefix);
     init_state(h, n, K, true);
@@ -4488,11 +4394,8 @@ int amd_ivf_train_samples_x(amd_ivf_t* h, size_t n, const float* x, size_t id_of
     OWNER_ONLY(h);
     use_device(h);
     if (n == 0) return 0;
-    h->w_x.ensure(n * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
-    train_core(h, h->w_x.as<float>(), id_offset, n, max_topk, gt_D, train_num, coarse_mode, raw, D, I, qr);
+    const QueryRows q = host_rows(h, x, n);
+    train_core(h, q.d_x, id_offset, n, max_topk, gt_D, train_num, coarse_mode, raw, D, I, q.range);
     API_END
 }
 
@@ -4503,12 +4406,9 @@ int amd_ivf_train_samples_pre(amd_ivf_t* h, size_t n, const float* x, size_t id_
     OWNER_ONLY(h);
     use_device(h);
     if (n == 0) return 0;
-    h->w_x.ensure(n * h->dpad * sizeof(float));
-    upload_rows(h, h->w_x.as<float>(), x, n);
-    IntRange qr;
-    qr.add(x, n * (size_t)h->d);
+    const QueryRows q = host_rows(h, x, n);
     GivenCoarse given(h, nprobe, keys, coarse_dis);
-    train_core(h, h->w_x.as<float>(), id_offset, n, max_topk, gt_D, train_num, 0, raw, D, I, qr);
+    train_core(h, q.d_x, id_offset, n, max_topk, gt_D, train_num, 0, raw, D, I, q.range);
     API_END
 }
 
@@ -4778,10 +4678,6 @@ int amd_ivf_last_scan_min_bytes(amd_ivf_t* h, double* bytes) {
 int amd_ivf_last_round_hints(amd_ivf_t* h, uint64_t out[2]) {
     out[0] = h->hinted_rounds;
     out[1] = h->short_rounds;
-    for (auto& kid : h->kids) {
-        out[0] += kid->hinted_rounds;
-        out[1] += kid->short_rounds;
-    }
     return 0;
 }
 
@@ -4799,15 +4695,12 @@ int amd_ivf_last_tie_fixed(amd_ivf_t* h, uint64_t* queries) {
     API_BEGIN
     use_device(h);
     *queries = 0;
-    auto add = [&](amd_ivf* c) {
-        if (!c->w_tie_flag.p || !c->last_state_n) return;
-        std::vector<uint32_t> f(c->last_state_n);
-        HIP_CHECK(stream_sync(c->stream));
-        HIP_CHECK(hipMemcpy(f.data(), c->w_tie_flag.p, f.size() * 4, hipMemcpyDeviceToHost));
+    if (h->w_tie_flag.p && h->last_state_n) {
+        std::vector<uint32_t> f(h->last_state_n);
+        HIP_CHECK(stream_sync(h->stream));
+        HIP_CHECK(hipMemcpy(f.data(), h->w_tie_flag.p, f.size() * 4, hipMemcpyDeviceToHost));
         for (uint32_t v : f) *queries += v == 2;
-    };
-    add(h);
-    for (auto& kid : h->kids) add(kid.get());
+    }
     API_END
 }
 int amd_ivf_last_direct_out(amd_ivf_t* h) { return h ? h->last_direct_out : 0; }
@@ -4831,17 +4724,13 @@ int amd_ivf_last_filter(amd_ivf_t* h, uint64_t out[2]) {
 int amd_ivf_coarse_tie_rows(amd_ivf_t* h, uint64_t* rows) {
     API_BEGIN
     use_device(h);
-    *rows = 0;
-    auto add = [&](amd_ivf* c) {
-        *rows += c->tie_rows_host;
-        if (!c->w_tie_rows.p) return;
+    *rows = h->tie_rows_host;
+    if (h->w_tie_rows.p) {
         uint64_t v = 0;
-        HIP_CHECK(stream_sync(c->stream));
-        HIP_CHECK(hipMemcpy(&v, c->w_tie_rows.p, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(stream_sync(h->stream));
+        HIP_CHECK(hipMemcpy(&v, h->w_tie_rows.p, 8, hipMemcpyDeviceToHost));
         *rows += v;
-    };
-    add(h);
-    for (auto& kid : h->kids) add(kid.get());  // the slices of an adaptive batch run on these
+    }
     API_END
 }
 

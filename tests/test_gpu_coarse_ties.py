@@ -194,3 +194,87 @@ def test_tie_order_applied_to_the_pass_under_way(capi, oracle, monkeypatch, seed
         nreal = min(max(nlist // 8 + 21, int((nlist // 8) * mult) + 2) + 16, nlist)
         deep = int((2 * tun.my_nprobe.astype(np.int64) + 14 + 1 >= nreal).sum())
         assert h.last_tie_redone() <= max(0, nq - 512) + deep
+
+
+# (nq -> seed) of test_failed_call_leaves_the_tie_regime_clean, picked with the oracle alone: the reference does not throw its
+# cosine_theorem precondition on these draws, a query of the 5 reads into its first run of equal distances (the small call is
+# repeated with the heap's order) and a query of the 60 reads to the end of what the first pass ranks (it is searched again)
+TIE_REGIME_SEEDS = {5: 2, 60: 3}
+_tie_regime_cases = {}
+
+
+def tie_regime_case(oracle, arcos, nq, seed):
+    """the data recipe of test_adaptive_search_with_coarse_ties at nlist 256, K 10 (the smallest shape at which the engine has all
+    three regimes: speculation needs nlist > 128, the patch of the pass under way a power of two), and the reference's result"""
+    rs = np.random.RandomState(8000 + seed)
+    nlist, d, K, nb = 256, 16, 10, 20000
+    xb, xq = grid_points(rs, nb, d, 12), grid_points(rs, nq, d, 12)
+    cen = xb[rs.choice(nb, nlist, replace=False)].copy()
+    traces = []
+    for _ in range(6):  # 2^5 <= nlist / 8 < 2^6
+        n = int(rs.randint(3, 60))
+        x = np.sort(rs.rand(n) * 25.0).astype(np.float32)
+        x += np.arange(n, dtype=np.float32) * 1e-3
+        traces.append((x, (0.5 + rs.rand(n) * 2.5).astype(np.float32), (rs.rand(n) * 0.5).astype(np.float32)))
+    qk = int(rs.choice([1, 10]))
+    req = rs.choice([0.8, 0.9, 0.95, 0.99], size=nq).astype(np.float32)
+    mult, sm = float(rs.choice([1.0, 2.0])), float(rs.choice([0.0, 1.0]))
+    _, a = oracle.knn(1, xb, cen, 1, nthreads=8)
+    assign = a[:, 0]
+    cd, ck = oracle.knn(1, xq, cen, nlist, nthreads=8)
+    gtD, _ = oracle.knn(1, xq, xb, K, nthreads=8)
+    tun = oracle.Tuner(oracle.interdis(1, cen), traces, K, nq, arcos=arcos)
+    stt = tun.struct(qk, req, mult, sm, gt_D=gtD, profile=False)
+    eD, eI, est = oracle.search_preassigned(oracle.Lists(1, cen, xb, assign), xq, K, ck, cd, tuner=stt, offset=0, nthreads=1)
+    return dict(nlist=nlist, d=d, K=K, nq=nq, xb=xb, xq=xq, cen=cen, traces=traces, qk=qk, req=req, mult=mult, sm=sm, assign=assign,
+                cd=cd, gtD=gtD, eD=eD, eI=eI, est=list(est), my_nprobe=tun.my_nprobe.astype(np.int64).copy())
+
+
+@pytest.mark.parametrize("entry", ["resident", "host"])
+@pytest.mark.parametrize("nq,ties", [(5, "auto"), (60, "redo"), (60, "heap")])
+def test_failed_call_leaves_the_tie_regime_clean(capi, oracle, monkeypatch, nq, ties, entry):
+    """a call that the engine refuses inside its adaptive search (query_topk beyond the tuner's max_topk), under each of the three
+    tie-order regimes and from both kinds of query rows, leaves nothing of the regime on the handle: the next, valid call on the
+    same handle returns the reference's result bit for bit"""
+    import ctypes as C
+    monkeypatch.setenv("AUNCEL_AMD_COARSE_TIES", ties)
+    arcos = capi.arcos_table()
+    if nq not in _tie_regime_cases:
+        _tie_regime_cases[nq] = tie_regime_case(oracle, arcos, nq, TIE_REGIME_SEEDS[nq])
+    c = _tie_regime_cases[nq]
+    K = c["K"]
+    h = capi.Handle(c["d"], c["nlist"], 1, 0)
+    h.set_centroids(c["cen"])
+    h.set_lists_from_assign(c["xb"], c["assign"])
+    h.set_interdis(None)
+    h.set_tuner(K, c["traces"], arcos)
+    if entry == "resident":
+        h.set_queries(c["xq"])
+
+    def search(query_topk):
+        my_np = np.zeros(nq, dtype=np.uint64)
+        t_rec = np.zeros(nq, dtype=np.float32)
+        if entry == "resident":
+            D, I = h.search_adaptive(0, nq, query_topk, c["mult"], c["sm"], c["req"], my_np, t_rec, gt_D=c["gtD"], profile=False)
+        else:
+            D, I = np.empty((nq, K), np.float32), np.empty((nq, K), np.int64)
+            f32p, u64p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
+            rc = capi.lib().amd_ivf_search_adaptive_x(
+                h._h, C.c_size_t(nq), c["xq"].ctypes.data_as(f32p), C.c_size_t(0), C.c_size_t(query_topk), C.c_float(c["mult"]),
+                C.c_float(c["sm"]), c["req"].ctypes.data_as(f32p), c["gtD"].ctypes.data_as(f32p), 0, 0, my_np.ctypes.data_as(u64p),
+                t_rec.ctypes.data_as(f32p), D.ctypes.data_as(f32p), I.ctypes.data_as(i64p))
+            if rc != 0:
+                raise capi.EngineError(rc, capi.lib().amd_ivf_last_error().decode())
+        return D, I, my_np
+
+    with pytest.raises(capi.EngineError, match="query_topk out of range"):
+        search(K + 1)
+    h.stats(reset=True)
+    D, I, my_np = search(c["qk"])
+    assert np.array_equal(my_np.astype(np.int64), c["my_nprobe"])
+    assert np.array_equal(I, c["eI"])
+    assert np.array_equal(bits(D), bits(c["eD"]))
+    st = h.stats()
+    assert [st["nlist"], st["ndis"], st["nheap_updates"]] == c["est"]
+    assert st["nq"] == nq
+    assert h.coarse_tie_rows() > 0
