@@ -33,6 +33,8 @@ SYMBOLS = [
     "amd_ivf_scan_arith",
     "amd_ivf_update_lists", "amd_ivf_remove_ids", "amd_ivf_last_update", "amd_ivf_layout_digest",
     "amd_ivf_subset", "amd_ivf_last_subset",
+    "amd_ivf_selector_create", "amd_ivf_selector_destroy", "amd_ivf_selector_info",
+    "amd_ivf_search_selected", "amd_ivf_search_preassigned_selected", "amd_ivf_search_resident_selected",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -219,6 +221,43 @@ def arcos_table():
     return out
 
 
+class Selector:
+    """thin owner of an amd_ivf_selector_t*: the keep bits of one id selector over one index (the arguments of Handle.subset).  It
+    keeps its index's Handle alive and is closed before it; `with handle.selector(...) as s:` closes it on the way out."""
+
+    def __init__(self, handle, kind, a1=0, a2=0, sel=None):
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.uint64 if kind == SUBSET_ID_BITS else np.int64)
+        self._s = C.c_void_p()
+        self._index = handle
+        _chk(lib().amd_ivf_selector_create(handle._h, int(kind), C.c_int64(int(a1)), C.c_int64(int(a2)),
+                                           sel.ctypes.data_as(C.c_void_p) if sel is not None else None,
+                                           C.c_size_t(0 if sel is None else sel.shape[0]), C.byref(self._s)))
+
+    def info(self):
+        """(entries looked at, entries kept, host-to-device bytes, device bytes held)"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_selector_info(self._s, out))
+        return tuple(int(v) for v in out)
+
+    def close(self):
+        if self._s:
+            lib().amd_ivf_selector_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Handle:
     """thin owner of an amd_ivf_t*"""
 
@@ -242,7 +281,9 @@ class Handle:
 
     def close(self):
         if self._h:
-            lib().amd_ivf_destroy(self._h)
+            rc = lib().amd_ivf_destroy(self._h)
+            if rc == -2:  # (refused: selectors made on the index are still alive -- the handle stays valid)
+                raise EngineError(rc, lib().amd_ivf_last_error().decode())
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -351,6 +392,36 @@ class Handle:
         out = (C.c_uint64 * 4)()
         _chk(lib().amd_ivf_last_subset(self._h, out))
         return tuple(int(v) for v in out)
+
+    # ---- search under an id selector (include/auncel_amd.h: amd_ivf_selector_create)
+    def selector(self, kind, a1=0, a2=0, sel=None):
+        """a Selector over this index's lists as they are now: the arguments of subset()"""
+        return Selector(self, kind, a1, a2, sel)
+
+    def search_selected(self, selector, x, k, nprobe, coarse_mode=0):
+        x = f32(x)
+        n = x.shape[0]
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_selected(self._h, selector._s, C.c_size_t(n), _f(x), C.c_size_t(k), C.c_size_t(nprobe), coarse_mode, _f(D), _i(I)))
+        return D, I
+
+    def search_preassigned_selected(self, selector, x, k, keys, coarse_dis=None):
+        x, keys = f32(x), i64(keys)
+        n, nprobe = keys.shape
+        cd = f32(coarse_dis) if coarse_dis is not None else None
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_preassigned_selected(self._h, selector._s, C.c_size_t(n), _f(x), C.c_size_t(k), C.c_size_t(nprobe), _i(keys),
+                                                       _f(cd), _f(D), _i(I)))
+        return D, I
+
+    def search_resident_selected(self, selector, start, n, k, nprobe, coarse_mode=0):
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_resident_selected(self._h, selector._s, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k), C.c_size_t(nprobe),
+                                                    coarse_mode, _f(D), _i(I)))
+        return D, I
 
     # ---- search
     def coarse(self, x, nprobe, mode=0):

@@ -1,8 +1,11 @@
 // faiss::IndexIVFFlat (Auncel/IndexIVFFlat.h:25-58)
 #pragma once
 #include <unordered_map>
+#include <vector>
 
 #include "IndexIVF.h"
+
+struct amd_ivf_selector;
 
 namespace faiss {
 
@@ -17,6 +20,27 @@ struct IndexIVFFlat : IndexIVF {
     /// IndexIVFFlat.cpp:190-224: vectors with ids new_ids[i] (< ntotal, direct map on) replaced by x[i]: the old entry leaves its
     /// list (the list's last entry takes its place), the new one is appended to the list of its nearest centroid
     virtual void update_vectors(int nv, idx_t* new_ids, const float* x);
+
+    /// search() over the members of `sel` only, on the lists that are resident on the device (include/auncel_amd.h:
+    /// amd_ivf_search_selected): the (distances, labels) an IndexIVFFlatSubset of the same selector returns, without the second index
+    /// -- the selector becomes one bit per stored entry.  An IDSelectorRange or an IDSelectorBatch; any other selector is "not
+    /// implemented".  The bits are made by one pass over the resident ids and kept while the lists (invlists->version) and the
+    /// selector's parameters repeat: selector_passes counts the passes made, selected_info() describes the one that is kept.
+    /// Fixed nprobe, the plain search only (not tune / training / time_tune, no max_codes); not for an IndexIVFFlatDedup.
+    void search_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const IDSelector& sel) const;
+    mutable size_t selector_passes = 0;
+    /// {entries looked at, entries kept, host-to-device bytes, device bytes held} of the kept selector (zeros: none)
+    void selected_info(uint64_t out[4]) const;
+    IndexIVFFlat(const IndexIVFFlat&) = delete;
+    IndexIVFFlat& operator=(const IndexIVFFlat&) = delete;
+    ~IndexIVFFlat() override;
+
+   private:
+    mutable amd_ivf_selector* sel_ = nullptr;  // the kept selector, and what it was made from
+    mutable size_t sel_version_ = 0;
+    mutable int sel_kind_ = -1;
+    mutable idx_t sel_a1_ = 0, sel_a2_ = 0;
+    mutable std::vector<int64_t> sel_ids_;
 };
 
 /// faiss::IndexIVFFlatDedup (Auncel/IndexIVFFlat.h:62-107): equal vectors are stored once; `instances` maps the id that

@@ -1274,6 +1274,50 @@ void IndexIVF::copy_subset_to(IndexIVF& other, int subset_type, idx_t a1, idx_t 
     FAISS_THROW_IF_NOT(seen == (size_t)ntotal);
 }
 
+// ------------------------------------------------------------------------------------- IndexIVFFlat::search_selected
+IndexIVFFlat::~IndexIVFFlat() {
+    if (sel_) amd_ivf_selector_destroy(sel_);  // (before ~IndexIVF destroys the engine it was made on)
+}
+
+void IndexIVFFlat::selected_info(uint64_t out[4]) const {
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (sel_) AMD(amd_ivf_selector_info(sel_, out));
+}
+
+void IndexIVFFlat::search_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const IDSelector& sel) const {
+    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(this) == nullptr, "search_selected of an IndexIVFFlatDedup is not implemented");
+    FAISS_THROW_IF_NOT_MSG(!tune && !training && !(t && t->time_tune), "search_selected is the plain fixed-nprobe search only");
+    FAISS_THROW_IF_NOT_MSG(max_codes == 0, "search_selected with max_codes is not implemented");
+    int kind;
+    idx_t a1 = 0, a2 = 0;
+    std::vector<int64_t> ids;
+    if (const IDSelectorRange* r = dynamic_cast<const IDSelectorRange*>(&sel)) {
+        kind = AMD_IVF_SUBSET_ID_RANGE;
+        a1 = r->imin;
+        a2 = r->imax;
+    } else if (const IDSelectorBatch* b = dynamic_cast<const IDSelectorBatch*>(&sel)) {
+        kind = AMD_IVF_SUBSET_ID_BATCH;
+        ids.assign(b->set.begin(), b->set.end());
+        std::sort(ids.begin(), ids.end());
+    } else {
+        FAISS_THROW_MSG("a search under this kind of IDSelector is not implemented");
+    }
+    amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
+    const bool kept = sel_ && sel_version_ == invlists->version && sel_kind_ == kind && sel_a1_ == a1 && sel_a2_ == a2 && sel_ids_ == ids;
+    if (!kept) {
+        if (sel_) amd_ivf_selector_destroy(sel_);
+        sel_ = nullptr;
+        AMD(amd_ivf_selector_create(g, kind, (int64_t)a1, (int64_t)a2, ids.empty() ? nullptr : ids.data(), ids.size(), &sel_));
+        selector_passes++;
+        sel_version_ = invlists->version;
+        sel_kind_ = kind;
+        sel_a1_ = a1;
+        sel_a2_ = a2;
+        sel_ids_.swap(ids);
+    }
+    AMD(amd_ivf_search_selected(g, sel_, (size_t)n, x, (size_t)k, nprobe, coarse_mode, distances, i64(labels)));
+}
+
 // ------------------------------------------------------------------------------------- IndexIVFFlatSubset
 void IndexIVFFlatSubset::cut(const IndexIVFFlat& src, int subset_type, idx_t a1, idx_t a2, const void* sel, size_t nsel) {
     FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(&src) == nullptr, "a subset of an IndexIVFFlatDedup is not implemented");

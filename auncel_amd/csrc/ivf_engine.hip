@@ -227,6 +227,13 @@ struct DevBuf {
         HIP_CHECK(hipMalloc(&p, want));
         cap = want;
     }
+    // a buffer that is sized once and kept (a selector's bits): no room to grow into
+    void exactly(size_t bytes) {
+        release();
+        if (bytes == 0) return;
+        HIP_CHECK(hipMalloc(&p, bytes));
+        cap = bytes;
+    }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
     void release() {
         if (p) (void)hipFree(p);
@@ -497,6 +504,10 @@ struct amd_ivf {
     uint64_t filter_launches = 0;  // last search: threshold rounds that went through the matrix-core filter (ivf_filter.hip)
     uint64_t hinted_rounds = 0, short_rounds = 0;  // last search: scan launches sized by a hint / of those, grids smaller than the work
     std::atomic<int> live_contexts{1};  // on the index owner: itself + its clones (amd_ivf_clone / amd_ivf_destroy)
+    // on the index owner: how often the lists were given or changed (amd_ivf_set_lists, _add, _update_lists, _remove_ids) -- what a
+    // selector's keep bits were laid out for (amd_ivf_selector_create) -- and the selectors made on it that are still alive
+    std::atomic<uint64_t> layout_gen{0};
+    std::atomic<int> live_selectors{0};
     std::atomic<float> tie_rate{-1.f};  // on the index owner: share of the last search's queries in which equal distances met (-1: none yet)
     std::atomic<int> active_searches{0};  // on the index owner: searches inside run_rounds_device right now
     bool force_heap_select = false;  // (set while a search is repeated after ERR_LOG_OVERFLOW)
@@ -1288,6 +1299,10 @@ struct RoundSpec {
     const uint32_t* split_wait = nullptr;
     const uint32_t* split_counts = nullptr; // [0] free, [1] waiting
     uint32_t split_wait_cap = 0;
+    // a search under an id selector (amd_ivf_search_selected): the selector's keep words, a bit per stored entry in the layout of
+    // ivf_subset.hip's mask.  Every round then carries a mask -- a dense round's is the keep words themselves, a threshold round's
+    // the scan's marks narrowed by them (keep_rows_kernel) -- and every selection is the masked one.
+    const unsigned long long* keep = nullptr;
 };
 
 static bool dbg_timing() {
@@ -2393,10 +2408,28 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
     // (profiles/r05_experiments.txt Y2)
     static const int nstreams = getenv("AUNCEL_AMD_SCAN_STREAMS") ? atoi(getenv("AUNCEL_AMD_SCAN_STREAMS")) : 1;
 
+    // a selected search (base.keep): the keep bits into the mask words of the round's rows, behind its scan
+    auto keep_args = [&](bool thr_mode, const uint32_t* counts, size_t round) {
+        KeepArgs ka{};
+        ka.nseg_dev = counts ? nullptr : dcnt + CNT_SEGMENTS;
+        ka.nseg = counts ? counts[CNT_SEGMENTS] : 0;
+        const uint32_t seen = hint_of(round, CNT_SEGMENTS);
+        ka.nseg_hint = (uint32_t)std::min<size_t>(seg_cap, seen ? (size_t)seen + seen / 8 + 4 : n * std::min<size_t>(total_nprobe, 64));
+        ka.nlist = (uint32_t)nlist;
+        ka.seg_list = h->w_seg_list.as<int32_t>();
+        ka.seg_off = h->w_seg_off.as<uint64_t>();
+        ka.list_off = I->d_list_off.as<uint64_t>();
+        ka.block_off = I->d_block_off.as<uint64_t>();
+        ka.keep = base.keep;
+        ka.mask = h->w_mask.as<unsigned long long>();
+        ka.write = thr_mode ? 0 : 1;
+        return ka;
+    };
     // ---- the scan of a planned round.  counts == nullptr: sizes on the device (chained); else the counters read back.
     auto enqueue_scan = [&](bool thr_mode, const uint32_t* counts, size_t round) {
         if (counts && counts[CNT_PAIRS] == 0) return;
         size_t t = h->timer.begin(thr_mode ? CAT_SCAN_THR : CAT_SCAN, s);
+        const KeepArgs ka = base.keep ? keep_args(thr_mode, counts, round) : KeepArgs{};
         if (base.bytes) {
             // byte codes: one launch of scan_mfma_kernel (no query packing: the A operand is gathered from the query matrix)
             MfmaScanArgs ma{};
@@ -2473,7 +2506,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
             ensure_aux(h, 3, 3);
             HIP_CHECK(hipEventRecord(h->ev_fork, s));
             HIP_CHECK(hipStreamWaitEvent(h->aux[3], h->ev_fork, 0));
-            launch_scan_filter(fa, h->aux[3]);
+            launch_scan_filter(fa, h->aux[3], base.keep ? &ka : nullptr);  // (the keep bits: before the survivors are rescored)
             h->filter_launches++;
             HIP_CHECK(hipEventRecord(h->ev_join[3], h->aux[3]));
             HIP_CHECK(hipStreamWaitEvent(s, h->ev_join[3], 0));
@@ -2527,6 +2560,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
                     HIP_CHECK(hipStreamWaitEvent(s, h->ev_join[i], 0));
                 }
         }
+        if (base.keep && !(filter_ok && thr_mode && !base.bytes)) launch_keep_rows(ka, s);
         h->timer.end(t, s);
     };
 
@@ -2585,7 +2619,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
         ra.round_probes = 0;
         ra.id_offset = base.id_offset;
         ra.dist = h->w_dist.as<float>();
-        ra.mask = thr_mode ? h->w_mask.as<unsigned long long>() : nullptr;
+        ra.mask = thr_mode || base.keep ? h->w_mask.as<unsigned long long>() : nullptr;
         ra.thr = no_thr ? nullptr : h->w_thr.as<float>();
         ra.seg_off = h->w_seg_off.as<uint64_t>();
         ra.seg_list = h->w_seg_list.as<int32_t>();
@@ -2957,7 +2991,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
 // round is cheaper than a second pass over the lists (5000 queries, 10M x 128, nprobe 8: 2.7 vs 2.1 M queries/s;
 // nprobe 32: 1.1 vs 1.3).
 void search_fixed_device(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, const int64_t* d_keys, float* D,
-                         int64_t* I, int store_pairs, size_t max_codes, const IntRange& qr) {
+                         int64_t* I, int store_pairs, size_t max_codes, const IntRange& qr, const unsigned long long* keep = nullptr) {
     CallScope call_scope(h);
     upload_lists(h);
     init_state(h, n, k, false);
@@ -2968,6 +3002,7 @@ void search_fixed_device(amd_ivf* h, const float* d_x, size_t n, size_t k, size_
     base.d_x = d_x;
     base.d_ckeys = d_keys;
     base.coarse_stride = (uint32_t)nprobe;
+    base.keep = keep;
     base.fused = h->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
     base.bytes = byte_queries(h, ix(h), d_x, n, qr);
     ix(h)->last_arith = base.bytes ? 2 : base.fused ? 1 : 0;
@@ -2988,12 +3023,13 @@ void search_fixed_device(amd_ivf* h, const float* d_x, size_t n, size_t k, size_
     });
 }
 
-void search_full(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I, const IntRange& qr) {
+void search_full(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I, const IntRange& qr,
+                 const unsigned long long* keep = nullptr) {
     h->w_cdis.ensure(n * nprobe * 4);
     h->w_ckeys.ensure(n * nprobe * 8);
     coarse_dev(h, d_x, n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
                h->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric));
-    search_fixed_device(h, d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, qr);
+    search_fixed_device(h, d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, qr, keep);
 }
 
 }  // namespace
@@ -3144,6 +3180,9 @@ int amd_ivf_clone(amd_ivf_t* h, amd_ivf_t** out) {
 int amd_ivf_destroy(amd_ivf_t* h) {
     API_BEGIN
     if (h) {
+        const int nsel = h->parent ? 0 : h->live_selectors.load();
+        if (nsel > 0)
+            throw EngineError(std::to_string(nsel) + " selector(s) made on this index are still alive: destroy them first (amd_ivf_selector_destroy)");
         use_device(h);
         if (h->parent) h->parent->live_contexts.fetch_sub(1);
         delete h;
@@ -3189,6 +3228,7 @@ int amd_ivf_set_lists(amd_ivf_t* h, const size_t* sizes, const float* const* cod
     NOT_A_SUBSET(h);
     size_t nt = 0;
     h->db_range = IntRange();
+    h->layout_gen.fetch_add(1);
     for (size_t l = 0; l < h->nlist; l++) {
         size_t n = sizes[l];
         h->db_range.add(codes[l], n * (size_t)h->d);
@@ -3235,6 +3275,7 @@ int amd_ivf_add(amd_ivf_t* h, size_t n, const float* x, const int64_t* xids, con
         double ms[NCAT], ln[NCAT];
         h->timer.collect(ms, NCAT, ln);
     }
+    h->layout_gen.fetch_add(1);  // (selectors made before this call are stale from here on)
     for (size_t i = 0; i < n; i++) {
         int64_t id = xids ? xids[i] : (int64_t)(h->ntotal + i);
         int64_t l = idx[i];
@@ -5141,6 +5182,7 @@ int amd_ivf_update_lists(amd_ivf_t* h, const size_t* sizes, size_t nw, const uin
     refuse_with_tickets(h);
     use_device(h);
     const bool journal = !h->lists_dirty && opt(h, OPT_INCREMENTAL, 1) != 0;
+    h->layout_gen.fetch_add(1);
     std::vector<char> moved(nlist, 0);
     for (size_t l = 0; l < nlist; l++) {  // (entries cut off take their values out of the list's range)
         const size_t os = h->h_ids[l].size();
@@ -5185,6 +5227,7 @@ int amd_ivf_remove_ids(amd_ivf_t* h, size_t n, const int64_t* ids, size_t* nremo
     auto member = [&](int64_t v) { const uint32_t b = bit(v); return ((bloom[b >> 6] >> (b & 63)) & 1) && sel.count(v); };
     const size_t dpad = h->dpad;
     const bool journal = !h->lists_dirty && opt(h, OPT_INCREMENTAL, 1) != 0;
+    h->layout_gen.fetch_add(1);
     size_t total = 0;
     // IndexIVF::remove_ids: a removed entry takes the list's last entry, and the entry that arrives there is looked at in turn
     for (size_t l = 0; l < h->nlist; l++) {
@@ -5264,6 +5307,65 @@ int amd_ivf_layout_digest(amd_ivf_t* h, uint64_t out[8]) {
     API_END
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------ membership of the stored entries
+// amd_ivf_selector_create: the keep bits of one selector over one index, as that index's lists lay when it was made
+struct amd_ivf_selector {
+    amd_ivf* index = nullptr;  // the owning handle of the index
+    uint64_t gen = 0;          // its layout_gen at the time
+    DevBuf keep;               // a bit per stored entry: list l owns words block_off[l] / 2 .. block_off[l + 1] / 2
+    DevBuf count;              // the set bits of every word
+    DevBuf list_kept;          // ... and of every list's words
+    uint64_t info[4] = {0, 0, 0, 0};  // amd_ivf_selector_info
+};
+
+namespace {
+// What the host prepares of a selector's arguments (selector_args.h), as long as the copies enqueued from it are in flight
+struct MemberStage {
+    DevBuf b_sel;
+    std::vector<uint64_t> runs;
+    std::vector<int64_t> batch;
+};
+// The one membership pass of a selector over h's resident lists (amd_ivf_subset, amd_ivf_selector_create): its arguments to the
+// device, then subset_member_kernel -- mask: a keep bit per stored entry, count: the set bits of every word, both in the layout
+// ivf_kernels.h describes (launch_subset_member).  The arguments were checked (selector_args_error), h's lists are uploaded and not
+// empty; enqueued on st, nothing is waited for.  Returns the bytes that crossed to the device.
+uint64_t membership_pass(amd_ivf* h, int type, int64_t a1, int64_t a2, const void* sel, size_t nsel, MemberStage& stage, uint64_t* mask,
+                                uint32_t* count, hipStream_t st) {
+    const size_t nlist = h->nlist;
+    const uint64_t nwords = h->h_block_off[nlist] / 2;
+    uint64_t h2d = 0;
+    SubsetSel ss{type, a1, a2, nullptr, nullptr, nullptr, 0};
+    DevBuf& b_sel = stage.b_sel;
+    if (type == SUBSET_SLICE) {
+        stage.runs = selector_slice_runs(h->h_list_off.data(), nlist, a1, a2);
+        b_sel.ensure(stage.runs.size() * 8);
+        HIP_CHECK(hipMemcpyAsync(b_sel.p, stage.runs.data(), stage.runs.size() * 8, hipMemcpyHostToDevice, st));
+        h2d += stage.runs.size() * 8;
+        ss.runs = b_sel.as<uint64_t>();
+    } else if (type == SUBSET_ID_BATCH) {
+        stage.batch = selector_batch(static_cast<const int64_t*>(sel), nsel);
+        b_sel.ensure(std::max<size_t>(stage.batch.size(), 1) * 8);
+        if (!stage.batch.empty()) HIP_CHECK(hipMemcpyAsync(b_sel.p, stage.batch.data(), stage.batch.size() * 8, hipMemcpyHostToDevice, st));
+        h2d += stage.batch.size() * 8;
+        ss.batch = b_sel.as<int64_t>();
+        ss.nsel = stage.batch.size();
+    } else if (type == SUBSET_ID_BITS) {
+        b_sel.ensure(std::max<size_t>(nsel, 1) * 8);
+        if (nsel) HIP_CHECK(hipMemcpyAsync(b_sel.p, sel, nsel * 8, hipMemcpyHostToDevice, st));
+        h2d += nsel * 8;
+        ss.bits = b_sel.as<uint64_t>();
+        ss.nsel = nsel;
+    }
+    launch_subset_member(h->d_ids.as<int64_t>(), h->d_list_off.as<uint64_t>(), h->d_block_off.as<uint64_t>(), (uint32_t)nlist, nwords, ss, mask, count,
+                         st);
+    return h2d;
+}
+}  // namespace
+
+extern "C" {
+
 // ------------------------------------------------------------------------------------ subset of a resident index
 // A new index on h's device whose list l holds the members of h's list l in h's order, cut in HBM (ivf_subset.hip): the device then
 // holds what amd_ivf_set_lists of the filtered lists would have made.  What crosses PCIe: the selector in, the SLICE runs in, the
@@ -5273,13 +5375,8 @@ int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const 
     if (!h || !out) throw EngineError("null argument");
     *out = nullptr;
     OWNER_ONLY(h);
-    const bool by_sel = subset_type == SUBSET_ID_BITS || subset_type == SUBSET_ID_BATCH;
-    if (subset_type != SUBSET_ID_RANGE && subset_type != SUBSET_ID_MOD && subset_type != SUBSET_SLICE && !by_sel)
-        throw EngineError("subset: unknown subset type (by-list subsets are made on the host)");
-    if (subset_type == SUBSET_ID_MOD && a1 <= 0) throw EngineError("subset: ID_MOD wants a1 > 0");
-    if (subset_type == SUBSET_SLICE && (a1 < 0 || a1 > a2 || (uint64_t)a2 > (uint64_t)h->ntotal))
-        throw EngineError("subset: SLICE wants 0 <= a1 <= a2 <= ntotal");
-    if (by_sel && !sel && nsel) throw EngineError("subset: null selector");
+    const std::string bad = selector_args_error("subset", subset_type, a1, a2, sel, nsel, (uint64_t)h->ntotal);
+    if (!bad.empty()) throw EngineError(bad);
     if (tickets_out(h)) throw EngineError("tickets are still out: wait for them before cutting a subset");
     use_device(h);
     upload_lists(h);  // (a pending journal or dirty lists: the subset sees every amd_ivf_add made before the call)
@@ -5343,51 +5440,17 @@ int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const 
     uint64_t kept = 0;
     if (nt > 0) {
         const uint64_t nwords = h->h_block_off[nlist] / 2;
-        DevBuf b_sel, b_mask, b_cnt, b_rank, b_tot, b_range;
-        SubsetSel ss{subset_type, a1, a2, nullptr, nullptr, nullptr, 0};
-        std::vector<uint64_t> runs;
-        std::vector<int64_t> batch;
-        if (subset_type == SUBSET_SLICE) {
-            // IndexIVF::copy_subset_to, type 2: the run of every list from the running count
-            runs.assign(2 * nlist, 0);
-            uint64_t cut1 = 0, cut2 = 0;
-            for (size_t l = 0; l < nlist; l++) {
-                const uint64_t next = h->h_list_off[l + 1], n1 = next * (uint64_t)a1 / nt, n2 = next * (uint64_t)a2 / nt;
-                runs[2 * l] = n1 - cut1;
-                runs[2 * l + 1] = n2 - cut2;
-                cut1 = n1;
-                cut2 = n2;
-            }
-            b_sel.ensure(runs.size() * 8);
-            HIP_CHECK(hipMemcpyAsync(b_sel.p, runs.data(), runs.size() * 8, hipMemcpyHostToDevice, st));
-            h2d += runs.size() * 8;
-            ss.runs = b_sel.as<uint64_t>();
-        } else if (subset_type == SUBSET_ID_BATCH) {
-            const int64_t* p = static_cast<const int64_t*>(sel);
-            batch.assign(p, p + nsel);
-            std::sort(batch.begin(), batch.end());
-            batch.erase(std::unique(batch.begin(), batch.end()), batch.end());
-            b_sel.ensure(std::max<size_t>(batch.size(), 1) * 8);
-            if (!batch.empty()) HIP_CHECK(hipMemcpyAsync(b_sel.p, batch.data(), batch.size() * 8, hipMemcpyHostToDevice, st));
-            h2d += batch.size() * 8;
-            ss.batch = b_sel.as<int64_t>();
-            ss.nsel = batch.size();
-        } else if (subset_type == SUBSET_ID_BITS) {
-            b_sel.ensure(std::max<size_t>(nsel, 1) * 8);
-            if (nsel) HIP_CHECK(hipMemcpyAsync(b_sel.p, sel, nsel * 8, hipMemcpyHostToDevice, st));
-            h2d += nsel * 8;
-            ss.bits = b_sel.as<uint64_t>();
-            ss.nsel = nsel;
-        }
+        DevBuf b_mask, b_cnt, b_rank, b_tot, b_range;
+        MemberStage stage;
         b_mask.ensure(nwords * 8);
         b_cnt.ensure(nwords * 4);
+        h2d += membership_pass(h, subset_type, a1, a2, sel, nsel, stage, b_mask.as<uint64_t>(), b_cnt.as<uint32_t>(), st);
         b_rank.ensure(nwords * 4);
         b_tot.ensure(nlist * 8);
         s->d_list_off.ensure((nlist + 1) * 8);
         s->d_block_off.ensure((nlist + 1) * 8);
         const uint64_t* p_off = h->d_list_off.as<uint64_t>();
         const uint64_t* p_boff = h->d_block_off.as<uint64_t>();
-        launch_subset_member(h->d_ids.as<int64_t>(), p_off, p_boff, (uint32_t)nlist, nwords, ss, b_mask.as<uint64_t>(), b_cnt.as<uint32_t>(), st);
         launch_subset_offsets(b_cnt.as<uint32_t>(), p_boff, (uint32_t)nlist, b_rank.as<uint32_t>(), b_tot.as<uint64_t>(), s->d_list_off.as<uint64_t>(),
                               s->d_block_off.as<uint64_t>(), st);
         s->h_block_off.assign(nlist + 1, 0);
@@ -5458,6 +5521,130 @@ int amd_ivf_last_subset(amd_ivf_t* sub, uint64_t out[4]) {
     API_BEGIN
     if (!sub || !out) throw EngineError("null argument");
     for (int i = 0; i < 4; i++) out[i] = ix(sub)->last_subset[i];
+    API_END
+}
+
+// ------------------------------------------------------------------------------------ search under an id selector
+int amd_ivf_selector_create(amd_ivf_t* h, int kind, int64_t a1, int64_t a2, const void* sel, size_t nsel, amd_ivf_selector_t** out) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("null argument");
+    *out = nullptr;
+    OWNER_ONLY(h);
+    const std::string bad = selector_args_error("selector", kind, a1, a2, sel, nsel, (uint64_t)h->ntotal);
+    if (!bad.empty()) throw EngineError(bad);
+    if (tickets_out(h)) throw EngineError("tickets are still out: wait for them before making a selector");
+    use_device(h);
+    upload_lists(h);  // (a pending journal or dirty lists: the selector sees every amd_ivf_add made before the call)
+    std::lock_guard<std::mutex> lock(h->upload_mu);
+    const size_t nlist = h->nlist;
+    const uint64_t nt = h->h_list_off[nlist];
+    for (size_t l = 0; l < nlist; l++)
+        if ((h->h_list_off[l + 1] - h->h_list_off[l]) >> 32) throw EngineError("selector: list too long");
+    std::unique_ptr<amd_ivf_selector> s(new amd_ivf_selector);
+    s->index = h;
+    s->gen = h->layout_gen.load();
+    uint64_t kept = 0, h2d = 0;
+    if (nt > 0) {
+        const uint64_t nwords = h->h_block_off[nlist] / 2;
+        hipStream_t st = h->stream;
+        MemberStage stage;
+        s->keep.exactly(nwords * 8);
+        s->count.exactly(nwords * 4);
+        s->list_kept.exactly(nlist * 4);
+        h2d += membership_pass(h, kind, a1, a2, sel, nsel, stage, s->keep.as<uint64_t>(), s->count.as<uint32_t>(), st);
+        launch_selector_list_kept(s->count.as<uint32_t>(), h->d_block_off.as<uint64_t>(), (uint32_t)nlist, s->list_kept.as<uint32_t>(), st);
+        std::vector<uint32_t> per_list(nlist, 0);
+        HIP_CHECK(hipMemcpyAsync(per_list.data(), s->list_kept.p, nlist * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(stream_sync(st));
+        for (size_t l = 0; l < nlist; l++) kept += per_list[l];
+        if (kept > nt) throw std::runtime_error("selector: more entries kept than looked at");
+    }
+    s->info[0] = nt;
+    s->info[1] = kept;
+    s->info[2] = h2d;
+    s->info[3] = s->keep.cap + s->count.cap + s->list_kept.cap;
+    h->live_selectors.fetch_add(1);
+    *out = s.release();
+    API_END
+}
+
+int amd_ivf_selector_destroy(amd_ivf_selector_t* s) {
+    API_BEGIN
+    if (!s) throw EngineError("null selector");
+    use_device(s->index);
+    s->index->live_selectors.fetch_sub(1);
+    delete s;
+    API_END
+}
+
+int amd_ivf_selector_info(amd_ivf_selector_t* s, uint64_t out[4]) {
+    API_BEGIN
+    if (!s || !out) throw EngineError("null argument");
+    for (int i = 0; i < 4; i++) out[i] = s->info[i];
+    API_END
+}
+
+}  // extern "C"
+
+namespace {
+// the keep words a selected search of h reads: the selector is of h's index and of its lists as they are now
+const unsigned long long* selector_words(amd_ivf* h, const amd_ivf_selector* s) {
+    if (s->index != ix(h)) throw EngineError("the selector was made on another index");
+    if (s->gen != ix(h)->layout_gen.load())
+        throw EngineError("the selector is stale: the index's lists were given or changed after it was made (amd_ivf_set_lists, amd_ivf_add, "
+                          "amd_ivf_update_lists, amd_ivf_remove_ids); make a new one");
+    return s->keep.as<unsigned long long>();
+}
+}  // namespace
+
+extern "C" {
+
+int amd_ivf_search_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe, int coarse_mode, float* D,
+                            int64_t* I) {
+    API_BEGIN
+    if (!h || !s) throw EngineError("null argument");
+    const unsigned long long* keep = selector_words(h, s);
+    use_device(h);
+    if (n == 0 || k == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const QueryRows q = host_rows(h, x, n);
+    search_full(h, q.d_x, n, k, nprobe, coarse_mode, D, I, q.range, keep);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_preassigned_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe,
+                                        const int64_t* keys, const float* coarse_dis, float* D, int64_t* I) {
+    API_BEGIN
+    (void)coarse_dis;  // (as in amd_ivf_search_preassigned)
+    if (!h || !s) throw EngineError("null argument");
+    const unsigned long long* keep = selector_words(h, s);
+    use_device(h);
+    if (n == 0 || k == 0) return 0;
+    if (!keys) throw EngineError("keys are required");
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const QueryRows q = host_rows(h, x, n);
+    h->w_ckeys.ensure(n * nprobe * 8);
+    HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, keys, n * nprobe * 8, hipMemcpyHostToDevice, h->stream));
+    search_fixed_device(h, q.d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, q.range, keep);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t k, size_t nprobe, int coarse_mode,
+                                     float* D, int64_t* I) {
+    API_BEGIN
+    if (!h || !s) throw EngineError("null argument");
+    const unsigned long long* keep = selector_words(h, s);
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    if (n == 0 || k == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    search_full(h, q.d_x, n, k, nprobe, coarse_mode, D, I, q.range, keep);
+    finish_timing(h, wc.stop());
     API_END
 }
 

@@ -333,12 +333,15 @@ void launch_filter_queries16(const float* x, size_t n, int d, int dpad, int metr
 // and request sixteen steps of their chain together: a survivor's chain of d / 4 steps is what the kernel's time is (a few
 // survivors per query, far fewer than lanes) -- with one lane a survivor and four steps a trip cfg 5 (d = 960) took 60 trips to
 // memory, 0.26 ms; now 15.
-template <int METRIC> __global__ __launch_bounds__(256) void rescore_kernel(FilterScanArgs a) {
+// KEEP (a search under an id selector): keep_rows_kernel has been through the round's mask words since the filter ran, and a survivor
+// whose bit went is not a member -- its distance is not computed, and nothing reads its place in the row.
+template <int METRIC, bool KEEP = false> __global__ __launch_bounds__(256) void rescore_kernel(FilterScanArgs a) {
     const uint32_t n = *a.surv_count < a.surv_cap ? *a.surv_count : a.surv_cap;
     const uint32_t sub = threadIdx.x & 3;
     for (uint32_t i = (blockIdx.x * 256 + threadIdx.x) >> 2; i < n; i += gridDim.x * 64) {
         const uint4 e = a.surv[i];  // (distance row position, query row, vector, -)
         if (e.x == 0xffffffffu) continue;  // (an unused slot of a wave's chunk; the same for the four lanes of a survivor)
+        if (KEEP && !((a.mask[e.x >> 6] >> (e.x & 63u)) & 1ull)) continue;
         const float* x = a.queries + (size_t)e.y * a.dpad;
         const float* y = a.codes + (size_t)e.z * a.dpad;
         float sl = 0.f;
@@ -833,43 +836,52 @@ uint32_t filter_item_vectors(int d) {
     return filter_steps(d) > 16 && !filter_narrow() ? FILTER_WIDE_VECTORS : mfma_chunk();
 }
 
-void launch_scan_filter(const FilterScanArgs& a, hipStream_t s) {
+void launch_scan_filter(const FilterScanArgs& a, hipStream_t s, const KeepArgs* keep) {
     if (a.nitems == 0 && !a.dev_nitems) return;
+    // the survivors' exact distances: all of them, or (keep) those of the selector's members
+    auto rescore = [&](auto resc, auto resc_keep) {
+        if (!keep) {
+            LAUNCH(resc, dim3(resident_grid(4)), dim3(256), 0, s, a);
+            return;
+        }
+        launch_keep_rows(*keep, s);
+        LAUNCH(resc_keep, dim3(resident_grid(4)), dim3(256), 0, s, a);
+    };
     const unsigned nwg = (a.nitems + 3) / 4;
     const int J = (int)(a.half ? filter_steps16(a.d) : filter_steps(a.d));
-    auto go = [&](auto kern, auto resc) {
+    auto go = [&](auto kern, auto resc, auto resc_keep) {
         static const unsigned per_cu = 3;
         const size_t hwg = ((size_t)a.hint_nitems + a.hint_nitems / 8 + 3) / 4;
         const unsigned hinted = (unsigned)((hwg + 7) / 8) * 8 + 8;
         const dim3 grid(a.dev_nitems ? (a.hint_nitems ? hinted : resident_grid(per_cu)) : (a.xcd_chunks ? ((nwg + 7) / 8) * 8 : nwg)), block(256);
         LAUNCH(kern, grid, block, 0, s, a);
-        LAUNCH(resc, dim3(resident_grid(4)), dim3(256), 0, s, a);
+        rescore(resc, resc_keep);
     };
-    auto go_wide = [&](auto kern, auto resc) {  // one workgroup per item
+    auto go_wide = [&](auto kern, auto resc, auto resc_keep) {  // one workgroup per item
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FILTER_WIDE_LDS);
         if (e != hipSuccess) throw std::runtime_error(std::string("filter kernel: cannot reserve LDS: ") + hipGetErrorString(e));
         const size_t hwg = (size_t)a.hint_nitems + a.hint_nitems / 8;
         const unsigned hinted = (unsigned)((hwg + 7) / 8) * 8 + 8;
         const dim3 grid(a.dev_nitems ? (a.hint_nitems ? hinted : resident_grid(2)) : (a.xcd_chunks ? ((a.nitems + 7) / 8) * 8 : a.nitems)), block(256);
         LAUNCH(kern, grid, block, FILTER_WIDE_LDS, s, a);
-        LAUNCH(resc, dim3(resident_grid(4)), dim3(256), 0, s, a);
+        rescore(resc, resc_keep);
     };
     const bool wide = filter_steps(a.d) > 16 && !filter_narrow();  // (as the planner shaped the items: filter_item_queries)
     auto pick = [&](auto metric) {
         constexpr int M = decltype(metric)::value;
         if (a.half) {
-            if (wide) return go_wide(scan_filter_wide_kernel<M, true>, rescore_kernel<M>);
-            if (J <= 4) return go(scan_filter_kernel<M, 4, true>, rescore_kernel<M>);
-            if (J <= 6) return go(scan_filter_kernel<M, 6, true>, rescore_kernel<M>);
-            if (J <= 8) return go(scan_filter_kernel<M, 8, true>, rescore_kernel<M>);
-            return go(scan_filter_kernel<M, 0, true>, rescore_kernel<M>);
+            if (wide) return go_wide(scan_filter_wide_kernel<M, true>, rescore_kernel<M>, rescore_kernel<M, true>);
+            if (J <= 4) return go(scan_filter_kernel<M, 4, true>, rescore_kernel<M>, rescore_kernel<M, true>);
+            if (J <= 6) return go(scan_filter_kernel<M, 6, true>, rescore_kernel<M>, rescore_kernel<M, true>);
+            if (J <= 8) return go(scan_filter_kernel<M, 8, true>, rescore_kernel<M>, rescore_kernel<M, true>);
+            return go(scan_filter_kernel<M, 0, true>, rescore_kernel<M>, rescore_kernel<M, true>);
         }
-        if (J <= 4) return go(scan_filter_kernel<M, 4, false>, rescore_kernel<M>);
-        if (J <= 8) return go(scan_filter_kernel<M, 8, false>, rescore_kernel<M>);
-        if (J <= 12) return go(scan_filter_kernel<M, 12, false>, rescore_kernel<M>);
-        if (J <= 16) return go(scan_filter_kernel<M, 16, false>, rescore_kernel<M>);
-        if (!wide) return go(scan_filter_kernel<M, 0, false>, rescore_kernel<M>);
-        return go_wide(scan_filter_wide_kernel<M, false>, rescore_kernel<M>);
+        if (J <= 4) return go(scan_filter_kernel<M, 4, false>, rescore_kernel<M>, rescore_kernel<M, true>);
+        if (J <= 8) return go(scan_filter_kernel<M, 8, false>, rescore_kernel<M>, rescore_kernel<M, true>);
+        if (J <= 12) return go(scan_filter_kernel<M, 12, false>, rescore_kernel<M>, rescore_kernel<M, true>);
+        if (J <= 16) return go(scan_filter_kernel<M, 16, false>, rescore_kernel<M>, rescore_kernel<M, true>);
+        if (!wide) return go(scan_filter_kernel<M, 0, false>, rescore_kernel<M>, rescore_kernel<M, true>);
+        return go_wide(scan_filter_wide_kernel<M, false>, rescore_kernel<M>, rescore_kernel<M, true>);
     };
     if (a.metric == METRIC_L2) pick(std::integral_constant<int, METRIC_L2>{});
     else pick(std::integral_constant<int, METRIC_IP>{});

@@ -11,6 +11,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "selector_args.h"
+
 namespace amdivf {
 
 // A launch the runtime rejects (grid, LDS or register limits) leaves nothing on the stream, and the later synchronisation
@@ -202,7 +204,10 @@ struct FilterScanArgs {
 struct FilterParams {
     float sx, ps, C, pad;
 };
-void launch_scan_filter(const FilterScanArgs& a, hipStream_t s);  // filter + rescoring, two launches
+struct KeepArgs;
+// filter + rescoring, two launches; keep (a selected search, ivf_selector.hip): the keep bits are brought into the round's mask
+// words between the two, and the rescoring leaves out the survivors whose bit went
+void launch_scan_filter(const FilterScanArgs& a, hipStream_t s, const KeepArgs* keep = nullptr);
 // pieces of 16 dimensions per vector in the fp16 fragment order: the step counts the one-wave kernel is built for (4, 6, 8) or an
 // even count beyond 128 dimensions
 inline __host__ __device__ uint32_t filter_steps16(int d) {
@@ -698,8 +703,7 @@ void launch_relayout_blocks(const void* old_main, void* new_main, uint64_t block
                             const uint64_t* old_boff, const uint64_t* new_boff, uint32_t nlist, uint64_t nblk_new, int shift, hipStream_t s);
 
 // ---------------------------------------------------------------------------- subset of a resident index (ivf_subset.hip)
-// Which entries a subset keeps (include/auncel_amd.h: amd_ivf_subset).  Every array is device memory.
-constexpr int SUBSET_ID_RANGE = 0, SUBSET_ID_MOD = 1, SUBSET_SLICE = 2, SUBSET_ID_BITS = 5, SUBSET_ID_BATCH = 6;
+// Which entries a subset keeps (include/auncel_amd.h: amd_ivf_subset; the kinds: selector_args.h).  Every array is device memory.
 struct SubsetSel {
     int type;
     int64_t a1, a2;          // ID_RANGE: a1 <= id < a2; ID_MOD: id % a1 == a2
@@ -721,6 +725,28 @@ void launch_subset_offsets(const uint32_t* count, const uint64_t* block_off, uin
 void launch_subset_compact(const float* old_codes, const int64_t* old_ids, const uint64_t* old_off, const uint64_t* old_block_off, uint32_t nlist,
                            uint64_t nwords, const uint64_t* mask, const uint32_t* rank_base, const uint64_t* new_off, int dpad, float* codes,
                            int64_t* ids, uint32_t* range, hipStream_t s);
+// ---------------------------------------------------------------------------- search under an id selector (ivf_selector.hip)
+// kept[l] = the set bits of list l's words (a wave per list)
+void launch_selector_list_kept(const uint32_t* count, const uint64_t* block_off, uint32_t nlist, uint32_t* kept, hipStream_t s);
+// The keep words of a selector into the mask words of a round's rows: row r (seg_list / seg_off, as the planner left them) of list l
+// owns the words seg_off[r] / 64 ... of the mask, one per 64 candidates, and word j of it lines up with keep word block_off[l] / 2 + j.
+// write = 1 (a dense round: the scan left no mask) the keep words become the row's mask, else (a threshold round) they are ANDed
+// into what the scan marked.
+struct KeepArgs {
+    const uint32_t* nseg_dev;  // rows of the round (device count), or null: nseg
+    uint32_t nseg;
+    uint32_t nseg_hint;        // sizes the grid
+    uint32_t nlist;
+    const int32_t* seg_list;
+    const uint64_t* seg_off;
+    const uint64_t* list_off;
+    const uint64_t* block_off;
+    const unsigned long long* keep;
+    unsigned long long* mask;
+    int write;
+};
+void launch_keep_rows(const KeepArgs& a, hipStream_t s);
+
 inline uint32_t subset_range_key(float x) {
     uint32_t u;
     memcpy(&u, &x, 4);

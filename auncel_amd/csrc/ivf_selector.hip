@@ -1,0 +1,63 @@
+// Search under an id selector (amd_ivf_selector_create, amd_ivf_search_selected): the selector is one keep bit per stored entry, in
+// the membership pass's own layout (ivf_subset.hip: a word per 64 entries of ONE list, list l's words from block_off[l] / 2), and a
+// search reads the parent's lists as they are.  What brings the bits into a round is keep_rows_kernel: the rounds already carry a
+// mask word per 64 candidates of a row, a row is the candidates of one list in list order, so word j of a row lines up with keep word
+// j of its list -- one pass over the round's mask words, 8 bytes in and 8 out per 64 candidates, behind the round's scan.  The
+// selection behind it is the masked walk it always was: no candidate that is not a member is ever seen.
+#include <hip/hip_runtime.h>
+
+#include "ivf_dev.h"
+
+namespace amdivf {
+
+namespace {
+
+// a wave per list: the set bits of its words
+__global__ __launch_bounds__(256) void selector_list_kept_kernel(const uint32_t* __restrict__ count, const uint64_t* __restrict__ boff, uint32_t nlist,
+                                                                 uint32_t* __restrict__ kept) {
+    const uint32_t l = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (l >= nlist) return;
+    const uint64_t w0 = boff[l] >> 1, w1 = boff[l + 1] >> 1;
+    uint32_t sum = 0;
+    for (uint64_t w = w0 + lane; w < w1; w += 64) sum += count[w];
+    sum = wave_sum_u32(sum);
+    if (lane == 0) kept[l] = sum;
+}
+
+// A wave per row, a lane per word, 64 words a trip (a row of the bench index is ~40 words: one trip); the rows of a round are dealt
+// to the resident waves in turn.  WRITE: a dense round (the scan stored every distance and no mask); else the scan's marks are
+// narrowed to the members.  Every word of a row is written, none behind it: what the selection's walk reads.
+template <bool WRITE> __global__ __launch_bounds__(256) void keep_rows_kernel(KeepArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t nseg = a.nseg_dev ? *a.nseg_dev : a.nseg;
+    const uint32_t stride = gridDim.x * 4u;
+    for (uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6); r < nseg; r += stride) {
+        const int key = a.seg_list[r];
+        if (key < 0 || (uint32_t)key >= a.nlist) continue;  // (an absent probe: the row is empty)
+        const uint32_t n = (uint32_t)(a.list_off[key + 1] - a.list_off[key]);
+        const uint32_t words = (n + 63u) >> 6;
+        const unsigned long long* kw = a.keep + (a.block_off[key] >> 1);
+        unsigned long long* mw = a.mask + (a.seg_off[r] >> 6);
+        for (uint32_t j = (uint32_t)lane; j < words; j += 64u) {
+            const unsigned long long k = kw[j];
+            mw[j] = WRITE ? k : (__builtin_nontemporal_load(mw + j) & k);
+        }
+    }
+}
+
+}  // namespace
+
+void launch_selector_list_kept(const uint32_t* count, const uint64_t* block_off, uint32_t nlist, uint32_t* kept, hipStream_t s) {
+    LAUNCH(selector_list_kept_kernel, dim3((nlist + 3) / 4), dim3(256), 0, s, count, block_off, nlist, kept);
+}
+
+void launch_keep_rows(const KeepArgs& a, hipStream_t s) {
+    const uint32_t want = a.nseg_dev ? a.nseg_hint : a.nseg;
+    if (want == 0) return;
+    const uint32_t grid = std::min<uint32_t>((want + 3u) / 4u, 8192u);
+    if (a.write) LAUNCH(keep_rows_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    else LAUNCH(keep_rows_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+}
+
+}  // namespace amdivf

@@ -119,6 +119,38 @@ int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const 
 /* {entries looked at, entries kept, host-to-device bytes, device-to-host bytes} of the call that made `sub` */
 int amd_ivf_last_subset(amd_ivf_t* sub, uint64_t out[4]);
 
+/* ---- search under an id selector, without a subset index -------------------------------
+ * The same selectors as amd_ivf_subset (kind, a1, a2, sel, nsel: the five AMD_IVF_SUBSET_* kinds, the same membership rules, made
+ * by the same pass over the resident ids), kept as ONE BIT PER STORED ENTRY instead of a second index: a selector moves no row and
+ * costs an eighth of a byte per entry plus its counts; several selectors of one index are alive at once and all of them search the
+ * same resident lists.  A pending amd_ivf_add of h is applied first; h itself is not changed.
+ * A selector belongs to the index it was made on and to the lists as they were: it is used from that handle and from its clones;
+ * amd_ivf_set_lists, amd_ivf_add, amd_ivf_update_lists and amd_ivf_remove_ids make it stale, and a search with a stale selector
+ * returns -2 (it never reads old bits).  It is destroyed on its own, and before its index: amd_ivf_destroy of an index with live
+ * selectors returns -2 and says how many there are.
+ * amd_ivf_selector_create returns -2 before the device is touched for: a null h / out, h a clone, tickets out on h, an unknown
+ * kind, a1 <= 0 (ID_MOD), a1 > a2 or a2 > ntotal (SLICE), sel == NULL with nsel > 0. */
+typedef struct amd_ivf_selector amd_ivf_selector_t;
+int amd_ivf_selector_create(amd_ivf_t* h, int kind, int64_t a1, int64_t a2, const void* sel, size_t nsel, amd_ivf_selector_t** out);
+int amd_ivf_selector_destroy(amd_ivf_selector_t* s);
+/* {entries looked at, entries kept, host-to-device bytes, device bytes held} */
+int amd_ivf_selector_info(amd_ivf_selector_t* s, uint64_t out[4]);
+/* amd_ivf_search / _search_preassigned / _search_resident over the members only: (D, I) are, bit for bit, what the same call
+ * returns on amd_ivf_subset(h, the same selector) -- the reference's search_preassigned over the lists with the non-members removed,
+ * in order; a query that finds fewer than k members ends with the reference's padding.  The coarse ranking is h's own.  In
+ * amd_ivf_stats, nheap_updates is the subset's (the admissions are the same sequence); ndis counts the entries of the probed lists
+ * AS h HOLDS THEM, members or not: every one of them is scanned.
+ * Fixed nprobe, ids, synchronous.  Not offered under a selector: the adaptive rule (its traces are trained on the whole index),
+ * range search, the scanner calls, tickets, store_pairs / max_codes, and one selector per QUERY -- there is no entry point that
+ * takes a selector for any of them, so none can return an unfiltered answer.  -2 for a null h / s, a selector of another index,
+ * a stale selector. */
+int amd_ivf_search_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe, int coarse_mode,
+                            float* D, int64_t* I);
+int amd_ivf_search_preassigned_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe,
+                                        const int64_t* keys, const float* coarse_dis, float* D, int64_t* I);
+int amd_ivf_search_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t k, size_t nprobe,
+                                     int coarse_mode, float* D, int64_t* I);
+
 /* ---- search ---------------------------------------------------------------------------- */
 
 /* quantizer->search(n, x, nprobe, coarse_dis, keys)  [IndexFlat.cpp:42-56].

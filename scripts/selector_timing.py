@@ -1,0 +1,79 @@
+"""Cost of a search under an id selector against a subset index: on the 10M x 128 byte-valued index of
+auncel_amd/synth.py, IVF4096, 1000 queries at nprobe 32, for id % 100 == 7, id % 10 == 3, id % 2 == 1 and a tenth of the id range,
+with byte codes and on the fp32 path: amd_ivf_selector_create and the first and the steady amd_ivf_search_selected; amd_ivf_subset
+and its first and steady search; the unfiltered search of the parent; the device bytes either route holds.  Steady: the median of
+--reps calls after a warm-up, as wall time and as the engine's own HIP-event time (amd_ivf_last_timing).  One JSON line per row.
+usage: python3 scripts/selector_timing.py [--nb N] [--reps R] [--unfiltered-only]"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from auncel_amd import capi, synth  # noqa: E402
+
+args = sys.argv[1:]
+NB = int(args[args.index("--nb") + 1]) if "--nb" in args else 10_000_000
+REPS = int(args[args.index("--reps") + 1]) if "--reps" in args else 20
+UNFILTERED_ONLY = "--unfiltered-only" in args  # (what also runs on a commit without the selector entry points)
+NQ, NLIST, D, K, NPROBE = 1000, 4096, 128, 10, 32
+xb, xq = synth.sift_like(NB, NQ, d=D)
+cen = synth.sample_centroids(xb, NLIST)
+h = capi.Handle(D, NLIST, capi.METRIC_L2, 0)
+h.set_centroids(cen)
+t0 = time.time()
+h.add(xb)
+h.search(xq, K, NPROBE)
+print(json.dumps({"nb": NB, "build_s": round(time.time() - t0, 1)}), flush=True)
+del xb
+
+
+def steady(handle, call):
+    """median wall and HIP-event ms of REPS calls after two warm-up calls"""
+    call()
+    call()
+    wall, dev = [], []
+    for _ in range(REPS):
+        t = time.time()
+        call()
+        wall.append((time.time() - t) * 1e3)
+        dev.append(handle.last_timing()["total_ms"])
+    return round(float(np.median(wall)), 3), round(float(np.median(dev)), 3)
+
+
+def timed(f):
+    t = time.time()
+    r = f()
+    return r, round((time.time() - t) * 1e3, 3)
+
+
+SELECTORS = [("mod_100 (1 %)", capi.SUBSET_ID_MOD, 100, 7), ("mod_10 (10 %)", capi.SUBSET_ID_MOD, 10, 3), ("mod_2 (50 %)", capi.SUBSET_ID_MOD, 2, 1),
+             ("range (10 %)", capi.SUBSET_ID_RANGE, NB // 2, NB // 2 + NB // 10)]
+for byte in (1, 0):
+    h.set_byte_codes(byte)
+    path = "bytes" if byte else "fp32"
+    w, d = steady(h, lambda: h.search(xq, K, NPROBE))
+    print(json.dumps({"path": path, "selector": "none (parent)", "steady_wall_ms": w, "steady_event_ms": d, "scan_arith": h.scan_arith()}), flush=True)
+    if UNFILTERED_ONLY:
+        continue
+    for name, kind, a1, a2 in SELECTORS:
+        row = {"path": path, "selector": name}
+        s, row["selector_create_ms"] = timed(lambda: h.selector(kind, a1, a2))
+        s.close()
+        s, row["selector_create_again_ms"] = timed(lambda: h.selector(kind, a1, a2))  # (allocations of the first are back in the pool)
+        (D0, I0), row["selected_first_ms"] = timed(lambda: h.search_selected(s, xq, K, NPROBE))
+        row["selected_steady_wall_ms"], row["selected_steady_event_ms"] = steady(h, lambda: h.search_selected(s, xq, K, NPROBE))
+        row["selector_info"] = s.info()
+        s.close()
+        sub, row["subset_ms"] = timed(lambda: h.subset(kind, a1, a2))
+        sub.set_byte_codes(byte)
+        (D1, I1), row["subset_first_ms"] = timed(lambda: sub.search(xq, K, NPROBE))
+        row["subset_steady_wall_ms"], row["subset_steady_event_ms"] = steady(sub, lambda: sub.search(xq, K, NPROBE))
+        nt, dpad = sub.ntotal, (D + 3) // 4 * 4
+        row["subset_rows_bytes"] = nt * (4 * dpad + 8)  # (rows and ids alone: the derived copies of its searches come on top)
+        row["same_results"] = bool(np.array_equal(I0, I1) and np.array_equal(D0.view(np.uint32), D1.view(np.uint32)))
+        sub.close()
+        print(json.dumps(row), flush=True)
+h.close()
