@@ -10,6 +10,7 @@ from . import build as _build
 
 METRIC_IP, METRIC_L2 = 0, 1
 SUBSET_ID_RANGE, SUBSET_ID_MOD, SUBSET_SLICE, SUBSET_ID_BITS, SUBSET_ID_BATCH = 0, 1, 2, 5, 6
+SELECTOR_AND, SELECTOR_OR, SELECTOR_ANDNOT, SELECTOR_NOT = 0, 1, 2, 3
 
 _f32p = C.POINTER(C.c_float)
 _i64p = C.POINTER(C.c_int64)
@@ -35,6 +36,8 @@ SYMBOLS = [
     "amd_ivf_subset", "amd_ivf_last_subset",
     "amd_ivf_selector_create", "amd_ivf_selector_destroy", "amd_ivf_selector_info",
     "amd_ivf_search_selected", "amd_ivf_search_preassigned_selected", "amd_ivf_search_resident_selected",
+    "amd_ivf_selector_combine", "amd_ivf_range_search_selected", "amd_ivf_range_search_preassigned_selected",
+    "amd_ivf_submit_search_resident_selected",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -240,10 +243,35 @@ class Selector:
         _chk(lib().amd_ivf_selector_info(self._s, out))
         return tuple(int(v) for v in out)
 
+    def combine(self, op, other=None):
+        """a new Selector of the same index from this one and `other` (SELECTOR_AND / OR / ANDNOT), or from this one alone
+        (SELECTOR_NOT: every stored entry it does not keep); made on the device, and alive on its own"""
+        out = Selector.__new__(Selector)
+        out._s = C.c_void_p()
+        out._index = self._index
+        _chk(lib().amd_ivf_selector_combine(int(op), self._s, other._s if other is not None else None, C.byref(out._s)))
+        return out
+
+    def __and__(self, other):
+        return self.combine(SELECTOR_AND, other)
+
+    def __or__(self, other):
+        return self.combine(SELECTOR_OR, other)
+
+    def __sub__(self, other):
+        return self.combine(SELECTOR_ANDNOT, other)
+
+    def __invert__(self):
+        return self.combine(SELECTOR_NOT)
+
     def close(self):
         if self._s:
-            lib().amd_ivf_selector_destroy(self._s)
+            rc = lib().amd_ivf_selector_destroy(self._s)
+            if rc == -2:  # (refused: tickets that search under it are still out -- the selector stays valid)
+                raise EngineError(rc, lib().amd_ivf_last_error().decode())
             self._s = C.c_void_p()
+
+    destroy = close
 
     def __enter__(self):
         return self
@@ -422,6 +450,41 @@ class Handle:
         _chk(lib().amd_ivf_search_resident_selected(self._h, selector._s, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k), C.c_size_t(nprobe),
                                                     coarse_mode, _f(D), _i(I)))
         return D, I
+
+    def range_search_selected(self, selector, x, radius, nprobe, keys=None, coarse_mode=0):
+        """range_search over the selector's members -> lims (n + 1), labels, distances"""
+        x = f32(x)
+        n = x.shape[0]
+        lims = np.zeros(n + 1, dtype=np.uintp)
+        lp = lims.ctypes.data_as(_szp)
+        if keys is None:
+            _chk(lib().amd_ivf_range_search_selected(self._h, selector._s, C.c_size_t(n), _f(x), C.c_float(radius), C.c_size_t(nprobe),
+                                                     coarse_mode, lp))
+        else:
+            keys = i64(keys)
+            assert keys.shape == (n, nprobe)
+            _chk(lib().amd_ivf_range_search_preassigned_selected(self._h, selector._s, C.c_size_t(n), _f(x), C.c_float(radius),
+                                                                 C.c_size_t(nprobe), _i(keys), lp))
+        tot = int(lims[n])
+        labels = np.empty(max(tot, 1), np.int64)
+        dist = np.empty(max(tot, 1), np.float32)
+        _chk(lib().amd_ivf_range_results(self._h, _i(labels), _f(dist)))
+        return lims.astype(np.int64), labels[:tot], dist[:tot]
+
+    def submit_search_resident_selected(self, selector, start, n, k, nprobe, coarse_mode=0, out=None):
+        """asynchronous search_resident_selected: returns a ticket for wait(); the selector cannot be closed before it"""
+        if out is not None:
+            D, I = out
+        else:
+            D = np.empty((n, k), np.float32)
+            I = np.empty((n, k), np.int64)
+        t = C.c_uint64(0)
+        _chk(lib().amd_ivf_submit_search_resident_selected(self._h, selector._s, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k),
+                                                           C.c_size_t(nprobe), coarse_mode, _f(D), _i(I), C.byref(t)))
+        if not hasattr(self, "_tickets"):
+            self._tickets = {}
+        self._tickets[int(t.value)] = (selector, None, None, None, D, I)
+        return int(t.value)
 
     # ---- search
     def coarse(self, x, nprobe, mode=0):

@@ -3410,8 +3410,11 @@ int amd_ivf_set_queries(amd_ivf_t* h, size_t n, const float* x) {
 }
 
 // IndexIVF::range_search_preassigned (IndexIVF.cpp:759-857): device-planned rounds in threshold mode, radius as threshold
+// keep: under an id selector (amd_ivf_range_search_selected) -- every round of a range search is a threshold round, so the keep
+// words are ANDed into the scan's marks (enqueue_scan: keep_rows_kernel behind the scan, whichever kernel it was) before
+// range_collect_kernel counts them: the mask bits it counts and fills from are the members' inside the radius, in list order
 static void range_core(amd_ivf* h, const float* d_x, size_t n, float radius, size_t nprobe, const int64_t* d_keys, const IntRange& qr,
-                       size_t* lims) {
+                       size_t* lims, const unsigned long long* keep = nullptr) {
     upload_lists(h);
     init_state(h, n, 1, false);
     launch_fill_f32(h->w_thr.as<float>(), n, radius, h->stream);
@@ -3424,6 +3427,7 @@ static void range_core(amd_ivf* h, const float* d_x, size_t n, float radius, siz
     base.d_x = d_x;
     base.d_ckeys = d_keys;
     base.coarse_stride = (uint32_t)nprobe;
+    base.keep = keep;
     base.fused = h->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
     base.bytes = byte_queries(h, ix(h), d_x, n, qr);
     ix(h)->last_arith = base.bytes ? 2 : base.fused ? 1 : 0;
@@ -4783,6 +4787,20 @@ int amd_ivf_last_direct_out(amd_ivf_t* h);
 
 }  // extern "C"
 
+// amd_ivf_selector_create, amd_ivf_selector_combine: the keep bits of one selector over one index, as that index's lists lay when it
+// was made
+struct amd_ivf_selector {
+    amd_ivf* index = nullptr;  // the owning handle of the index
+    uint64_t gen = 0;          // its layout_gen at the time
+    DevBuf keep;               // a bit per stored entry: list l owns words block_off[l] / 2 .. block_off[l + 1] / 2
+    DevBuf count;              // the set bits of every word
+    DevBuf list_kept;          // ... and of every list's words
+    uint64_t info[4] = {0, 0, 0, 0};  // amd_ivf_selector_info
+    // tickets that search under it and have not finished running (amd_ivf_submit_search_resident_selected): counted under the
+    // pool's mutex, and amd_ivf_selector_destroy refuses while there are any -- no kernel of a ticket reads freed keep words
+    mutable int tickets = 0;
+};
+
 // ---------------------------------------------------------------------------------------------
 // Asynchronous searches.  One synchronous call leaves the GPU to one search at a time, whose selection and planning phases are
 // latency-bound; several searches in flight fill those phases with each other's scans (1.6 x the throughput on the bench
@@ -4806,6 +4824,7 @@ struct AsyncJob {
     std::function<int(amd_ivf_t*)> run;
     bool adaptive = false;
     AdaptiveSpec spec;
+    const amd_ivf_selector* sel = nullptr;  // the selector it searches under: its use count is this job's until it has run
     uint32_t coalesced = 1;  // tickets the pass that served this one served
     int rc = 0;
     bool done = false;
@@ -4925,6 +4944,7 @@ static void async_worker(AsyncPool* p, size_t i) {
                 j->error = err;
                 j->rc = rc;
                 j->done = true;
+                if (j->sel) j->sel->tickets--;  // (the search has synchronised: nothing of it reads the keep words any more)
             }
             p->running--;
             p->served_tickets += group.size();
@@ -4982,10 +5002,12 @@ static void async_shutdown(amd_ivf* h) {
     delete p;
 }
 
-static uint64_t async_enqueue(amd_ivf* h, std::function<int(amd_ivf_t*)> run, const AdaptiveSpec* spec = nullptr) {
+static uint64_t async_enqueue(amd_ivf* h, std::function<int(amd_ivf_t*)> run, const AdaptiveSpec* spec = nullptr,
+                              const amd_ivf_selector* sel = nullptr) {
     AsyncPool* p = async_pool(h);
     std::unique_ptr<AsyncJob> j(new AsyncJob);
     j->run = std::move(run);
+    j->sel = sel;
     if (spec) {
         j->adaptive = true;
         j->spec = *spec;
@@ -4994,6 +5016,7 @@ static uint64_t async_enqueue(amd_ivf* h, std::function<int(amd_ivf_t*)> run, co
     {
         std::lock_guard<std::mutex> lk(p->mu);
         id = p->next++;
+        if (sel) sel->tickets++;
         p->queue.push_back(j.get());
         p->jobs[id] = std::move(j);
     }
@@ -5310,16 +5333,6 @@ int amd_ivf_layout_digest(amd_ivf_t* h, uint64_t out[8]) {
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------ membership of the stored entries
-// amd_ivf_selector_create: the keep bits of one selector over one index, as that index's lists lay when it was made
-struct amd_ivf_selector {
-    amd_ivf* index = nullptr;  // the owning handle of the index
-    uint64_t gen = 0;          // its layout_gen at the time
-    DevBuf keep;               // a bit per stored entry: list l owns words block_off[l] / 2 .. block_off[l + 1] / 2
-    DevBuf count;              // the set bits of every word
-    DevBuf list_kept;          // ... and of every list's words
-    uint64_t info[4] = {0, 0, 0, 0};  // amd_ivf_selector_info
-};
-
 namespace {
 // What the host prepares of a selector's arguments (selector_args.h), as long as the copies enqueued from it are in flight
 struct MemberStage {
@@ -5568,9 +5581,58 @@ int amd_ivf_selector_create(amd_ivf_t* h, int kind, int64_t a1, int64_t a2, cons
     API_END
 }
 
+// A selector from one or two others of the same index and layout: one pass over their keep words (selector_combine_kernel), nothing
+// crosses PCIe but the per-list counts coming back.  The result owns its words: the operands may go first.
+int amd_ivf_selector_combine(int op, const amd_ivf_selector_t* a, const amd_ivf_selector_t* b, amd_ivf_selector_t** out) {
+    API_BEGIN
+    if (out) *out = nullptr;
+    if (!a || !out) throw EngineError(selector_combine_error(op, nullptr, nullptr, false, 0, false));  // (nothing of a is read)
+    {
+        const SelectorOperand oa{a->index, a->gen}, ob{b ? b->index : nullptr, b ? b->gen : 0};
+        const std::string bad = selector_combine_error(op, &oa, b ? &ob : nullptr, true, a->index->layout_gen.load(), tickets_out(a->index));
+        if (!bad.empty()) throw EngineError(bad);
+    }
+    amd_ivf* h = a->index;
+    use_device(h);
+    std::lock_guard<std::mutex> lock(h->upload_mu);
+    const size_t nlist = h->nlist;
+    const uint64_t nt = a->info[0];
+    std::unique_ptr<amd_ivf_selector> s(new amd_ivf_selector);
+    s->index = h;
+    s->gen = a->gen;
+    uint64_t kept = 0;
+    if (nt > 0) {  // (the operands are of the lists as they are now: what amd_ivf_selector_create uploaded is what the device holds)
+        const uint64_t nwords = h->h_block_off[nlist] / 2;
+        if (a->keep.cap < nwords * 8 || (b && b->keep.cap < nwords * 8)) throw std::runtime_error("selector combine: an operand is shorter than the lists");
+        hipStream_t st = h->stream;
+        s->keep.exactly(nwords * 8);
+        s->count.exactly(nwords * 4);
+        s->list_kept.exactly(nlist * 4);
+        launch_selector_combine(op, a->keep.as<uint64_t>(), b ? b->keep.as<uint64_t>() : nullptr, h->d_list_off.as<uint64_t>(),
+                                h->d_block_off.as<uint64_t>(), (uint32_t)nlist, s->keep.as<uint64_t>(), s->count.as<uint32_t>(),
+                                s->list_kept.as<uint32_t>(), st);
+        std::vector<uint32_t> per_list(nlist, 0);
+        HIP_CHECK(hipMemcpyAsync(per_list.data(), s->list_kept.p, nlist * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(stream_sync(st));
+        for (size_t l = 0; l < nlist; l++) kept += per_list[l];
+        if (kept > nt) throw std::runtime_error("selector combine: more entries kept than looked at");
+    }
+    s->info[0] = nt;
+    s->info[1] = kept;
+    s->info[2] = 0;
+    s->info[3] = s->keep.cap + s->count.cap + s->list_kept.cap;
+    h->live_selectors.fetch_add(1);
+    *out = s.release();
+    API_END
+}
+
 int amd_ivf_selector_destroy(amd_ivf_selector_t* s) {
     API_BEGIN
     if (!s) throw EngineError("null selector");
+    if (AsyncPool* p = s->index->async) {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (s->tickets > 0) throw EngineError("tickets that search under this selector are still out: wait for them first (amd_ivf_wait)");
+    }
     use_device(s->index);
     s->index->live_selectors.fetch_sub(1);
     delete s;
@@ -5645,6 +5707,74 @@ int amd_ivf_search_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, 
     reset_scan_counters(h);
     search_full(h, q.d_x, n, k, nprobe, coarse_mode, D, I, q.range, keep);
     finish_timing(h, wc.stop());
+    API_END
+}
+
+// amd_ivf_range_search_preassigned / amd_ivf_range_search over the members only (range_core: where the AND sits in a round)
+int amd_ivf_range_search_preassigned_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, float radius, size_t nprobe,
+                                              const int64_t* keys, size_t* lims) {
+    API_BEGIN
+    if (!h || !s || !lims) throw EngineError("null argument");
+    const unsigned long long* keep = selector_words(h, s);
+    use_device(h);
+    if (nprobe == 0) throw EngineError("nprobe must be positive");
+    if (n && !keys) throw EngineError("keys are required");
+    WallClock wc(h->stream);
+    const QueryRows q = host_rows(h, x, n);
+    h->w_ckeys.ensure(std::max<size_t>(n, 1) * nprobe * 8);
+    if (n) HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, keys, n * nprobe * 8, hipMemcpyHostToDevice, h->stream));
+    if (n == 0) {
+        h->r_lims.assign(1, 0);
+        h->r_labels.clear();
+        h->r_dist.clear();
+        lims[0] = 0;
+        return 0;
+    }
+    reset_scan_counters(h);
+    range_core(h, q.d_x, n, radius, nprobe, h->w_ckeys.as<int64_t>(), q.range, lims, keep);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_range_search_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, float radius, size_t nprobe,
+                                  int coarse_mode, size_t* lims) {
+    API_BEGIN
+    if (!h || !s || !lims) throw EngineError("null argument");
+    const unsigned long long* keep = selector_words(h, s);
+    use_device(h);
+    if (nprobe == 0) throw EngineError("nprobe must be positive");
+    WallClock wc(h->stream);
+    if (n == 0) {
+        h->r_lims.assign(1, 0);
+        h->r_labels.clear();
+        h->r_dist.clear();
+        lims[0] = 0;
+        return 0;
+    }
+    const QueryRows q = host_rows(h, x, n);
+    upload_lists(h);
+    h->w_cdis.ensure(n * nprobe * 4);
+    h->w_ckeys.ensure(n * nprobe * 8);
+    coarse_dev(h, q.d_x, n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
+               h->allow_fused && ix(h)->centroid_range.fusable_with(q.range, h->metric));
+    reset_scan_counters(h);
+    range_core(h, q.d_x, n, radius, nprobe, h->w_ckeys.as<int64_t>(), q.range, lims, keep);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+// amd_ivf_search_resident_selected as a ticket.  The selector is checked here; the calls that would make it stale are refused while
+// tickets are out, and its use count (amd_ivf_selector::tickets) keeps it alive until the search has run.
+int amd_ivf_submit_search_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t k, size_t nprobe,
+                                            int coarse_mode, float* D, int64_t* I, uint64_t* ticket) {
+    API_BEGIN
+    if (!h || !s || !ticket) throw EngineError("null argument");
+    OWNER_ONLY(h);
+    selector_words(h, s);
+    use_device(h);
+    if (start + n > h->n_resident) throw EngineError("resident query range out of bounds");
+    *ticket = async_enqueue(
+        h, [=](amd_ivf_t* c) { return amd_ivf_search_resident_selected(c, s, start, n, k, nprobe, coarse_mode, D, I); }, nullptr, s);
     API_END
 }
 

@@ -728,6 +728,11 @@ void launch_subset_compact(const float* old_codes, const int64_t* old_ids, const
 // ---------------------------------------------------------------------------- search under an id selector (ivf_selector.hip)
 // kept[l] = the set bits of list l's words (a wave per list)
 void launch_selector_list_kept(const uint32_t* count, const uint64_t* block_off, uint32_t nlist, uint32_t* kept, hipStream_t s);
+// amd_ivf_selector_combine: keep[w] = op(a[w], b[w]) & the bits of w that stand for entries of its list (selector_args.h:
+// selector_combine_word, selector_valid_word, from list_off alone), count[w] its set bits, kept[l] those of list l's words.  A wave
+// per list; b is null for SELECTOR_NOT; keep may not alias a or b.
+void launch_selector_combine(int op, const uint64_t* a, const uint64_t* b, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                             uint64_t* keep, uint32_t* count, uint32_t* kept, hipStream_t s);
 // The keep words of a selector into the mask words of a round's rows: row r (seg_list / seg_off, as the planner left them) of list l
 // owns the words seg_off[r] / 64 ... of the mask, one per 64 candidates, and word j of it lines up with keep word block_off[l] / 2 + j.
 // write = 1 (a dense round: the scan left no mask) the keep words become the row's mask, else (a threshold round) they are ANDed

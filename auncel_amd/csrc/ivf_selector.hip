@@ -4,6 +4,7 @@
 // mask word per 64 candidates of a row, a row is the candidates of one list in list order, so word j of a row lines up with keep word
 // j of its list -- one pass over the round's mask words, 8 bytes in and 8 out per 64 candidates, behind the round's scan.  The
 // selection behind it is the masked walk it always was: no candidate that is not a member is ever seen.
+// Selectors of one index share that layout, so they combine word by word (amd_ivf_selector_combine: selector_combine_kernel).
 #include <hip/hip_runtime.h>
 
 #include "ivf_dev.h"
@@ -21,6 +22,29 @@ __global__ __launch_bounds__(256) void selector_list_kept_kernel(const uint32_t*
     const uint64_t w0 = boff[l] >> 1, w1 = boff[l + 1] >> 1;
     uint32_t sum = 0;
     for (uint64_t w = w0 + lane; w < w1; w += 64) sum += count[w];
+    sum = wave_sum_u32(sum);
+    if (lane == 0) kept[l] = sum;
+}
+
+// amd_ivf_selector_combine.  A wave per list, its lanes stride over the list's words, 8 bytes in per operand and 8 out; what a word
+// may hold comes from the list's length, never from the operands -- ~a sets the tail of the last used word and every padding word,
+// and a dense round would take those bits for candidates.  The counts ride along: no second pass, no shared counter.
+__global__ __launch_bounds__(256) void selector_combine_kernel(int op, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
+                                                               const uint64_t* __restrict__ off, const uint64_t* __restrict__ boff, uint32_t nlist,
+                                                               uint64_t* __restrict__ keep, uint32_t* __restrict__ count,
+                                                               uint32_t* __restrict__ kept) {
+    const uint32_t l = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (l >= nlist) return;
+    const uint64_t w0 = boff[l] >> 1, w1 = boff[l + 1] >> 1, n = off[l + 1] - off[l];
+    uint32_t sum = 0;
+    for (uint64_t w = w0 + lane; w < w1; w += 64) {
+        const uint64_t r = selector_combine_word(op, a[w], b ? b[w] : 0ull) & selector_valid_word(n, w - w0);
+        const uint32_t c = (uint32_t)__popcll(r);
+        keep[w] = r;
+        count[w] = c;
+        sum += c;
+    }
     sum = wave_sum_u32(sum);
     if (lane == 0) kept[l] = sum;
 }
@@ -50,6 +74,12 @@ template <bool WRITE> __global__ __launch_bounds__(256) void keep_rows_kernel(Ke
 
 void launch_selector_list_kept(const uint32_t* count, const uint64_t* block_off, uint32_t nlist, uint32_t* kept, hipStream_t s) {
     LAUNCH(selector_list_kept_kernel, dim3((nlist + 3) / 4), dim3(256), 0, s, count, block_off, nlist, kept);
+}
+
+void launch_selector_combine(int op, const uint64_t* a, const uint64_t* b, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
+                             uint64_t* keep, uint32_t* count, uint32_t* kept, hipStream_t s) {
+    if (nlist == 0) return;
+    LAUNCH(selector_combine_kernel, dim3((nlist + 3) / 4), dim3(256), 0, s, op, a, b, list_off, block_off, nlist, keep, count, kept);
 }
 
 void launch_keep_rows(const KeepArgs& a, hipStream_t s) {

@@ -1,13 +1,21 @@
 // The host side of an id selector (include/auncel_amd.h: amd_ivf_subset, amd_ivf_selector_create): which kinds there are, which
 // arguments they take, and what the host prepares for the membership pass (ivf_subset.hip) -- the per-list runs of a SLICE and the
 // sorted ids of an ID_BATCH.  Plain C++, nothing of the device in it: both callers share it, and it builds on its own
-// (tests/cpp/selector_args_main.cpp runs it under the address and undefined-behaviour sanitizers).
+// (tests/cpp/selector_args_main.cpp runs it under the address and undefined-behaviour sanitizers).  So are the operand checks of
+// amd_ivf_selector_combine and the one rule that says which bits of a keep word stand for entries (selector_valid_word: the combine
+// kernel and tests/cpp/selector_combine_main.cpp read the same definition).
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
+
+#if defined(__HIPCC__)
+#define SELECTOR_HD __host__ __device__
+#else
+#define SELECTOR_HD
+#endif
 
 namespace amdivf {
 
@@ -48,6 +56,44 @@ inline std::vector<int64_t> selector_batch(const int64_t* ids, size_t n) {
     std::sort(batch.begin(), batch.end());
     batch.erase(std::unique(batch.begin(), batch.end()), batch.end());
     return batch;
+}
+
+// ---- amd_ivf_selector_combine
+constexpr int SELECTOR_AND = 0, SELECTOR_OR = 1, SELECTOR_ANDNOT = 2, SELECTOR_NOT = 3;
+
+// what the checks read of an operand: the index it was made on and that index's layout_gen at the time
+struct SelectorOperand {
+    const void* index;
+    uint64_t gen;
+};
+
+// empty: the operands can be combined; else the message of the refusal.  a / b: null where the caller passed none; index_gen: the
+// layout_gen of a's index as it is now (read only behind the null checks); tickets: searches submitted on it and not yet waited for
+inline std::string selector_combine_error(int op, const SelectorOperand* a, const SelectorOperand* b, bool have_out, uint64_t index_gen, bool tickets) {
+    const std::string w("selector combine: ");
+    if (!a || !have_out) return w + "null argument";
+    if (op != SELECTOR_AND && op != SELECTOR_OR && op != SELECTOR_ANDNOT && op != SELECTOR_NOT) return w + "unknown op";
+    if (op == SELECTOR_NOT && b) return w + "NOT takes one operand (b must be null)";
+    if (op != SELECTOR_NOT && !b) return w + "a binary op wants two operands (null b)";
+    if (b && b->index != a->index) return w + "the operands were made on different indexes";
+    if (a->gen != index_gen || (b && b->gen != index_gen))
+        return w + "an operand is stale: the index's lists were given or changed after it was made; make a new one";
+    if (tickets) return w + "tickets are still out: wait for them before making a selector";
+    return std::string();
+}
+
+// The bits of keep word j of a list of n entries that stand for entries: all 64 while the word lies inside the list, the low n - 64 j
+// in the word the list ends in, none in a word behind it (a list's block count is rounded up to even, and may be padded further).
+// Every reader of keep words relies on the other bits being zero: a dense round's mask is the keep words themselves.
+SELECTOR_HD inline uint64_t selector_valid_word(uint64_t n, uint64_t j) {
+    const uint64_t first = j << 6;
+    if (j >= ((uint64_t)1 << 58) || first >= n) return 0;
+    const uint64_t left = n - first;
+    return left >= 64 ? ~(uint64_t)0 : (((uint64_t)1 << left) - 1);
+}
+
+SELECTOR_HD inline uint64_t selector_combine_word(int op, uint64_t a, uint64_t b) {
+    return op == SELECTOR_AND ? (a & b) : op == SELECTOR_OR ? (a | b) : op == SELECTOR_ANDNOT ? (a & ~b) : ~a;
 }
 
 }  // namespace amdivf

@@ -127,7 +127,8 @@ int amd_ivf_last_subset(amd_ivf_t* sub, uint64_t out[4]);
  * A selector belongs to the index it was made on and to the lists as they were: it is used from that handle and from its clones;
  * amd_ivf_set_lists, amd_ivf_add, amd_ivf_update_lists and amd_ivf_remove_ids make it stale, and a search with a stale selector
  * returns -2 (it never reads old bits).  It is destroyed on its own, and before its index: amd_ivf_destroy of an index with live
- * selectors returns -2 and says how many there are.
+ * selectors returns -2 and says how many there are; amd_ivf_selector_destroy of a selector that tickets still search under
+ * (amd_ivf_submit_search_resident_selected) returns -2 and leaves it alive until they have been waited for.
  * amd_ivf_selector_create returns -2 before the device is touched for: a null h / out, h a clone, tickets out on h, an unknown
  * kind, a1 <= 0 (ID_MOD), a1 > a2 or a2 > ntotal (SLICE), sel == NULL with nsel > 0. */
 typedef struct amd_ivf_selector amd_ivf_selector_t;
@@ -135,21 +136,45 @@ int amd_ivf_selector_create(amd_ivf_t* h, int kind, int64_t a1, int64_t a2, cons
 int amd_ivf_selector_destroy(amd_ivf_selector_t* s);
 /* {entries looked at, entries kept, host-to-device bytes, device bytes held} */
 int amd_ivf_selector_info(amd_ivf_selector_t* s, uint64_t out[4]);
+/* Selectors combined on the device: *out keeps the stored entries that op says, from the keep bits of a and b as they lie in HBM --
+ * one pass over a bit per entry, nothing crosses PCIe (info: {entries looked at, kept, 0, device bytes held}).  *out is a selector
+ * like any other: it belongs to a's index and to the same lists, counts among the index's live selectors, works with every
+ * _selected entry point and as an operand of a later combine, and is destroyed on its own -- a and b may be destroyed before it.
+ * NOT keeps every STORED entry that a does not keep: the bits past a list's end stay zero whatever the op.
+ * Returns -2 before the device is touched for: a null a / out, an unknown op, b == NULL for a binary op or b != NULL for NOT,
+ * operands made on different indexes, a stale operand, tickets out on the index. */
+#define AMD_IVF_SELECTOR_AND 0    /* a & b  */
+#define AMD_IVF_SELECTOR_OR 1     /* a | b  */
+#define AMD_IVF_SELECTOR_ANDNOT 2 /* a & ~b */
+#define AMD_IVF_SELECTOR_NOT 3    /* ~a, b must be NULL */
+int amd_ivf_selector_combine(int op, const amd_ivf_selector_t* a, const amd_ivf_selector_t* b, amd_ivf_selector_t** out);
 /* amd_ivf_search / _search_preassigned / _search_resident over the members only: (D, I) are, bit for bit, what the same call
  * returns on amd_ivf_subset(h, the same selector) -- the reference's search_preassigned over the lists with the non-members removed,
  * in order; a query that finds fewer than k members ends with the reference's padding.  The coarse ranking is h's own.  In
  * amd_ivf_stats, nheap_updates is the subset's (the admissions are the same sequence); ndis counts the entries of the probed lists
  * AS h HOLDS THEM, members or not: every one of them is scanned.
- * Fixed nprobe, ids, synchronous.  Not offered under a selector: the adaptive rule (its traces are trained on the whole index),
- * range search, the scanner calls, tickets, store_pairs / max_codes, and one selector per QUERY -- there is no entry point that
- * takes a selector for any of them, so none can return an unfiltered answer.  -2 for a null h / s, a selector of another index,
- * a stale selector. */
+ * Fixed nprobe or a radius (below), ids.  Not offered under a selector: the adaptive rule (its traces are trained on the whole
+ * index), the scanner calls, store_pairs / max_codes, tickets of any search but amd_ivf_search_resident_selected, and one selector
+ * per QUERY -- there is no entry point that takes a selector for any of them, so none can return an unfiltered answer.  -2 for a
+ * null h / s, a selector of another index, a stale selector. */
 int amd_ivf_search_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe, int coarse_mode,
                             float* D, int64_t* I);
 int amd_ivf_search_preassigned_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe,
                                         const int64_t* keys, const float* coarse_dis, float* D, int64_t* I);
 int amd_ivf_search_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t k, size_t nprobe,
                                      int coarse_mode, float* D, int64_t* I);
+/* amd_ivf_range_search / _range_search_preassigned over the members only; the results are fetched with amd_ivf_range_results.  lims,
+ * labels and distances are, bit for bit and in the same order, what the same call returns on amd_ivf_subset(h, the same selector).
+ * ndis as above: the probed lists' entries as h holds them.  -2 as above, before anything is read. */
+int amd_ivf_range_search_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, float radius, size_t nprobe,
+                                  int coarse_mode, size_t* lims);
+int amd_ivf_range_search_preassigned_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, float radius,
+                                              size_t nprobe, const int64_t* keys, size_t* lims);
+/* amd_ivf_search_resident_selected in flight: a ticket for amd_ivf_wait, as amd_ivf_submit_search_resident (below).  The selector is
+ * checked at submit (-2 as above, and no ticket is issued); it cannot go stale under a ticket, since every call that changes the
+ * lists is refused while tickets are out, and it cannot be destroyed under one (amd_ivf_selector_destroy, above).  Owner only. */
+int amd_ivf_submit_search_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t k, size_t nprobe,
+                                            int coarse_mode, float* D, int64_t* I, uint64_t* ticket);
 
 /* ---- search ---------------------------------------------------------------------------- */
 
