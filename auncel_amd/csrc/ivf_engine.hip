@@ -502,6 +502,7 @@ struct amd_ivf {
     int64_t* out_I = nullptr;
     int last_direct_out = 0;  // whether the last search did
     uint64_t filter_launches = 0;  // last search: threshold rounds that went through the matrix-core filter (ivf_filter.hip)
+    uint64_t plan_passes = 0;      // last call: planning passes launched (amd_ivf_last_timing's rounds; counted whether or not phases are timed)
     uint64_t hinted_rounds = 0, short_rounds = 0;  // last search: scan launches sized by a hint / of those, grids smaller than the work
     std::atomic<int> live_contexts{1};  // on the index owner: itself + its clones (amd_ivf_clone / amd_ivf_destroy)
     // on the index owner: how often the lists were given or changed (amd_ivf_set_lists, _add, _update_lists, _remove_ids) -- what a
@@ -1749,7 +1750,7 @@ static void fill_timing(amd_ivf* h, const double* ms, const double* ln) {
     h->timing[1] = ms[CAT_SCAN] + ms[CAT_SCAN_THR];
     h->timing[2] = ms[CAT_SELECT] + ms[CAT_SELECT_THR] + ms[CAT_TIE_FIX];
     h->timing[4] = ln[CAT_SCAN] + ln[CAT_SCAN_THR];
-    h->timing[7] = ln[CAT_SELECT] + ln[CAT_SELECT_THR] + ln[CAT_TIE_FIX];
+    h->timing[7] = (double)h->plan_passes;
     for (int c = 0; c < NCAT; c++) h->timing_detail[2 * c] = ms[c], h->timing_detail[2 * c + 1] = ln[c];
     h->timing_detail[2 * NCAT] = h->scan_min_bytes - h->scan_min_bytes_thr;
     h->timing_detail[2 * NCAT + 1] = h->scan_min_bytes_thr;
@@ -1767,6 +1768,7 @@ void finish_timing(amd_ivf* h, double wall_ms) {
 static inline void reset_scan_counters(amd_ivf* h) {
     h->scan_bytes = h->scan_min_bytes = h->scan_min_bytes_thr = 0;
     h->scan_slots = h->scan_useful = 0;
+    h->plan_passes = 0;
 }
 
 struct WallClock {
@@ -2173,6 +2175,12 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
     size_t maxlist = 0;
     for (size_t l = 0; l < nlist; l++) maxlist = std::max<size_t>(maxlist, I->h_list_off[l + 1] - I->h_list_off[l]);
     const size_t item_cap = (seg_cap / 32 + nlist) * ((maxlist + SCAN_WAVE_VECS - 1) / SCAN_WAVE_VECS) + nlist * 4 + 16;
+    // AUNCEL_AMD_SEG_CAP_PAIRS (tests; read once per process): fewer pairs a round, so that the planner's cut is taken at small
+    // shapes.  It only lowers what a ROUND may hold -- the planner's limit and the host's "nothing can be deferred" below -- and
+    // never below one query's probes (the first active query of a round is admitted unconditionally).  Every buffer and grid hint
+    // stays sized from seg_cap itself.
+    static const size_t seg_cap_env = getenv("AUNCEL_AMD_SEG_CAP_PAIRS") ? (size_t)atol(getenv("AUNCEL_AMD_SEG_CAP_PAIRS")) : 0;
+    const size_t round_pairs = seg_cap_env ? std::min(seg_cap, std::max(seg_cap_env, total_nprobe)) : seg_cap;
     // rows are padded to multiples of 64 floats (one mask word covers 64 candidates of one row)
     // A query's rows of a round are consecutive, one (padded) list length per probe, whether the scan stores every distance
     // (round 0) or the < 1 % that beat the threshold: after round 0 the buffer is address space more than traffic, and a
@@ -2277,7 +2285,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
     pa.grow = std::max<double>(base.tuner.multipler, grow);
     pa.id_offset = base.id_offset;
     pa.dist_budget = budget;
-    pa.seg_cap = (uint32_t)seg_cap;
+    pa.seg_cap = (uint32_t)round_pairs;
     pa.keys = base.d_ckeys;
     pa.list_off = I->d_list_off.as<uint64_t>();
     pa.stage = h->w_stage.as<uint32_t>();
@@ -2399,6 +2407,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
         launch_plan(pa, s);
         h->timer.end(t, s);
         planned_rounds++;
+        h->plan_passes++;
     };
     static const bool xcd_off = getenv("AUNCEL_AMD_NO_XCD_CHUNKS") != nullptr;
     // side streams of an fp32 round's tile shapes.  Round 4 gave every shape its own (each filled the chip's LDS by itself); the
@@ -2802,7 +2811,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
     if (chained) {
         // a fixed-nprobe search ends with its last planned round when no query can be deferred (rows and pairs fit the buffers)
         const size_t padded = (maxlist + 1023) & ~(size_t)1023;
-        const bool fits = (double)n * (double)total_nprobe * (double)padded <= (double)budget && n * total_nprobe <= seg_cap;
+        const bool fits = (double)n * (double)total_nprobe * (double)padded <= (double)budget && n * total_nprobe <= round_pairs;
         bool fixed_complete = !base.tuner.enabled && !base.train.enabled && fits && (base.fixed_two || first_round >= total_nprobe);
         static const size_t ahead_env = getenv("AUNCEL_AMD_ROUNDS_AHEAD") ? (size_t)atoi(getenv("AUNCEL_AMD_ROUNDS_AHEAD")) : 0;
         // (a handful of queries: three in four are done after the first round, and looking costs less than a round of empty launches)

@@ -355,12 +355,20 @@ int amd_ivf_range_results(amd_ivf_t* h, int64_t* labels, float* distances);
  *                              amd_ivf_clone contexts) exports GPU_MAX_HW_QUEUES=8 before anything -- torch included -- starts the HIP
  *                              runtime (bench.py and the tests do).  With fewer queues the asynchronous entry points run only as
  *                              many searches at a time as there are queues in a class and say so once on stderr (AUNCEL_AMD_QUIET)
+ * Debugging knobs of the round planner's cut (plan_prefix_body defers the queries that do not fit a round to another pass over the
+ * lists), each read ONCE per process, by the first search -- setting them later changes nothing (tests/test_gpu_budget_cut.py runs
+ * them in child processes):
+ * AUNCEL_AMD_DIST_BUDGET_MB=<n> the distance workspace of a round in MiB (2^18 floats each) instead of what the search would take;
+ *                              never below the lists' vectors + 1024 x nlist + 1024 floats, so one query's rows always fit
+ * AUNCEL_AMD_SEG_CAP_PAIRS=<n>  the (query, list) pairs a round may hold; only ever lowers the engine's own cap (2 Mi pairs), never
+ *                              below a query's nprobe; the buffers keep the size they have without it
  * The other AUNCEL_AMD_* variables the sources read are measurement switches (DESIGN.md names the ones it quotes). */
 
 /* ---- measurement hooks (bench.py): time of the kernels of the last search call, from HIP events
  *      recorded on the engine's own stream: {coarse_ms, scan_ms, select_ms, total_ms, scan_launches,
  *      bytes of the distances the scan tiles computed (x d x 4), fraction of the computed (query, vector)
- *      slots that were wanted pairs, select launches (= rounds x sub-batches)} */
+ *      slots that were wanted pairs, planning passes of the call (= rounds planned, the last look of a search that is planned
+ *      once more to find nothing left included; counted on the host, so also where the phases are not timed)} */
 int amd_ivf_last_timing(amd_ivf_t* h, double out[8]);
 /* the same by phase, (ms, launches) pairs: coarse ranking, dense scan (round 0), selection of dense rounds, threshold scan,
  * selection of threshold rounds, tie_fix_kernel (its own stream), round planning; then the bytes the dense and the threshold
