@@ -770,6 +770,17 @@ class Handle:
                                          C.c_size_t(train_num), coarse_mode, ptrs, _f(D), _i(I)))
         return D, I
 
+    def train_samples_x(self, x, id_offset, max_topk, gt_D, train_num, raw, coarse_mode=0):
+        """train_samples over the caller's query rows: row qi is query id_offset + qi of gt_D and of raw"""
+        x, gt = f32(x), f32(gt_D)
+        n = x.shape[0]
+        D = np.empty((n, max_topk), np.float32)
+        I = np.empty((n, max_topk), np.int64)
+        ptrs = (_f32p * len(raw))(*[_f(r) for r in raw])
+        _chk(lib().amd_ivf_train_samples_x(self._h, C.c_size_t(n), _f(x), C.c_size_t(id_offset), C.c_size_t(max_topk), _f(gt),
+                                           C.c_size_t(train_num), coarse_mode, ptrs, _f(D), _i(I)))
+        return D, I
+
     def scan_arith(self):
         """0 fp32 reference order, 1 fp32 fused, 2 byte codes (include/auncel_amd.h)"""
         return int(lib().amd_ivf_scan_arith(self._h))

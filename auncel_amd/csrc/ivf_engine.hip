@@ -4368,10 +4368,20 @@ int amd_ivf_search_adaptive_pre(amd_ivf_t* h, size_t n, const float* x, size_t i
     API_END
 }
 
+// A raw trace holds train_num rows of max_topk / 4 samples and query start + qi writes row start + qi: both limits are the caller's
+// to keep, and past them the kernel would write behind the buffer (the reference does, in host memory).  Checked before a call
+// uploads or launches anything.
+static void check_train_rows(size_t start, size_t n, size_t max_topk, size_t train_num) {
+    if (max_topk < 4) throw EngineError("train mode needs max_topk >= 4 (a raw trace row holds max_topk / 4 samples)");
+    if (n > train_num || start > train_num - n)
+        throw EngineError("train mode needs start + n (id_offset + n) <= train_num: the raw traces hold train_num rows");
+}
+
 static void train_core(amd_ivf_t* h, const float* d_x, size_t start, size_t n, size_t max_topk, const float* gt_D, size_t train_num,
                           int coarse_mode, float* const* raw, float* D, int64_t* I, const IntRange& qr) {
     use_device(h);
     if (!h->have_interdis) throw EngineError("Search tune start can't start without IVF_pro init and training");
+    check_train_rows(start, n, max_topk, train_num);
     if (n == 0) return;
     const size_t K = max_topk, nlist = h->nlist;
     if (nlist <= nlist / 8 + 20) throw EngineError("train mode needs nprobe(=nlist) > nlist/8 + 20");
@@ -4421,6 +4431,7 @@ static void train_core(amd_ivf_t* h, const float* d_x, size_t start, size_t n, s
     base.train.arcos = h->d_arcos.as<float>();
     base.train.gt_D = h->w_misc2.as<float>();
     base.train.raw = reinterpret_cast<float* const*>(h->w_rawptrs.p);
+    h->plan_passes = 0;
     run_rounds_device(h, base, n, 32, np_row, nullptr);
     HIP_CHECK(hipMemcpyAsync(D, h->w_D.p, n * K * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipMemcpyAsync(I, h->w_I.p, n * K * 8, hipMemcpyDeviceToHost, h->stream));
@@ -4429,6 +4440,7 @@ static void train_core(amd_ivf_t* h, const float* d_x, size_t start, size_t n, s
     HIP_CHECK(stream_sync(h->stream));
     double ms[NCAT], ln[NCAT];
     h->timer.collect(ms, NCAT, ln);
+    h->timing[7] = (double)h->plan_passes;  // amd_ivf_last_timing's rounds: the planning passes of this call (the phases are not reported)
 }
 
 int amd_ivf_train_samples(amd_ivf_t* h, size_t start, size_t n, size_t max_topk, const float* gt_D, size_t train_num,
@@ -4447,6 +4459,7 @@ int amd_ivf_train_samples_x(amd_ivf_t* h, size_t n, const float* x, size_t id_of
     API_BEGIN
     OWNER_ONLY(h);
     use_device(h);
+    check_train_rows(id_offset, n, max_topk, train_num);
     if (n == 0) return 0;
     const QueryRows q = host_rows(h, x, n);
     train_core(h, q.d_x, id_offset, n, max_topk, gt_D, train_num, coarse_mode, raw, D, I, q.range);
@@ -4459,6 +4472,7 @@ int amd_ivf_train_samples_pre(amd_ivf_t* h, size_t n, const float* x, size_t id_
     API_BEGIN
     OWNER_ONLY(h);
     use_device(h);
+    check_train_rows(id_offset, n, max_topk, train_num);
     if (n == 0) return 0;
     const QueryRows q = host_rows(h, x, n);
     GivenCoarse given(h, nprobe, keys, coarse_dis);

@@ -288,15 +288,21 @@ int amd_ivf_search_timed_x(amd_ivf_t* h, size_t n, const float* x, size_t id_off
 
 /* search_preassigned, training branch, driven as Error_sys::sys_train does: raw (sum_angle, kscaling)
  * samples for stages 1,2,4..nlist/8 of resident queries [start, start+n); raw[i] has
- * train_num*(max_topk/4) (x,y) pairs and must be pre-filled with (-1,-1)  [IndexIVF.cpp:640-673, profile.cpp:88-156] */
+ * train_num*(max_topk/4) (x,y) pairs and must be pre-filled with (-1,-1)  [IndexIVF.cpp:640-673, profile.cpp:88-156].
+ * Query start + qi reads row start + qi of gt_D (max_topk floats a row) and writes row start + qi of every raw[i] (max_topk / 4
+ * pairs a row, rounded down), so the call is refused with -2, before anything reaches the device and with raw, D and I untouched,
+ * when start + n > train_num or when max_topk < 4 (a row of no pairs; the reference writes behind its buffers in both cases).
+ * amd_ivf_last_timing reports the call's planning passes (out[7]) and leaves the phase times of the search before it. */
 int amd_ivf_train_samples(amd_ivf_t* h, size_t start, size_t n, size_t max_topk, const float* gt_D, size_t train_num,
                           int coarse_mode, float* const* raw, float* D, int64_t* I);
 
+/* the same over n query rows of the caller's: row qi is query id_offset + qi of gt_D and of raw.  -2 as above when
+ * id_offset + n > train_num or max_topk < 4. */
 int amd_ivf_train_samples_x(amd_ivf_t* h, size_t n, const float* x, size_t id_offset, size_t max_topk, const float* gt_D,
                             size_t train_num, int coarse_mode, float* const* raw, float* D, int64_t* I);
 
 /* the training branch over the caller's coarse ranking (search_preassigned with training on and its keys / coarse_dis
- * arguments, IndexIVF.cpp:382-386,640-673); nprobe > nlist/8 + 20 */
+ * arguments, IndexIVF.cpp:382-386,640-673); nprobe > nlist/8 + 20.  -2 as above when id_offset + n > train_num or max_topk < 4. */
 int amd_ivf_train_samples_pre(amd_ivf_t* h, size_t n, const float* x, size_t id_offset, size_t nprobe, const int64_t* keys,
                               const float* coarse_dis, size_t max_topk, const float* gt_D, size_t train_num, float* const* raw,
                               float* D, int64_t* I);

@@ -67,6 +67,13 @@ def run_call(capi, inp, h, call):
                                                gt_D=inp[call["gt"]], profile=call["profile"])
         out["my_nprobe"] = my_np.astype(np.int64)
         out["t_recalls"] = t_rec
+    elif op == "train":
+        n, K, ntr = xq.shape[0], call["K"], call["ntraces"]
+        h.set_queries(xq)
+        raw = [np.full((n * (K // 4), 2), -1, dtype=np.float32) for _ in range(ntr)]
+        out["D"], out["I"] = h.train_samples(0, n, K, inp[call["gt"]], n, raw)
+        for i, r in enumerate(raw):
+            out[f"raw{i}"] = r
     else:
         raise ValueError("unknown op " + op)
     st = h.stats()

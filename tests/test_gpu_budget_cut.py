@@ -9,7 +9,8 @@ MORE planning passes under a knob than without (last_timing()["rounds"]): a comp
 Groups: A plan_small_kernel (20 queries); B the full planner, a query a thread (1024), ragged lists (byte / float data, both metrics,
 k 10 / 100, one / two rounds, sorted / heap selection, store_pairs, max_codes); C two queries a thread (1500 queries); D heavy ties
 (tie_fix_kernel replays deferred queries); E range search, plain and under an id selector, one radius exactly on a query's 5th
-distance; F adaptive search (byte, float, inner product; profile on / off); G search under an id selector; H time-bounded search.
+distance; F adaptive search (byte, float, inner product; profile on / off); G search under an id selector; H time-bounded search;
+T trace training over F's indexes and queries (raw traces, D and I).
 
 Measured on an MI355X: the module takes 5 s (the oracle's side, 1 s, included); the children 0.9 s (no knob), 1.4 s and 1.6 s."""
 import json
@@ -27,9 +28,9 @@ CHILD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "budget_cut_chi
 L2, IP = 1, 0
 CHILDREN = {"baseline": {}, "budget": {"AUNCEL_AMD_DIST_BUDGET_MB": "1"}, "pairs": {"AUNCEL_AMD_SEG_CAP_PAIRS": "256"}}
 GROUPS = ["A", "B_bytes_l2", "B_bytes_ip", "B_float_l2", "B_float_ip", "C", "D", "E_bytes_l2", "E_bytes_ip", "E_float_l2", "E_float_ip",
-          "E_dups", "F_bytes", "F_float", "F_ip", "G", "H"]
+          "E_dups", "F_bytes", "F_float", "F_ip", "G", "H", "T"]
 # the calls of these groups hold more than 256 pairs a round (A: 20 x 8, D's search: 64 x 5 only just, G / H: not asked for)
-PAIR_GROUPS = ("B", "C", "E", "F")
+PAIR_GROUPS = ("B", "C", "E", "F", "T")
 # make_case seeds of test_gpu_random_adaptive.py whose 150 queries are byte-valued / float / inner product.  Queries of the oracle
 # that read past the first round (my_nprobe > 12, the probes of an adaptive search's first round), the same with profile on and off:
 # 147, 141 and 80 of 150.
@@ -191,6 +192,7 @@ def build_cases(oracle, adaptive_seeds=None, counts=None):
     c.group("E_dups")
     add_range_calls(c, "E_dups", "D", dlists, L2, dxq, dck, "D/xq", "D/keys")
     # ---- F: adaptive search, 150 queries each
+    trained = []
     for gname, seed in (adaptive_seeds or ADAPTIVE_SEEDS).items():
         f = make_case(seed)
         assert f["xq"].shape[0] == 150
@@ -206,6 +208,7 @@ def build_cases(oracle, adaptive_seeds=None, counts=None):
         cd, ck = oracle.knn(f["metric"], f["xq"], f["cen"], f["nlist"], nthreads=8)
         gtD, _ = oracle.knn(f["metric"], f["xq"], f["xb"], K, nthreads=8)
         c.arrays[gname + "/xq"], c.arrays[gname + "/req"], c.arrays[gname + "/gt"] = f["xq"], f["req"], gtD
+        trained.append((gname, f, lists, cd, ck, gtD))
         c.group(gname)
         for profile in (False, True):
             tun = oracle.Tuner(oracle.interdis(f["metric"], f["cen"]), traces, K, nq)
@@ -239,6 +242,18 @@ def build_cases(oracle, adaptive_seeds=None, counts=None):
     assert (np.diff(cd, axis=1) != 0).all(), "coarse ties: take another seed"
     eD, eI, _ = oracle.search_preassigned(lists, xq, 10, ck, cd)
     c.call("H_timed", "B_bytes_l2", "timed", dict(D=eD, I=eI, used=np.full(130, 16, np.int64)), xq="B_bytes_l2/xq", k=10, nprobe=16)
+    # ---- T: trace training (the search pass of Error_sys::sys_train) over F's indexes, queries and ground truth: the first round
+    #         holds 150 x 32 pairs, so both knobs cut it
+    c.group("T")
+    for gname, f, lists, cd, ck, gtD in trained:
+        K, ntr = f["K"], 1
+        while (1 << ntr) <= f["nlist"] // 8:
+            ntr += 1
+        raw = [np.full((150 * (K // 4), 2), -1, dtype=np.float32) for _ in range(ntr)]
+        eD, eI = oracle.train_samples(lists, f["xq"], K, ck, cd, oracle.interdis(f["metric"], f["cen"]), oracle.arcos_table(), gtD, 0, 150, raw)
+        assert all((r[:, 1] > 0).any() for r in raw), gname
+        c.call("T" + gname[1:], gname, "train", dict(D=eD, I=eI, **{f"raw{i}": r for i, r in enumerate(raw)}), xq=gname + "/xq",
+               gt=gname + "/gt", K=int(K), ntraces=ntr)
     return c
 
 
