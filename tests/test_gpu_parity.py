@@ -775,17 +775,25 @@ def test_asynchronous_searches_equal_the_synchronous_ones(capi, name):
 
 @pytest.mark.parametrize("name", ["fixed_sift_l2", "fixed_deep_ip_d96"])
 def test_asynchronous_fixed_nprobe_searches(capi, name):
-    """amd_ivf_submit_search_resident: fixed-nprobe searches in flight from one caller; same bits as the synchronous call"""
+    """amd_ivf_submit_search_resident: fixed-nprobe searches in flight from one caller; same bits as the synchronous call, and as the
+    reference's golden (D, I) -- over the whole resident set and over a slice that does not start at its first query"""
     case, gold = load_case(name)
     h = make_index(capi, case, gold)
     h.set_queries(case["xq"])
     nq, k = case["xq"].shape[0], int(case["ks"][0])
     eD, eI = h.search_resident(0, nq, k, case["nprobe"])
+    assert np.array_equal(eI, gold[f"I_k{k}"]) and np.array_equal(bits(eD), bits(gold[f"D_k{k}"]))
     h.set_async_depth(2)
     tickets = [h.submit_search_resident(0, nq, k, case["nprobe"]) for _ in range(5)]
+    q0 = nq // 2 + 1
+    sliced = [h.submit_search_resident(q0, n, k, case["nprobe"]) for n in (nq - q0, 1)]
     for t in tickets:
         D, I, timing, diag = h.wait(t)
         assert np.array_equal(I, eI) and np.array_equal(bits(D), bits(eD))
+        assert np.array_equal(I, gold[f"I_k{k}"]) and np.array_equal(bits(D), bits(gold[f"D_k{k}"]))
+    for t, n in zip(sliced, (nq - q0, 1)):
+        D, I, timing, diag = h.wait(t)
+        assert np.array_equal(I, gold[f"I_k{k}"][q0:q0 + n]) and np.array_equal(bits(D), bits(gold[f"D_k{k}"][q0:q0 + n]))
     h.close()
 
 
