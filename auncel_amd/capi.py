@@ -38,6 +38,7 @@ SYMBOLS = [
     "amd_ivf_search_selected", "amd_ivf_search_preassigned_selected", "amd_ivf_search_resident_selected",
     "amd_ivf_selector_combine", "amd_ivf_range_search_selected", "amd_ivf_range_search_preassigned_selected",
     "amd_ivf_submit_search_resident_selected",
+    "amd_ivf_search_exact", "amd_ivf_search_exact_resident", "amd_ivf_last_exact",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -512,6 +513,28 @@ class Handle:
         I = np.empty((n, k), np.int64)
         _chk(lib().amd_ivf_search(self._h, C.c_size_t(n), _f(x), C.c_size_t(k), C.c_size_t(nprobe), coarse_mode, _f(D), _i(I)))
         return D, I
+
+    def search_exact(self, x, k):
+        """exact top-k over every list (include/auncel_amd.h: amd_ivf_search_exact): search_preassigned with identity keys, bit for bit"""
+        x = f32(x)
+        n = x.shape[0]
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_exact(self._h, C.c_size_t(n), _f(x), C.c_size_t(k), _f(D), _i(I)))
+        return D, I
+
+    def search_exact_resident(self, start, n, k):
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_exact_resident(self._h, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k), _f(D), _i(I)))
+        return D, I
+
+    def last_exact(self):
+        """(queries answered by the list pass, searched the general way because equal distances met, ... for any other reason,
+        candidates the list pass emitted) of the last exact call"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_last_exact(self._h, out))
+        return tuple(int(v) for v in out)
 
     def range_search(self, x, radius, nprobe, keys=None, coarse_mode=0):
         """IndexIVF::range_search(_preassigned) -> lims (n + 1), labels, distances"""

@@ -1,0 +1,46 @@
+// The host side of the exact search over the whole index (include/auncel_amd.h: amd_ivf_search_exact): what the entry points refuse
+// before anything touches a device, and the one rule that says when a query's result can be read off its sorted candidates (DESIGN.md
+// 13).  Plain C++, nothing of the device in it: exact_select_kernel (ivf_exact.hip) and the host read the same definition, and it
+// builds on its own (tests/cpp/exact_args_main.cpp runs it under the address and undefined-behaviour sanitizers).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#if defined(__HIPCC__)
+#define EXACT_HD __host__ __device__
+#else
+#define EXACT_HD
+#endif
+
+namespace amdivf {
+
+// empty: the arguments are valid; else the message of the refusal.  have_queries: the query rows were passed (the resident form has
+// them on the device: true); [start, start + n) is the resident range (start = 0 for the form that takes rows), checked here only
+// for wrapping round -- whether it lies inside the resident queries is the handle's to say
+inline std::string exact_args_error(bool have_handle, bool have_queries, size_t start, size_t n, size_t k, const void* D, const void* I) {
+    const std::string w("exact search: ");
+    if (!have_handle) return w + "null handle";
+    if (k == 0) return w + "k must be positive";
+    if (start + n < start) return w + "resident query range out of bounds";
+    if (n && (!have_queries || !D || !I)) return w + "null argument";
+    return std::string();
+}
+
+// A candidate's sort key: the order key of its distance (smaller = better, whatever the metric) above its global position.
+EXACT_HD inline uint64_t exact_key(uint32_t dist_key, uint32_t position) { return ((uint64_t)dist_key << 32) | position; }
+
+// The tie rule.  sorted: a query's candidates -- every stored entry at or within its threshold -- as exact_key values in ascending
+// order, `count` of them (>= k: the threshold is the k-th distance of a search of the same lists).  The window that decides the
+// result is the best min(count, k + 1): with fewer than k + 1 candidates the (k + 1)-th best entry lies beyond the threshold and so
+// differs from the k-th.  True when two neighbours of the window have the same distance: then, and only then, the reference's result
+// depends on the order its heap met the entries in.  The pairs looked at are (i, i + 1) for i = first, first + step, ...: the host
+// passes (0, 1), a wave its lane and 64.
+EXACT_HD inline bool exact_window_tied(const uint64_t* sorted, size_t count, size_t k, size_t first = 0, size_t step = 1) {
+    const size_t window = count < k + 1 ? count : k + 1;
+    bool tied = false;
+    for (size_t i = first; i + 1 < window; i += step) tied |= (sorted[i] >> 32) == (sorted[i + 1] >> 32);
+    return tied;
+}
+
+}  // namespace amdivf

@@ -1318,6 +1318,23 @@ void IndexIVFFlat::search_selected(idx_t n, const float* x, idx_t k, float* dist
     AMD(amd_ivf_search_selected(g, sel_, (size_t)n, x, (size_t)k, nprobe, coarse_mode, distances, i64(labels)));
 }
 
+// ------------------------------------------------------------------------------------- IndexIVFFlat::search_exact
+void IndexIVFFlat::search_exact(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const {
+    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(this) == nullptr, "search_exact of an IndexIVFFlatDedup is not implemented");
+    FAISS_THROW_IF_NOT_MSG(!tune && !training && !(t && t->time_tune), "search_exact is the plain search only");
+    FAISS_THROW_IF_NOT_MSG(max_codes == 0, "search_exact with max_codes is not implemented");
+    amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
+    AMD(amd_ivf_search_exact(g, (size_t)n, x, (size_t)k, distances, i64(labels)));
+}
+
+void IndexIVFFlat::exact_info(uint64_t out[4]) const { AMD(amd_ivf_last_exact(engine(), out)); }
+
+void IndexIVFFlatSubset::search_exact(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const {
+    AMD(amd_ivf_search_exact(gpu_, (size_t)n, x, (size_t)k, distances, i64(labels)));
+}
+
+void IndexIVFFlatSubset::exact_info(uint64_t out[4]) const { AMD(amd_ivf_last_exact(gpu_, out)); }
+
 // ------------------------------------------------------------------------------------- IndexIVFFlatSubset
 void IndexIVFFlatSubset::cut(const IndexIVFFlat& src, int subset_type, idx_t a1, idx_t a2, const void* sel, size_t nsel) {
     FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(&src) == nullptr, "a subset of an IndexIVFFlatDedup is not implemented");

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/auncel_amd.h"
+#include "exact_args.h"
 #include "ivf_kernels.h"
 #include "kmeans_host.h"
 
@@ -52,6 +53,8 @@ struct EngineError : std::runtime_error {  // what the reference raises as Faiss
 constexpr double OPT_UNSET = -1e300;
 constexpr double ROW_LISTS_DEFAULT = -1;
 constexpr uint32_t CL_ARENA = 4u << 20;  // entries of CompactArgs::arena (32 MiB)
+constexpr double EXACT_SEED_DEFAULT = 16;   // amd_ivf_search_exact: nprobe of the seed search (the measured sweep)
+constexpr uint32_t EXACT_CAP_DEFAULT = 1024, EXACT_CAP_MAX = 4096;  // ... candidate slots per query (exact_select_kernel sorts them in LDS)
 enum OptId {
     OPT_COARSE_TIES,    // order inside runs of bit-equal coarse distances: 0 centroid number, 1 the reference's heap, 2 "redo"
                         // (search again the queries that read such a run); unset: heap for calls of < 20 queries, else 0
@@ -82,6 +85,7 @@ enum OptId {
                         // buffers) that one pass over the lists may serve together (1: every ticket its own pass)
     OPT_INCREMENTAL,    // changes of the lists between searches applied in HBM from a journal of the written entries (1, ivf_update.hip) or
                         // by sending every list again (0)
+    OPT_EXACT_SEED_NPROBE,  // amd_ivf_search_exact: nprobe of the seed search whose k-th distance is the list pass's threshold
     N_OPT
 };
 struct OptSpec {
@@ -109,6 +113,7 @@ const OptSpec OPT_TABLE[N_OPT] = {
     {"fp32_in_flight", "AUNCEL_AMD_FP32_IN_FLIGHT", nullptr},
     {"coalesce", "AUNCEL_AMD_COALESCE", nullptr},
     {"incremental", "AUNCEL_AMD_INCREMENTAL", nullptr},
+    {"exact_seed_nprobe", "AUNCEL_AMD_EXACT_SEED", nullptr},
 };
 struct Options {
     // (atomic: amd_ivf_set_option on the owner may run while search contexts cloned from it are searching; a search reads the
@@ -517,6 +522,10 @@ struct amd_ivf {
     const int64_t* given_keys = nullptr;
     const float* given_dis = nullptr;
     size_t given_nprobe = 0;
+    // amd_ivf_search_exact: per-block table of the fragment copy, the queries' candidate counters and buffers, the selection's flags
+    // and totals, its results, the rows and numbers of the queries that go the general way; the counts of the last call
+    DevBuf w_ex_blk, w_ex_cnt, w_ex_cand, w_ex_flag, w_ex_tot, w_ex_D, w_ex_I, w_ex_x, w_ex_idx;
+    uint64_t last_exact[4] = {0, 0, 0, 0};
     DevBuf w_limit;  // time-bounded search: per-slot end of the probe loop (plan_counts_kernel -> replay_kernel)
     DevBuf w_tie_rows;  // rankings re-run through the reference's heap because of equal distances (launch_heap_tie_order)
 
@@ -4721,6 +4730,7 @@ static double opt_default(OptId id) {
         case OPT_SCAN_PIPELINED: return 7;
         case OPT_FILTER: case OPT_COARSE_PICK: return 2;
         case OPT_ROW_LISTS: return ROW_LISTS_DEFAULT;
+        case OPT_EXACT_SEED_NPROBE: return EXACT_SEED_DEFAULT;
         default: return 1;
     }
 }
@@ -5798,6 +5808,239 @@ int amd_ivf_submit_search_resident_selected(amd_ivf_t* h, const amd_ivf_selector
     if (start + n > h->n_resident) throw EngineError("resident query range out of bounds");
     *ticket = async_enqueue(
         h, [=](amd_ivf_t* c) { return amd_ivf_search_resident_selected(c, s, start, n, k, nprobe, coarse_mode, D, I); }, nullptr, s);
+    API_END
+}
+
+}  // extern "C"
+
+// ============================================================================================
+// exact search over the whole index (kernels: ivf_exact.hip)
+// ============================================================================================
+namespace {
+
+// candidate slots per query: AUNCEL_AMD_EXACT_CAP (a test knob, read once per process), else the default
+uint32_t exact_cap() {
+    static const uint32_t v = [] {
+        const char* e = getenv("AUNCEL_AMD_EXACT_CAP");
+        const long x = e && *e ? atol(e) : 0;
+        return x >= 2 ? (uint32_t)std::min<long>(x, EXACT_CAP_MAX) : EXACT_CAP_DEFAULT;
+    }();
+    return v;
+}
+
+// The queries idx[0 .. m) of d_x (all n of them when idx is null) the general way: search_preassigned over every list in
+// list-number order, with the keys made on the device, in slices that keep the key table small; rows written to their places in
+// (D, I).  Returns the heap updates the slices made (the only part of an exact call the reference's admission count exists for).
+size_t exact_general(amd_ivf* h, const float* d_x, const uint32_t* idx, size_t m, size_t k, float* D, int64_t* I, const IntRange& qr) {
+    const size_t nlist = h->nlist;
+    const size_t slice = std::max<size_t>(1, std::min<size_t>(4096, ((size_t)4 << 20) / std::max<size_t>(nlist, 1)));
+    std::vector<float> tD;
+    std::vector<int64_t> tI;
+    size_t heap = 0;
+    for (size_t o = 0; o < m; o += slice) {
+        const size_t c = std::min(slice, m - o);
+        const float* rows = d_x + o * (size_t)h->dpad;
+        if (idx) {
+            h->w_ex_idx.ensure(c * 4);
+            h->w_ex_x.ensure(c * (size_t)h->dpad * sizeof(float));
+            HIP_CHECK(hipMemcpyAsync(h->w_ex_idx.p, idx + o, c * 4, hipMemcpyHostToDevice, h->stream));
+            launch_gather_rows(d_x, h->w_ex_idx.as<uint32_t>(), (uint32_t)c, (uint32_t)h->dpad, h->w_ex_x.as<float>(), h->stream);
+            HIP_CHECK(stream_sync(h->stream));  // (idx + o is the caller's pageable memory)
+            rows = h->w_ex_x.as<float>();
+        }
+        h->w_ckeys.ensure(c * nlist * 8);
+        launch_identity_keys(h->w_ckeys.as<int64_t>(), c, (uint32_t)nlist, h->stream);
+        const size_t before = h->stats_host[3];
+        if (!idx) {
+            search_fixed_device(h, rows, c, k, nlist, h->w_ckeys.as<int64_t>(), D + o * k, I + o * k, 0, 0, qr);
+        } else {
+            tD.resize(c * k);
+            tI.resize(c * k);
+            search_fixed_device(h, rows, c, k, nlist, h->w_ckeys.as<int64_t>(), tD.data(), tI.data(), 0, 0, qr);
+            for (size_t j = 0; j < c; j++) {
+                memcpy(D + (size_t)idx[o + j] * k, tD.data() + j * k, k * sizeof(float));
+                memcpy(I + (size_t)idx[o + j] * k, tI.data() + j * k, k * sizeof(int64_t));
+            }
+        }
+        heap += h->stats_host[3] - before;
+    }
+    return heap;
+}
+
+// one slice of an exact call: seed, list pass, selection, and the flagged queries the general way.  out: amd_ivf_last_exact's counts
+// (added to); returns the heap updates of the general-way part.
+size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int64_t* I, const IntRange& qr, uint64_t out[4]) {
+    amd_ivf* index = ix(h);
+    const size_t nlist = h->nlist;
+    const uint64_t ntotal = index->h_list_off.size() == nlist + 1 ? index->h_list_off[nlist] : 0;
+    const uint32_t cap = exact_cap();
+    const uint64_t nblk = index->h_block_off.size() == nlist + 1 ? index->h_block_off[nlist] : 0;
+    // the list pass runs on byte codes up to four K-steps, under the rule every byte scan runs under
+    const bool pass = index->have_codes8 && h->allow_bytes && index->have_centroids && h->d <= 128 && nblk > 0 && ntotal < 0xffffffffull &&
+                      index->db_range.bytes_with(qr, (size_t)h->d) && k < cap && k <= ntotal;
+    if (!pass) {
+        out[2] += n;
+        return exact_general(h, d_x, nullptr, n, k, D, I, qr);
+    }
+    // ---- 1. seed: an ordinary fixed-nprobe search; its k-th distance is a distance of k stored entries, so the true k-th is within it
+    const size_t seed = std::min<size_t>(nlist, (size_t)std::max(1.0, opt(h, OPT_EXACT_SEED_NPROBE, EXACT_SEED_DEFAULT)));
+    search_full(h, d_x, n, k, seed, -1, D, I, qr);
+    const float* seed_D = h->last_direct_out ? static_cast<const float*>(device_view(D)) : h->w_D.as<float>();
+    const int64_t* seed_I = h->last_direct_out ? static_cast<const int64_t*>(device_view(I)) : h->w_I.as<int64_t>();
+    if (!seed_D || !seed_I) throw std::runtime_error("exact search: the seed's result is not on the device");
+    // ---- 2. list pass
+    if (!byte_queries(h, index, d_x, n, qr)) throw std::runtime_error("exact search: no byte view of the queries");
+    hipStream_t s = h->stream;
+    h->w_ex_blk.ensure(nblk * sizeof(uint2));
+    h->w_ex_cnt.ensure(n * 4);
+    h->w_ex_cand.ensure(n * (size_t)cap * sizeof(uint2));
+    h->w_ex_flag.ensure(n * 4);
+    h->w_ex_tot.ensure(4 * 8);
+    h->w_ex_D.ensure(n * k * sizeof(float));
+    h->w_ex_I.ensure(n * k * sizeof(int64_t));
+    launch_exact_blocks(index->d_list_off.as<uint64_t>(), index->d_block_off.as<uint64_t>(), (uint32_t)nlist, nblk, h->w_ex_blk.as<uint2>(), s);
+    HIP_CHECK(hipMemsetAsync(h->w_ex_cnt.p, 0, n * 4, s));
+    HIP_CHECK(hipMemsetAsync(h->w_ex_tot.p, 0, 4 * 8, s));
+    ExactScanArgs sa{};
+    sa.codes_frag = index->d_frag.as<uint8_t>();
+    sa.code_cy = index->d_cy.as<int32_t>();
+    sa.blk = h->w_ex_blk.as<uint2>();
+    sa.nblk = nblk;
+    sa.slab = exact_slab_blocks(nblk, (uint32_t)n);
+    sa.queries8 = h->w_x8.as<int8_t>();
+    sa.query_cx = h->w_xnorm8.as<int32_t>();
+    sa.seed_D = seed_D;
+    sa.seed_I = seed_I;
+    sa.n = (uint32_t)n;
+    sa.k = (uint32_t)k;
+    sa.d = h->d;
+    sa.metric = h->metric;
+    sa.cnt = h->w_ex_cnt.as<uint32_t>();
+    sa.cand = h->w_ex_cand.as<uint2>();
+    sa.cap = cap;
+    static const bool timed = getenv("AUNCEL_AMD_EXACT_TIMING") != nullptr;  // (scripts/exact_timing.py: the stages' share of a call)
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (timed)
+        for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    if (timed) HIP_CHECK(hipEventRecord(ev[0], s));
+    launch_scan_all(sa, s);
+    if (timed) HIP_CHECK(hipEventRecord(ev[1], s));
+    // ---- 3. exact selection
+    ExactSelectArgs ea{};
+    ea.n = (uint32_t)n;
+    ea.k = (uint32_t)k;
+    ea.cap = cap;
+    ea.metric = h->metric;
+    ea.cnt = sa.cnt;
+    ea.cand = sa.cand;
+    ea.seed_I = seed_I;
+    ea.ids = index->d_ids.as<int64_t>();
+    ea.D = h->w_ex_D.as<float>();
+    ea.I = h->w_ex_I.as<int64_t>();
+    ea.flag = h->w_ex_flag.as<uint32_t>();
+    ea.totals = h->w_ex_tot.as<unsigned long long>();
+    launch_exact_select(ea, s);
+    if (timed) HIP_CHECK(hipEventRecord(ev[2], s));
+    std::vector<uint32_t> flag(n);
+    unsigned long long tot[4] = {0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(flag.data(), h->w_ex_flag.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(tot, h->w_ex_tot.p, sizeof tot, hipMemcpyDeviceToHost, s));
+    // (the rows of flagged queries are not written by the selection: the general way fills them below)
+    HIP_CHECK(hipMemcpyAsync(D, h->w_ex_D.p, n * k * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(I, h->w_ex_I.p, n * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(stream_sync(s));
+    if (timed) {
+        float a = 0, b = 0;
+        (void)hipEventElapsedTime(&a, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&b, ev[1], ev[2]);
+        fprintf(stderr, "[exact] n %zu k %zu seed %zu: pass %.3f ms, select %.3f ms\n", n, k, seed, a, b);
+        for (auto& e : ev) (void)hipEventDestroy(e);
+    }
+    for (int i = 0; i < 4; i++) out[i] += tot[i];
+    // ---- 4. the general way for the queries in which equal distances met (or that had no threshold, or too many candidates)
+    std::vector<uint32_t> redo;
+    for (size_t i = 0; i < n; i++)
+        if (flag[i]) redo.push_back((uint32_t)i);
+    if (redo.empty()) return 0;
+    return exact_general(h, d_x, redo.data(), redo.size(), k, D, I, qr);
+}
+
+void exact_core(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int64_t* I, const IntRange& qr) {
+    upload_lists(h);  // (a pending journal is applied first, as every search does)
+    amd_ivf* index = ix(h);
+    const size_t nlist = h->nlist;
+    const uint64_t ntotal = index->h_list_off.size() == nlist + 1 ? index->h_list_off[nlist] : 0;
+    size_t st[4];
+    for (int i = 0; i < 4; i++) st[i] = h->stats_host[i];
+    uint64_t out[4] = {0, 0, 0, 0};
+    size_t heap = 0;
+    if (ntotal == 0) {  // an empty index: the reference's padding for every query
+        std::fill(D, D + n * k, h->metric == METRIC_L2 ? FLT_MAX : -FLT_MAX);
+        std::fill(I, I + n * k, (int64_t)-1);
+        out[2] = n;
+    } else {
+        const size_t slice = 8192;  // (bounds the candidate buffers: slice x cap x 8 bytes)
+        for (size_t o = 0; o < n; o += slice) {
+            const size_t c = std::min(slice, n - o);
+            heap += exact_slice(h, d_x + o * (size_t)h->dpad, c, k, D + o * k, I + o * k, qr, out);
+        }
+    }
+    // the statistics of the call as the header states them: the seed searches leave no trace, the list pass has no admission count
+    h->stats_host[0] = st[0] + n;
+    h->stats_host[1] = st[1] + n * nlist;
+    h->stats_host[2] = st[2] + n * (size_t)ntotal;
+    h->stats_host[3] = st[3] + heap;
+    for (int i = 0; i < 4; i++) h->last_exact[i] = out[i];
+}
+
+// a usable device before the handle is read (without one: -4, as every call)
+void require_device() {
+    int count = 0;
+    HIP_CHECK(hipGetDeviceCount(&count));
+    if (count <= 0) throw std::runtime_error("no HIP device");
+}
+
+}  // namespace
+
+extern "C" {
+
+int amd_ivf_search_exact(amd_ivf_t* h, size_t n, const float* x, size_t k, float* D, int64_t* I) {
+    API_BEGIN
+    const std::string bad = exact_args_error(h != nullptr, x != nullptr, 0, n, k, D, I);
+    if (!bad.empty()) throw EngineError(bad);
+    require_device();
+    use_device(h);
+    for (int i = 0; i < 4; i++) h->last_exact[i] = 0;
+    if (n == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const QueryRows q = host_rows(h, x, n);
+    exact_core(h, q.d_x, n, k, D, I, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, float* D, int64_t* I) {
+    API_BEGIN
+    const std::string bad = exact_args_error(h != nullptr, true, start, n, k, D, I);
+    if (!bad.empty()) throw EngineError(bad);
+    require_device();
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    for (int i = 0; i < 4; i++) h->last_exact[i] = 0;
+    if (n == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    exact_core(h, q.d_x, n, k, D, I, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_last_exact(amd_ivf_t* h, uint64_t out[4]) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("null argument");
+    require_device();
+    for (int i = 0; i < 4; i++) out[i] = h->last_exact[i];
     API_END
 }
 

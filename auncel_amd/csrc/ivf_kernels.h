@@ -752,6 +752,44 @@ struct KeepArgs {
 };
 void launch_keep_rows(const KeepArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------- exact search over the whole index (ivf_exact.hip)
+// The list pass of amd_ivf_search_exact: every query against every 32-vector block of the byte fragments (d <= 128), candidates at or
+// within the query's threshold appended to the query's buffer.  seed_D / seed_I: the n x k result of a search of the same lists
+// (row q's last entry is the threshold; id < 0 there: the query has none and emits nothing).
+struct ExactScanArgs {
+    const uint8_t* codes_frag;    // lists in fragment order
+    const int32_t* code_cy;       // per stored slot
+    const uint2* blk;             // per block: (global position of its first slot, slots that hold an entry) -- launch_exact_blocks
+    uint64_t nblk;                // blocks of the copy (even)
+    uint32_t slab;                // consecutive blocks per workgroup (even)
+    const int8_t* queries8;       // signed query bytes, row stride ks * 32
+    const int32_t* query_cx;
+    const float* seed_D;
+    const int64_t* seed_I;
+    uint32_t n, k;
+    int d, metric;
+    uint32_t* cnt;                // [n] candidates of the query so far (zeroed by the caller); keeps counting beyond cap
+    uint2* cand;                  // [n][cap] (global position, distance bits)
+    uint32_t cap;
+};
+struct ExactSelectArgs {
+    uint32_t n, k, cap;
+    int metric;
+    const uint32_t* cnt;
+    const uint2* cand;
+    const int64_t* seed_I;
+    const int64_t* ids;           // per stored vector
+    float* D;                     // [n][k], written for the queries flagged 0
+    int64_t* I;
+    uint32_t* flag;               // [n] 0 answered, 1 equal distances met, 2 no threshold / more candidates than slots
+    unsigned long long* totals;   // [0..2] += queries by flag, [3] += candidates emitted (zeroed by the caller)
+};
+void launch_exact_blocks(const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, uint64_t nblk, uint2* out, hipStream_t s);
+void launch_identity_keys(int64_t* keys, size_t rows, uint32_t nlist, hipStream_t s);  // keys[i][l] = l
+uint32_t exact_slab_blocks(uint64_t nblk, uint32_t n);
+void launch_scan_all(const ExactScanArgs& a, hipStream_t s);
+void launch_exact_select(const ExactSelectArgs& a, hipStream_t s);
+
 inline uint32_t subset_range_key(float x) {
     uint32_t u;
     memcpy(&u, &x, 4);

@@ -194,6 +194,35 @@ int amd_ivf_search_preassigned(amd_ivf_t* h, size_t n, const float* x, size_t k,
 int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t nprobe, int coarse_mode, float* D,
                    int64_t* I);
 
+/* ---- exact k-NN over the whole index -----------------------------------------------------
+ * (D, I) are, bit for bit, what amd_ivf_search_preassigned(h, n, x, k, nprobe = nlist, keys, ..., store_pairs = 0, max_codes = 0)
+ * returns when every row of keys is 0, 1, ..., nlist - 1: the reference's search_preassigned over every list in list-number order
+ * [IndexIVF.cpp:382-736], padding included (k > ntotal, an empty index).  A pending amd_ivf_add / _update_lists / _remove_ids is
+ * applied first.  _resident: over resident queries [start, start + n) (amd_ivf_set_queries).  Both work on amd_ivf_clone contexts.
+ * How: the reference's heap admits an entry only if it strictly beats the top, so a query whose best
+ * min(k + 1, ntotal) distances are pairwise different ends with exactly the k best entries, sorted, whatever the scan order was.
+ * Byte-valued lists of d <= 128 (the rule of every byte scan, amd_ivf_scan_arith 2) are therefore searched in four stages: a seed
+ * search with a fixed nprobe (option "exact_seed_nprobe") gives each query a threshold, its k-th distance; ONE pass over all lists
+ * (scan_all_kernel: a list block is fetched once per 256 queries) emits each query's entries at or within its threshold; a
+ * selection orders them and writes the result of every query in which no equal distances met in that window; the other queries --
+ * and those without a full seed result or with more candidates than slots -- are searched the general way, as one sliced
+ * amd_ivf_search_preassigned with identity keys made on the device.  A call whose lists or queries do not qualify (float lists,
+ * d > 128, a query value outside the byte rule, byte codes switched off, k > ntotal) goes the general way whole.
+ * Returns -2 before the device is touched for: a null h, k = 0, null x / D / I with n > 0, a resident range that wraps round; -2 for
+ * a resident range outside the resident queries.
+ * amd_ivf_stats after the call: nq += n, nlist += n x nlist, ndis += n x ntotal -- every query meets every entry; nheap_updates
+ * changes only by what the general-way part of the call did: the list pass does not replay the reference's heap, so it has no
+ * admission count and does not invent one (the seed search leaves no trace in any of the four).
+ * amd_ivf_last_exact: out[0] queries of the last exact call answered by the list pass, out[1] queries searched the general way
+ * because equal distances met, out[2] queries searched the general way for any other reason (candidate overflow, no full seed
+ * result, the whole call not qualifying), out[3] candidates the list pass emitted, summed over the call.
+ * AUNCEL_AMD_EXACT_CAP=<n> (a test knob, read once per process): candidate slots per query, 2..4096 (default 1024).
+ * Not offered: a matrix-core exact pass for float lists (the fp16 filter's bound with rescoring: the next step), d > 128 in the
+ * pass, selectors, tickets, store_pairs / max_codes, the adaptive rule -- there is no exact entry point that takes any of them. */
+int amd_ivf_search_exact(amd_ivf_t* h, size_t n, const float* x, size_t k, float* D, int64_t* I);
+int amd_ivf_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, float* D, int64_t* I);
+int amd_ivf_last_exact(amd_ivf_t* h, uint64_t out[4]);
+
 /* InvertedListScanner: set_query + set_list + scan_codes on a caller-owned raw binary heap
  * (simi/idxi, k entries, heapified by the caller as in tests/test_lowlevel_ivf.cpp:150-175);
  * returns the number of heap updates in *nup  [IndexIVFFlat.cpp:101-137] */
@@ -526,6 +555,8 @@ int amd_ivf_set_byte_codes(amd_ivf_t* h, int enable);
  *                     an in-place relayout in HBM that re-encodes only the blocks they touched (1), or as a full
  *                     upload of every list (0); a journal that writes more than a quarter of the entries, or an
  *                     allocation that fails, takes the full upload either way
+ *   "exact_seed_nprobe"  amd_ivf_search_exact: nprobe of the seed search whose k-th distance is the list pass's     16
+ *                     threshold (at most nlist; AUNCEL_AMD_EXACT_SEED is the environment's form).  Cannot change a result
  * amd_ivf_set_option(h, key, NAN) returns the key to "unset".  May be called while search contexts of the index are searching: a
  * search reads what shapes its launches once, when it starts, so the change takes effect with the searches that start after it. */
 int amd_ivf_set_option(amd_ivf_t* h, const char* key, double value);
