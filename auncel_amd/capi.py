@@ -38,7 +38,7 @@ SYMBOLS = [
     "amd_ivf_search_selected", "amd_ivf_search_preassigned_selected", "amd_ivf_search_resident_selected",
     "amd_ivf_selector_combine", "amd_ivf_range_search_selected", "amd_ivf_range_search_preassigned_selected",
     "amd_ivf_submit_search_resident_selected",
-    "amd_ivf_search_exact", "amd_ivf_search_exact_resident", "amd_ivf_last_exact",
+    "amd_ivf_search_exact", "amd_ivf_search_exact_resident", "amd_ivf_last_exact", "amd_ivf_last_exact_detail",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -534,6 +534,13 @@ class Handle:
         candidates the list pass emitted) of the last exact call"""
         out = (C.c_uint64 * 4)()
         _chk(lib().amd_ivf_last_exact(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def last_exact_detail(self):
+        """(which list pass the last exact call ran: 0 none, 1 bytes, 2 fp16 + rescoring; candidates emitted; candidates at or within
+        the threshold after rescoring; the largest emitted count of one query)"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_last_exact_detail(self._h, out))
         return tuple(int(v) for v in out)
 
     def range_search(self, x, radius, nprobe, keys=None, coarse_mode=0):

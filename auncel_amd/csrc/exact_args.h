@@ -1,7 +1,8 @@
 // The host side of the exact search over the whole index (include/auncel_amd.h: amd_ivf_search_exact): what the entry points refuse
 // before anything touches a device, and the one rule that says when a query's result can be read off its sorted candidates (DESIGN.md
-// 13).  Plain C++, nothing of the device in it: exact_select_kernel (ivf_exact.hip) and the host read the same definition, and it
-// builds on its own (tests/cpp/exact_args_main.cpp runs it under the address and undefined-behaviour sanitizers).
+// 13), and the keep rule of the fp16 list pass over float lists.  Plain C++, nothing of the device in it: the kernels of ivf_exact.hip
+// and the host read the same definitions, and it builds on its own (tests/cpp/exact_args_main.cpp and exact_float_main.cpp, which
+// are what the address and undefined-behaviour sanitizers are pointed at).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -41,6 +42,26 @@ EXACT_HD inline bool exact_window_tied(const uint64_t* sorted, size_t count, siz
     bool tied = false;
     for (size_t i = first; i + 1 < window; i += step) tied |= (sorted[i] >> 32) == (sorted[i + 1] >> 32);
     return tied;
+}
+
+// The keep rule of the fp16 list pass over float lists (scan_all_f16_kernel; the bound is ivf_filter.hip's, the argument for the
+// non-strict comparison DESIGN.md 13).  p = the fp16 matrix-core dot product brought back to the operands' scale, xn / yn = |x|^2,
+// |y|^2 (L2) or |x|, |y| (IP) accumulated in double and rounded once, tau = the query's threshold, a reference distance.  Every stored
+// entry whose reference distance r satisfies r <= tau (L2) / r >= tau (IP) is kept, the all-zero pair included; what else is kept is
+// weeded out by the rescoring.
+// The constant: (2 d + 32) 2^-24 for the fp32 roundings on either side, + 2^-10 + 2^-12 for the operands' rounding to fp16 unless every
+// element of both matrices is an integer of magnitude <= 2048 (fp16 holds those as they are).
+EXACT_HD inline float exact_float_constant(int d, bool operands_exact) {
+    const float C = (float)(2 * d + 32) * 5.9604644775390625e-08f;
+    return operands_exact ? C : C + 0.0009765625f + 0.000244140625f;
+}
+// per query: what the entry's side of the test is compared with, and (IP) the factor of |y|
+EXACT_HD inline float exact_float_bound(bool l2, float C, float xn, float tau) { return l2 ? (1.f - C) * xn - tau : tau; }
+EXACT_HD inline float exact_float_slack(bool l2, float C, float xn) { return l2 ? 0.f : C * xn; }
+// per pair: L2 keeps iff 2 p - (1 - C) yn >= (1 - C) xn - tau, IP iff p + C |x| |y| >= tau
+EXACT_HD inline bool exact_float_keep(bool l2, float C, float p, float yn, float bound, float slack) {
+    const float t = l2 ? __builtin_fmaf(2.f, p, -((1.f - C) * yn)) : __builtin_fmaf(slack, yn, p);
+    return t >= bound;
 }
 
 }  // namespace amdivf

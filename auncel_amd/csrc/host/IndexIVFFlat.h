@@ -34,9 +34,11 @@ struct IndexIVFFlat : IndexIVF {
     /// exact top-k over every list, on the lists that are resident on the device (include/auncel_amd.h: amd_ivf_search_exact): bit for
     /// bit search_preassigned with every row of `assign` = 0 .. nlist - 1, from one pass over the lists for all queries where the
     /// lists hold bytes (d <= 128).  The plain search only (not tune / training / time_tune, no max_codes); not for an
-    /// IndexIVFFlatDedup.  exact_info: the four counts of the last call (amd_ivf_last_exact).
+    /// IndexIVFFlatDedup.  exact_info: the four counts of the last call (amd_ivf_last_exact); exact_detail: which list pass it ran
+    /// and its candidate counts (amd_ivf_last_exact_detail).
     void search_exact(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const;
     void exact_info(uint64_t out[4]) const;
+    void exact_detail(uint64_t out[4]) const;
     IndexIVFFlat(const IndexIVFFlat&) = delete;
     IndexIVFFlat& operator=(const IndexIVFFlat&) = delete;
     ~IndexIVFFlat() override;
@@ -94,9 +96,10 @@ struct IndexIVFFlatSubset : Index {
     void reset() override;
     void search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const override;
     void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result) const override;
-    /// IndexIVFFlat::search_exact / exact_info over the subset's own lists
+    /// IndexIVFFlat::search_exact / exact_info / exact_detail over the subset's own lists
     void search_exact(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const;
     void exact_info(uint64_t out[4]) const;
+    void exact_detail(uint64_t out[4]) const;
     bool device_bound() const override { return true; }
     amd_ivf* engine() const { return gpu_; }
 

@@ -1328,12 +1328,14 @@ void IndexIVFFlat::search_exact(idx_t n, const float* x, idx_t k, float* distanc
 }
 
 void IndexIVFFlat::exact_info(uint64_t out[4]) const { AMD(amd_ivf_last_exact(engine(), out)); }
+void IndexIVFFlat::exact_detail(uint64_t out[4]) const { AMD(amd_ivf_last_exact_detail(engine(), out)); }
 
 void IndexIVFFlatSubset::search_exact(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const {
     AMD(amd_ivf_search_exact(gpu_, (size_t)n, x, (size_t)k, distances, i64(labels)));
 }
 
 void IndexIVFFlatSubset::exact_info(uint64_t out[4]) const { AMD(amd_ivf_last_exact(gpu_, out)); }
+void IndexIVFFlatSubset::exact_detail(uint64_t out[4]) const { AMD(amd_ivf_last_exact_detail(gpu_, out)); }
 
 // ------------------------------------------------------------------------------------- IndexIVFFlatSubset
 void IndexIVFFlatSubset::cut(const IndexIVFFlat& src, int subset_type, idx_t a1, idx_t a2, const void* sel, size_t nsel) {

@@ -86,6 +86,7 @@ enum OptId {
     OPT_INCREMENTAL,    // changes of the lists between searches applied in HBM from a journal of the written entries (1, ivf_update.hip) or
                         // by sending every list again (0)
     OPT_EXACT_SEED_NPROBE,  // amd_ivf_search_exact: nprobe of the seed search whose k-th distance is the list pass's threshold
+    OPT_EXACT_FLOAT,        // amd_ivf_search_exact over float lists: 1 the fp16 matrix-core list pass + rescoring, 0 (the default) the general way
     N_OPT
 };
 struct OptSpec {
@@ -114,6 +115,7 @@ const OptSpec OPT_TABLE[N_OPT] = {
     {"coalesce", "AUNCEL_AMD_COALESCE", nullptr},
     {"incremental", "AUNCEL_AMD_INCREMENTAL", nullptr},
     {"exact_seed_nprobe", "AUNCEL_AMD_EXACT_SEED", nullptr},
+    {"exact_float", "AUNCEL_AMD_EXACT_FLOAT", nullptr},
 };
 struct Options {
     // (atomic: amd_ivf_set_option on the owner may run while search contexts cloned from it are searching; a search reads the
@@ -526,6 +528,7 @@ struct amd_ivf {
     // and totals, its results, the rows and numbers of the queries that go the general way; the counts of the last call
     DevBuf w_ex_blk, w_ex_cnt, w_ex_cand, w_ex_flag, w_ex_tot, w_ex_D, w_ex_I, w_ex_x, w_ex_idx;
     uint64_t last_exact[4] = {0, 0, 0, 0};
+    uint64_t last_exact_detail[4] = {0, 0, 0, 0};  // amd_ivf_last_exact_detail: pass kind, emitted, within the threshold, largest per query
     DevBuf w_limit;  // time-bounded search: per-slot end of the probe loop (plan_counts_kernel -> replay_kernel)
     DevBuf w_tie_rows;  // rankings re-run through the reference's heap because of equal distances (launch_heap_tie_order)
 
@@ -4725,7 +4728,7 @@ static int opt_id(const char* key) {
 static double opt_default(OptId id) {
     switch (id) {
         case OPT_COARSE_TIES: case OPT_TIE_FIX: case OPT_PHASE_TIMING: return -1;
-        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: return 0;  // (0: chosen per search)
+        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: case OPT_EXACT_FLOAT: return 0;  // (0: chosen per search)
         case OPT_ROUND_FIRST: return 12;
         case OPT_SCAN_PIPELINED: return 7;
         case OPT_FILTER: case OPT_COARSE_PICK: return 2;
@@ -5876,9 +5879,23 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     const uint32_t cap = exact_cap();
     const uint64_t nblk = index->h_block_off.size() == nlist + 1 ? index->h_block_off[nlist] : 0;
     // the list pass runs on byte codes up to four K-steps, under the rule every byte scan runs under
-    const bool pass = index->have_codes8 && h->allow_bytes && index->have_centroids && h->d <= 128 && nblk > 0 && ntotal < 0xffffffffull &&
-                      index->db_range.bytes_with(qr, (size_t)h->d) && k < cap && k <= ntotal;
-    if (!pass) {
+    const bool shape_ok = index->have_centroids && h->d <= 128 && nblk > 0 && ntotal < 0xffffffffull && k < cap && k <= ntotal;
+    const bool bytes = index->have_codes8 && h->allow_bytes && index->db_range.bytes_with(qr, (size_t)h->d);
+    const bool pass = shape_ok && bytes;
+    // ... and on the filter's fp16 copy of float lists, where lists and queries have a usable scale (ivf_filter.hip: no non-finite
+    // element, magnitudes within 2^+-24, no row tiny beside the largest -- which also keeps every reference distance finite)
+    hipStream_t s = h->stream;
+    bool pass16 = !pass && shape_ok && filter_available(h, index, bytes) && opt(h, OPT_EXACT_FLOAT, 0) != 0 && ensure_frag16(index);
+    if (pass16) {
+        uint32_t info[4] = {0, 0, 0, 0};
+        h->w_qinfo.ensure(16);
+        HIP_CHECK(hipMemsetAsync(h->w_qinfo.p, 0, 16, s));
+        launch_amax(d_x, n, h->dpad, h->w_qinfo.as<uint32_t>(), s);
+        HIP_CHECK(hipMemcpyAsync(info, h->w_qinfo.p, 16, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(stream_sync(s));
+        pass16 = filter_half_scale(info, h->d) != 0.f;
+    }
+    if (!pass && !pass16) {
         out[2] += n;
         return exact_general(h, d_x, nullptr, n, k, D, I, qr);
     }
@@ -5889,18 +5906,17 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     const int64_t* seed_I = h->last_direct_out ? static_cast<const int64_t*>(device_view(I)) : h->w_I.as<int64_t>();
     if (!seed_D || !seed_I) throw std::runtime_error("exact search: the seed's result is not on the device");
     // ---- 2. list pass
-    if (!byte_queries(h, index, d_x, n, qr)) throw std::runtime_error("exact search: no byte view of the queries");
-    hipStream_t s = h->stream;
+    if (pass && !byte_queries(h, index, d_x, n, qr)) throw std::runtime_error("exact search: no byte view of the queries");
     h->w_ex_blk.ensure(nblk * sizeof(uint2));
     h->w_ex_cnt.ensure(n * 4);
     h->w_ex_cand.ensure(n * (size_t)cap * sizeof(uint2));
     h->w_ex_flag.ensure(n * 4);
-    h->w_ex_tot.ensure(4 * 8);
+    h->w_ex_tot.ensure(6 * 8);
     h->w_ex_D.ensure(n * k * sizeof(float));
     h->w_ex_I.ensure(n * k * sizeof(int64_t));
     launch_exact_blocks(index->d_list_off.as<uint64_t>(), index->d_block_off.as<uint64_t>(), (uint32_t)nlist, nblk, h->w_ex_blk.as<uint2>(), s);
     HIP_CHECK(hipMemsetAsync(h->w_ex_cnt.p, 0, n * 4, s));
-    HIP_CHECK(hipMemsetAsync(h->w_ex_tot.p, 0, 4 * 8, s));
+    HIP_CHECK(hipMemsetAsync(h->w_ex_tot.p, 0, 6 * 8, s));
     ExactScanArgs sa{};
     sa.codes_frag = index->d_frag.as<uint8_t>();
     sa.code_cy = index->d_cy.as<int32_t>();
@@ -5922,8 +5938,49 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (timed)
         for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-    if (timed) HIP_CHECK(hipEventRecord(ev[0], s));
-    launch_scan_all(sa, s);
+    if (pass) {
+        if (timed) HIP_CHECK(hipEventRecord(ev[0], s));
+        launch_scan_all(sa, s);
+    } else {
+        // the fp16 query operands and FilterParams by the filter's own launches (the seed search may have left them; not every seed does)
+        h->w_xf.ensure(n * (size_t)filter_steps(h->d) * 8 * sizeof(float));
+        h->w_xn.ensure(n * sizeof(float));
+        h->w_fparams.ensure(2 * sizeof(FilterParams));
+        HIP_CHECK(hipMemsetAsync(h->w_qinfo.p, 0, 16, s));
+        launch_amax(d_x, n, h->dpad, h->w_qinfo.as<uint32_t>(), s);
+        launch_filter_queries16(d_x, n, h->d, h->dpad, h->metric, h->w_qinfo.as<uint32_t>(), index->d_yinfo.as<uint32_t>(), h->w_xf.as<float>(),
+                                h->w_xn.as<float>(), h->w_fparams.as<FilterParams>(), s);
+        ExactScanF16Args fa{};
+        fa.codes_frag = index->d_frag16.as<float>();
+        fa.yn = index->d_yn.as<float>();
+        fa.blk = sa.blk;
+        fa.nblk = nblk;
+        fa.slab = sa.slab;
+        fa.xf = h->w_xf.as<float>();
+        fa.xn = h->w_xn.as<float>();
+        fa.params = h->w_fparams.as<FilterParams>();
+        fa.seed_D = seed_D;
+        fa.seed_I = seed_I;
+        fa.n = (uint32_t)n;
+        fa.k = (uint32_t)k;
+        fa.d = h->d;
+        fa.metric = h->metric;
+        fa.cnt = sa.cnt;
+        fa.cand = sa.cand;
+        fa.cap = cap;
+        if (timed) HIP_CHECK(hipEventRecord(ev[0], s));
+        launch_scan_all_f16(fa, s);
+        ExactRescoreArgs ra{};
+        ra.n = (uint32_t)n;
+        ra.cap = cap;
+        ra.dpad = h->dpad;
+        ra.metric = h->metric;
+        ra.cnt = sa.cnt;
+        ra.cand = sa.cand;
+        ra.queries = d_x;
+        ra.codes = index->d_codes.as<float>();
+        launch_exact_rescore(ra, s);
+    }
     if (timed) HIP_CHECK(hipEventRecord(ev[1], s));
     // ---- 3. exact selection
     ExactSelectArgs ea{};
@@ -5931,6 +5988,8 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     ea.k = (uint32_t)k;
     ea.cap = cap;
     ea.metric = h->metric;
+    ea.rescored = pass ? 0 : 1;
+    ea.seed_D = seed_D;
     ea.cnt = sa.cnt;
     ea.cand = sa.cand;
     ea.seed_I = seed_I;
@@ -5942,7 +6001,7 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     launch_exact_select(ea, s);
     if (timed) HIP_CHECK(hipEventRecord(ev[2], s));
     std::vector<uint32_t> flag(n);
-    unsigned long long tot[4] = {0, 0, 0, 0};
+    unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};
     HIP_CHECK(hipMemcpyAsync(flag.data(), h->w_ex_flag.p, n * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(tot, h->w_ex_tot.p, sizeof tot, hipMemcpyDeviceToHost, s));
     // (the rows of flagged queries are not written by the selection: the general way fills them below)
@@ -5953,10 +6012,14 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         float a = 0, b = 0;
         (void)hipEventElapsedTime(&a, ev[0], ev[1]);
         (void)hipEventElapsedTime(&b, ev[1], ev[2]);
-        fprintf(stderr, "[exact] n %zu k %zu seed %zu: pass %.3f ms, select %.3f ms\n", n, k, seed, a, b);
+        fprintf(stderr, "[exact] n %zu k %zu seed %zu: pass%s %.3f ms, select %.3f ms\n", n, k, seed, pass ? "" : " (fp16 + rescoring)", a, b);
         for (auto& e : ev) (void)hipEventDestroy(e);
     }
     for (int i = 0; i < 4; i++) out[i] += tot[i];
+    h->last_exact_detail[0] = std::max<uint64_t>(h->last_exact_detail[0], pass ? 1 : 2);
+    h->last_exact_detail[1] += tot[3];
+    h->last_exact_detail[2] += tot[4];
+    h->last_exact_detail[3] = std::max<uint64_t>(h->last_exact_detail[3], tot[5]);
     // ---- 4. the general way for the queries in which equal distances met (or that had no threshold, or too many candidates)
     std::vector<uint32_t> redo;
     for (size_t i = 0; i < n; i++)
@@ -6010,7 +6073,7 @@ int amd_ivf_search_exact(amd_ivf_t* h, size_t n, const float* x, size_t k, float
     if (!bad.empty()) throw EngineError(bad);
     require_device();
     use_device(h);
-    for (int i = 0; i < 4; i++) h->last_exact[i] = 0;
+    for (int i = 0; i < 4; i++) h->last_exact[i] = h->last_exact_detail[i] = 0;
     if (n == 0) return 0;
     WallClock wc(h->stream);
     reset_scan_counters(h);
@@ -6027,7 +6090,7 @@ int amd_ivf_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, size_t k
     require_device();
     use_device(h);
     const QueryRows q = resident_rows(h, start, n);
-    for (int i = 0; i < 4; i++) h->last_exact[i] = 0;
+    for (int i = 0; i < 4; i++) h->last_exact[i] = h->last_exact_detail[i] = 0;
     if (n == 0) return 0;
     WallClock wc(h->stream);
     reset_scan_counters(h);
@@ -6041,6 +6104,14 @@ int amd_ivf_last_exact(amd_ivf_t* h, uint64_t out[4]) {
     if (!h || !out) throw EngineError("null argument");
     require_device();
     for (int i = 0; i < 4; i++) out[i] = h->last_exact[i];
+    API_END
+}
+
+int amd_ivf_last_exact_detail(amd_ivf_t* h, uint64_t out[4]) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("null argument");
+    require_device();
+    for (int i = 0; i < 4; i++) out[i] = h->last_exact_detail[i];
     API_END
 }
 

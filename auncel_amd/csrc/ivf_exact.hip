@@ -21,6 +21,9 @@ namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 
 // per 32-vector block of the fragment copy: (global position of its first slot, slots that hold an entry).  A list is padded to an
 // even number of blocks: the block in which a list ends holds fewer than 32 entries, the padding block behind it none.
@@ -193,25 +196,194 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
     }
 }
 
+// The list pass over float lists: the same grid, slabs, query tiles and block stream, on the fp16 copy the filter keeps (ivf_filter.hip:
+// a block is NJ pieces of 1 KiB, 16 dimensions each, in the operand order of v_mfma_f32_32x32x16_f16; the query rows are
+// filter_queries16_kernel's).  Wave w holds the A operands of its two query blocks -- NJ pieces of four registers each -- for the
+// whole slab, two list blocks are in flight, no workgroup barrier.  An accumulator times ps is x.y up to the filter's bound, and the
+// keep rule is exact_args.h's exact_float_keep, NON-strict: every stored entry whose reference distance is at or within the query's
+// threshold is emitted, with others the bound lets through; exact_rescore_kernel computes the reference's value of
+// each and the selection drops what lies beyond the threshold.  Emitted: (global position, -).
+// Registers (hipcc -O3, gfx950, --save-temps): NJ = 8 is the largest form, 2 x 32 operand registers of the queries, 2 x 32 of the
+// blocks in flight, 2 x 16 accumulators; no instantiation uses scratch (DESIGN.md 13 has the table).
+template <int METRIC, int NJ>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_all_f16_kernel(ExactScanF16Args a) {
+    static_assert(NJ == 4 || NJ == 6 || NJ == 8, "the piece counts of filter_steps16 up to 128 dimensions");
+    constexpr bool L2 = METRIC == METRIC_L2;
+    __shared__ float s_u[4][64];
+    __shared__ float s_c[4][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int m = lane & 31, h = lane >> 5;
+    constexpr size_t qstride = (size_t)NJ * 8;      // floats of a query row (16 NJ halves)
+    constexpr size_t block_floats = (size_t)NJ * 256;
+    const uint32_t qbase = blockIdx.y * 256u + (uint32_t)wave * 64u;
+    if (qbase >= a.n) return;
+    const uint32_t nq = a.n - qbase < 64u ? a.n - qbase : 64u;  // query slots of this wave that hold a query
+    const bool two = nq > 32;                                  // (wave-uniform)
+    const uint64_t B0 = (uint64_t)blockIdx.x * a.slab;
+    const uint64_t B1 = B0 + a.slab < a.nblk ? B0 + a.slab : a.nblk;  // (slab and nblk are even)
+    if (B0 >= B1) return;
+    const FilterParams fp = *a.params;
+    const float C = fp.C, ps = fp.ps;
+
+    // ---- per query slot (slot = lane): what the keep rule compares with; +inf where nothing may pass (no query, no threshold)
+    {
+        const bool sok = (uint32_t)lane < nq;
+        const uint32_t q = qbase + (sok ? (uint32_t)lane : 0u);
+        const size_t last = (size_t)q * a.k + (a.k - 1);
+        const float tau = a.seed_D[last], xn = a.xn[q];
+        const bool have = sok && a.seed_I[last] >= 0 && tau == tau;
+        s_u[wave][lane] = have ? exact_float_bound(L2, C, xn, tau) : __builtin_inff();
+        s_c[wave][lane] = exact_float_slack(L2, C, xn);
+    }
+    // ---- the A operands: lane (m, h) of query block g holds halves 16 j + 8 h .. + 7 of query slot 32 g + m, piece j
+    v4f af0[NJ], af1[NJ];
+    {
+        const bool qok0 = (uint32_t)m < nq, qok1 = (uint32_t)(32 + m) < nq;
+        const float* q0p = a.xf + (size_t)(qbase + (qok0 ? (uint32_t)m : 0u)) * qstride + (size_t)h * 4;
+        const float* q1p = a.xf + (size_t)(qbase + (qok1 ? 32u + (uint32_t)m : 0u)) * qstride + (size_t)h * 4;
+#pragma unroll
+        for (int j = 0; j < NJ; j++) af0[j] = qok0 ? *reinterpret_cast<const v4f*>(q0p + 8 * j) : v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < NJ; j++) af1[j] = qok1 ? *reinterpret_cast<const v4f*>(q1p + 8 * j) : v4f{0.f, 0.f, 0.f, 0.f};
+    }
+    wave_sync();
+
+    // ---- the block stream: two blocks in flight per wave, block i + 2 requested right behind the MFMAs of block i
+    v4f b0[NJ], b1[NJ];
+    float yn0 = 0.f, yn1 = 0.f;
+    uint2 bi0 = make_uint2(0, 0), bi1 = make_uint2(0, 0);
+    auto fetch = [&](v4f (&b)[NJ], float& yn, uint2& bi, uint64_t blk) {
+        const float* bp = a.codes_frag + blk * block_floats + (size_t)lane * 4;
+#pragma unroll
+        for (int j = 0; j < NJ; j++) b[j] = *reinterpret_cast<const v4f*>(bp + (size_t)j * 256);
+        yn = a.yn[blk * 32 + m];
+        bi = a.blk[blk];
+    };
+    fetch(b0, yn0, bi0, B0);
+    fetch(b1, yn1, bi1, B0 + 1);
+
+    auto step = [&](v4f (&b)[NJ], float& ynv, uint2& biv, uint64_t i) {
+        __builtin_amdgcn_sched_barrier(0);
+        v16f acc0, acc1;
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc0[r] = acc1[r] = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; j++)
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, af0[j]), __builtin_bit_cast(v8h, b[j]), acc0, 0, 0, 0);
+        if (two) {
+#pragma unroll
+            for (int j = 0; j < NJ; j++)
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, af1[j]), __builtin_bit_cast(v8h, b[j]), acc1, 0, 0, 0);
+        }
+        // what the epilogue needs of the block's constants is taken before their registers are requested again
+        const bool vok = (uint32_t)m < biv.y;  // (a slot behind the list's end emits nothing)
+        uint32_t pos = biv.x + (uint32_t)m;
+        float yn;
+        asm volatile("v_mov_b32 %0, %1" : "=v"(yn) : "v"(ynv));
+        asm volatile("" : "+v"(pos));
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(b, ynv, biv, i + 2 < B1 ? i + 2 : i);  // (past the slab's end: its own block again, never used)
+        __builtin_amdgcn_sched_barrier(0);
+        auto epilogue = [&](const v16f& acc, auto QB) {
+            constexpr int qb = decltype(QB)::value;
+            static_for(std::make_integer_sequence<int, 4>{}, [&](auto G) {
+                constexpr int g = decltype(G)::value;
+                // register 4 g + c of lane half h belongs to query slot qb + 8 g + 4 h + c: four registers at a time, most hold nothing
+                const v4f tu = *reinterpret_cast<const v4f*>(&s_u[wave][qb + 8 * g + 4 * h]);
+                const v4f tc = *reinterpret_cast<const v4f*>(&s_c[wave][qb + 8 * g + 4 * h]);
+                bool keep[4];
+                bool any = false;
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    keep[c] = vok && exact_float_keep(L2, C, ps * acc[4 * g + c], yn, tu[c], tc[c]);  // (ps: a power of two, exact)
+                    any |= keep[c];
+                }
+                if (__ballot(any) == 0) return;
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    const int sl = qb + 8 * g + 4 * h + c;
+                    if (keep[c] && (uint32_t)sl < nq) {
+                        const uint32_t q = qbase + (uint32_t)sl;
+                        const uint32_t slot = atomicAdd(&a.cnt[q], 1u);  // (beyond cap only the counter moves)
+                        if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = make_uint2(pos, 0u);
+                    }
+                }
+            });
+        };
+        epilogue(acc0, std::integral_constant<int, 0>{});
+        if (two) epilogue(acc1, std::integral_constant<int, 32>{});
+    };
+    for (uint64_t i = B0; i < B1; i += 2) {
+        step(b0, yn0, bi0, i);
+        step(b1, yn1, bi1, i + 1);
+    }
+}
+
+// The candidates of the fp16 pass recomputed from the fp32 rows in the reference's rounding sequence (ivf_dev.h: exact_distance; as in
+// rescore_kernel four neighbouring lanes take one candidate, lane l running sum l, then (s0 + s1) + (s2 + s3)): the distance's bits
+// replace the candidate's second word.  A workgroup per query, 64 candidates a trip.
+template <int METRIC> __global__ __launch_bounds__(256) void exact_rescore_kernel(ExactRescoreArgs a) {
+    const uint32_t q = blockIdx.x;
+    const uint32_t n = a.cnt[q] < a.cap ? a.cnt[q] : a.cap;
+    const uint32_t sub = threadIdx.x & 3;
+    const float* x = a.queries + (size_t)q * a.dpad;
+    for (uint32_t i = threadIdx.x >> 2; i < n; i += 64) {
+        uint2* slot = a.cand + (size_t)q * a.cap + i;
+        const float* y = a.codes + (size_t)slot->x * a.dpad;
+        float sl = 0.f;
+        for (int c = (int)sub; c < a.dpad; c += 4) {
+            if (METRIC == METRIC_L2) {
+                const float t = y[c] - x[c];
+                sl += t * t;
+            } else {
+                sl += y[c] * x[c];
+            }
+        }
+        const float pair = sl + __shfl_xor(sl, 1);    // lanes 0/1: s0 + s1, lanes 2/3: s2 + s3
+        const float ex = pair + __shfl_xor(pair, 2);  // (s0 + s1) + (s2 + s3)
+        if (sub == 0) slot->y = __float_as_uint(ex);
+    }
+}
+
 // A wave per query: its candidates sorted by (distance, global position) in LDS (a bitonic network over the next power of two), then
 // the tie rule.  flag[q]: 0 the result was written, 1 equal distances met in the window, 2 anything else (no threshold: the seed's
-// result was not full; more candidates than slots).  totals: [0..2] queries by flag, [3] candidates emitted.
-__global__ __launch_bounds__(64) void exact_select_kernel(ExactSelectArgs a) {
+// result was not full; more candidates than slots).  totals: [0..2] queries by flag, [3] candidates emitted, [4] candidates at or
+// within the threshold, [5] the largest emitted count of one query.
+// RESCORED (the fp16 pass): a candidate's distance is the reference's value, recomputed; one that lies strictly beyond the threshold
+// was let through by the bound only -- its key is the largest there is, so it sorts behind every other, and it is not counted: the
+// window and the test for "fewer than k" see the VALID candidates.  The keys are the distances' bit patterns through fkey, an order
+// only without NaN and -0: neither occurs.
+template <bool RESCORED> __global__ __launch_bounds__(64) void exact_select_kernel(ExactSelectArgs a) {
     extern __shared__ unsigned long long s_key[];
     const uint32_t q = blockIdx.x;
     const uint32_t lane = threadIdx.x;
-    const uint32_t cnt = a.cnt[q], k = a.k;
+    const uint32_t emitted = a.cnt[q], k = a.k;
     const bool have = a.seed_I[(size_t)q * k + (k - 1)] >= 0;
-    uint32_t flag = (!have || cnt > a.cap || cnt < k) ? 2u : 0u;  // (wave-uniform)
+    uint32_t cnt = emitted;  // the valid candidates
+    if (RESCORED) {
+        const uint32_t stored = emitted < a.cap ? emitted : a.cap;
+        const float tau = a.seed_D[(size_t)q * k + (k - 1)];
+        uint32_t mine = 0;
+        if (have)
+            for (uint32_t i = lane; i < stored; i += 64) {
+                const float dis = __uint_as_float(a.cand[(size_t)q * a.cap + i].y);
+                mine += a.metric == METRIC_L2 ? dis <= tau : dis >= tau;
+            }
+        cnt = wave_sum_u32(mine);
+    }
+    uint32_t flag = (!have || emitted > a.cap || cnt < k) ? 2u : 0u;  // (wave-uniform)
     if (!flag) {
         uint32_t P = 2;
-        while (P < cnt) P <<= 1;
+        while (P < emitted) P <<= 1;
+        const float tau = RESCORED ? a.seed_D[(size_t)q * k + (k - 1)] : 0.f;
         for (uint32_t i = lane; i < P; i += 64) {
             unsigned long long key = ~0ull;
-            if (i < cnt) {
+            if (i < emitted) {
                 const uint2 c = a.cand[(size_t)q * a.cap + i];
-                const uint32_t fk = fkey(__uint_as_float(c.y));
-                key = exact_key(a.metric == METRIC_L2 ? fk : ~fk, c.x);
+                const float dis = __uint_as_float(c.y);
+                const uint32_t fk = fkey(dis);
+                if (!RESCORED || (a.metric == METRIC_L2 ? dis <= tau : dis >= tau)) key = exact_key(a.metric == METRIC_L2 ? fk : ~fk, c.x);
             }
             s_key[i] = key;
         }
@@ -245,7 +417,9 @@ __global__ __launch_bounds__(64) void exact_select_kernel(ExactSelectArgs a) {
     if (lane == 0) {
         a.flag[q] = flag;
         atomicAdd(&a.totals[flag], 1ull);
-        atomicAdd(&a.totals[3], (unsigned long long)cnt);
+        atomicAdd(&a.totals[3], (unsigned long long)emitted);
+        atomicAdd(&a.totals[4], (unsigned long long)cnt);
+        atomicMax(&a.totals[5], (unsigned long long)emitted);
     }
 }
 
@@ -293,11 +467,38 @@ void launch_scan_all(const ExactScanArgs& a, hipStream_t s) {
     }
 }
 
+void launch_scan_all_f16(const ExactScanF16Args& a, hipStream_t s) {
+    if (a.n == 0 || a.nblk == 0) return;
+    const int J = a.d >= 1 && a.d <= 128 ? (int)filter_steps16(a.d) : 0;
+    if (J == 0 || a.slab == 0 || (a.slab & 1) || (a.nblk & 1)) throw std::runtime_error("scan_all_f16_kernel: shape not supported");
+    const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + 255) / 256)), block(256);
+    auto go = [&](auto kern) { LAUNCH(kern, grid, block, 0, s, a); };
+    if (a.metric == METRIC_L2) {
+        switch (J) {
+            case 4: return go(scan_all_f16_kernel<METRIC_L2, 4>);
+            case 6: return go(scan_all_f16_kernel<METRIC_L2, 6>);
+            default: return go(scan_all_f16_kernel<METRIC_L2, 8>);
+        }
+    }
+    switch (J) {
+        case 4: return go(scan_all_f16_kernel<METRIC_IP, 4>);
+        case 6: return go(scan_all_f16_kernel<METRIC_IP, 6>);
+        default: return go(scan_all_f16_kernel<METRIC_IP, 8>);
+    }
+}
+
+void launch_exact_rescore(const ExactRescoreArgs& a, hipStream_t s) {
+    if (a.n == 0) return;
+    if (a.metric == METRIC_L2) LAUNCH(exact_rescore_kernel<METRIC_L2>, dim3(a.n), dim3(256), 0, s, a);
+    else LAUNCH(exact_rescore_kernel<METRIC_IP>, dim3(a.n), dim3(256), 0, s, a);
+}
+
 void launch_exact_select(const ExactSelectArgs& a, hipStream_t s) {
     if (a.n == 0) return;
     uint32_t P = 2;
     while (P < a.cap) P <<= 1;
-    LAUNCH(exact_select_kernel, dim3(a.n), dim3(64), (size_t)P * 8, s, a);
+    if (a.rescored) LAUNCH(exact_select_kernel<true>, dim3(a.n), dim3(64), (size_t)P * 8, s, a);
+    else LAUNCH(exact_select_kernel<false>, dim3(a.n), dim3(64), (size_t)P * 8, s, a);
 }
 
 }  // namespace amdivf

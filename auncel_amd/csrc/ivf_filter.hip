@@ -39,6 +39,7 @@
 // Where every element on both sides is an integer of magnitude <= 2048 fp16 holds it exactly: s = 1 and C16 = C.  Queries
 // with a non-finite element (no usable scale) make the whole call keep every candidate (C < 0 in FilterParams): slow, never wrong.
 // Survivors are recomputed from the fp32 rows as before, so results do not depend on which form filtered.
+#include "exact_args.h"
 #include "ivf_dev.h"
 
 #include <algorithm>
@@ -281,9 +282,7 @@ __global__ void half_params_kernel(const uint32_t* qinfo, const uint32_t* yinfo,
     FilterParams p;
     p.sx = sx;
     p.pad = sy;
-    const float C = (float)(2 * d + 32) * 5.9604644775390625e-08f;
-    const bool exact = !qinfo[1] && !yinfo[1];
-    p.C = sx == 0.f || sy == 0.f ? -1.f : exact ? C : C + 0.0009765625f + 0.000244140625f;
+    p.C = sx == 0.f || sy == 0.f ? -1.f : exact_float_constant(d, !qinfo[1] && !yinfo[1]);
     p.ps = sx == 0.f || sy == 0.f ? 0.f : 1.f / (sx * sy);
     *params = p;
 }
@@ -300,9 +299,8 @@ __global__ __launch_bounds__(256) void filter_queries16_kernel(const float* x, s
         FilterParams p;
         p.sx = sx;
         p.pad = 0.f;
-        const float C = (float)(2 * d + 32) * 5.9604644775390625e-08f;  // (2 d + 32) 2^-24
-        const bool exact = !qinfo[1] && !yinfo[1];                       // every element on both sides held exactly
-        p.C = sx == 0.f || sy == 0.f ? -1.f : exact ? C : C + 0.0009765625f + 0.000244140625f;
+        // (2 d + 32) 2^-24, + 2^-10 + 2^-12 unless every element on both sides is held exactly: exact_args.h, shared with the exact pass
+        p.C = sx == 0.f || sy == 0.f ? -1.f : exact_float_constant(d, !qinfo[1] && !yinfo[1]);
         p.ps = sx == 0.f || sy == 0.f ? 0.f : 1.f / (sx * sy);
         *params = p;
     }

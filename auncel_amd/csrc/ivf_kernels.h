@@ -772,9 +772,39 @@ struct ExactScanArgs {
     uint2* cand;                  // [n][cap] (global position, distance bits)
     uint32_t cap;
 };
+// The same pass over float lists (d <= 128), on the filter's fp16 copy: codes_frag / yn are the index's (launch_frag16_from_f32), xf /
+// xn / params the call's (launch_filter_queries16).  A candidate is emitted as (global position, -): launch_exact_rescore writes the
+// reference's distance into the second word.
+struct ExactScanF16Args {
+    const float* codes_frag;      // fp16 fragments: filter_steps16(d) pieces of 1 KiB per block
+    const float* yn;              // per stored slot: |y|^2 (L2) / |y| (IP)
+    const uint2* blk;             // as above
+    uint64_t nblk;
+    uint32_t slab;
+    const float* xf;              // scaled fp16 query rows, row stride 8 filter_steps16(d) floats
+    const float* xn;
+    const FilterParams* params;
+    const float* seed_D;
+    const int64_t* seed_I;
+    uint32_t n, k;
+    int d, metric;
+    uint32_t* cnt;
+    uint2* cand;
+    uint32_t cap;
+};
+struct ExactRescoreArgs {
+    uint32_t n, cap;
+    int dpad, metric;
+    const uint32_t* cnt;
+    uint2* cand;
+    const float* queries;         // the query rows as passed (stride dpad)
+    const float* codes;           // the lists as stored (CSR rows, stride dpad)
+};
 struct ExactSelectArgs {
     uint32_t n, k, cap;
     int metric;
+    int rescored;                 // 1: the fp16 pass -- candidates beyond the threshold (seed_D) sort last and are not counted
+    const float* seed_D;
     const uint32_t* cnt;
     const uint2* cand;
     const int64_t* seed_I;
@@ -782,12 +812,15 @@ struct ExactSelectArgs {
     float* D;                     // [n][k], written for the queries flagged 0
     int64_t* I;
     uint32_t* flag;               // [n] 0 answered, 1 equal distances met, 2 no threshold / more candidates than slots
-    unsigned long long* totals;   // [0..2] += queries by flag, [3] += candidates emitted (zeroed by the caller)
+    unsigned long long* totals;   // [0..2] += queries by flag, [3] += candidates emitted, [4] += candidates at or within the threshold,
+                                  // [5] = max of one query's emitted count (six words, zeroed by the caller)
 };
 void launch_exact_blocks(const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, uint64_t nblk, uint2* out, hipStream_t s);
 void launch_identity_keys(int64_t* keys, size_t rows, uint32_t nlist, hipStream_t s);  // keys[i][l] = l
 uint32_t exact_slab_blocks(uint64_t nblk, uint32_t n);
 void launch_scan_all(const ExactScanArgs& a, hipStream_t s);
+void launch_scan_all_f16(const ExactScanF16Args& a, hipStream_t s);
+void launch_exact_rescore(const ExactRescoreArgs& a, hipStream_t s);
 void launch_exact_select(const ExactSelectArgs& a, hipStream_t s);
 
 inline uint32_t subset_range_key(float x) {

@@ -201,13 +201,23 @@ int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t npro
  * applied first.  _resident: over resident queries [start, start + n) (amd_ivf_set_queries).  Both work on amd_ivf_clone contexts.
  * How: the reference's heap admits an entry only if it strictly beats the top, so a query whose best
  * min(k + 1, ntotal) distances are pairwise different ends with exactly the k best entries, sorted, whatever the scan order was.
- * Byte-valued lists of d <= 128 (the rule of every byte scan, amd_ivf_scan_arith 2) are therefore searched in four stages: a seed
+ * Lists of d <= 128 are therefore searched in four stages (byte-valued lists -- the rule of every byte scan, amd_ivf_scan_arith 2 --
+ * in exact integer arithmetic; float lists as described below): a seed
  * search with a fixed nprobe (option "exact_seed_nprobe") gives each query a threshold, its k-th distance; ONE pass over all lists
  * (scan_all_kernel: a list block is fetched once per 256 queries) emits each query's entries at or within its threshold; a
  * selection orders them and writes the result of every query in which no equal distances met in that window; the other queries --
  * and those without a full seed result or with more candidates than slots -- are searched the general way, as one sliced
- * amd_ivf_search_preassigned with identity keys made on the device.  A call whose lists or queries do not qualify (float lists,
- * d > 128, a query value outside the byte rule, byte codes switched off, k > ntotal) goes the general way whole.
+ * amd_ivf_search_preassigned with identity keys made on the device.
+ * Float lists (and byte-valued ones whose byte codes are switched off or whose queries leave the byte rule): the pass runs on the
+ * fp16 copy of the lists that the filter keeps (option "filter" = 2), v_mfma_f32_32x32x16_f16 against the fp16 query rows
+ * (scan_all_f16_kernel).  Such a dot product differs from the reference's distance by at most the filter's bound, so the pass emits
+ * every entry that MAY lie at or within the threshold -- the comparison is not strict: an entry exactly at the threshold is never
+ * lost -- each emitted entry's distance is recomputed from the fp32 rows in the reference's rounding sequence, and the selection
+ * drops what lies strictly beyond the threshold before it looks for equal distances.  Option "exact_float" = 1 switches it on;
+ * without it such calls go the general way whole, as they always did.
+ * A call goes the general way whole when it does not qualify: d > 128, k > ntotal, k >= the candidate slots, no centroids; for the
+ * fp16 pass also option "exact_float" 0, option "filter" below 2, and lists or queries of the call without a usable fp16 scale (a non-finite element,
+ * magnitudes outside 2^+-24, a row that is not all zero whose largest element is below 2^-12 of the matrix's).
  * Returns -2 before the device is touched for: a null h, k = 0, null x / D / I with n > 0, a resident range that wraps round; -2 for
  * a resident range outside the resident queries.
  * amd_ivf_stats after the call: nq += n, nlist += n x nlist, ndis += n x ntotal -- every query meets every entry; nheap_updates
@@ -215,13 +225,18 @@ int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t npro
  * admission count and does not invent one (the seed search leaves no trace in any of the four).
  * amd_ivf_last_exact: out[0] queries of the last exact call answered by the list pass, out[1] queries searched the general way
  * because equal distances met, out[2] queries searched the general way for any other reason (candidate overflow, no full seed
- * result, the whole call not qualifying), out[3] candidates the list pass emitted, summed over the call.
+ * result, the whole call not qualifying), out[3] candidates the list pass emitted (the fp16 pass: before rescoring), summed over
+ * the call.
+ * amd_ivf_last_exact_detail: out[0] the list pass the last exact call ran (0 none, 1 bytes, 2 fp16 + rescoring), out[1] candidates
+ * emitted, out[2] candidates at or within the threshold (the fp16 pass: after rescoring, among the stored ones; the byte pass emits
+ * nothing else: out[1]), out[3] the largest emitted count of any one query -- what the candidate slots have to hold.
  * AUNCEL_AMD_EXACT_CAP=<n> (a test knob, read once per process): candidate slots per query, 2..4096 (default 1024).
- * Not offered: a matrix-core exact pass for float lists (the fp16 filter's bound with rescoring: the next step), d > 128 in the
- * pass, selectors, tickets, store_pairs / max_codes, the adaptive rule -- there is no exact entry point that takes any of them. */
+ * Not offered: d > 128 in the pass, selectors, tickets, store_pairs / max_codes, the adaptive rule -- there is no exact entry
+ * point that takes any of them. */
 int amd_ivf_search_exact(amd_ivf_t* h, size_t n, const float* x, size_t k, float* D, int64_t* I);
 int amd_ivf_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, float* D, int64_t* I);
 int amd_ivf_last_exact(amd_ivf_t* h, uint64_t out[4]);
+int amd_ivf_last_exact_detail(amd_ivf_t* h, uint64_t out[4]);
 
 /* InvertedListScanner: set_query + set_list + scan_codes on a caller-owned raw binary heap
  * (simi/idxi, k entries, heapified by the caller as in tests/test_lowlevel_ivf.cpp:150-175);
@@ -557,6 +572,8 @@ int amd_ivf_set_byte_codes(amd_ivf_t* h, int enable);
  *                     allocation that fails, takes the full upload either way
  *   "exact_seed_nprobe"  amd_ivf_search_exact: nprobe of the seed search whose k-th distance is the list pass's     16
  *                     threshold (at most nlist; AUNCEL_AMD_EXACT_SEED is the environment's form).  Cannot change a result
+ *   "exact_float"     amd_ivf_search_exact over float lists: 1 the fp16 matrix-core list pass with rescoring, 0 the general      0
+ *                     way for the whole call (AUNCEL_AMD_EXACT_FLOAT is the environment's form).  Cannot change a result
  * amd_ivf_set_option(h, key, NAN) returns the key to "unset".  May be called while search contexts of the index are searching: a
  * search reads what shapes its launches once, when it starts, so the change takes effect with the searches that start after it. */
 int amd_ivf_set_option(amd_ivf_t* h, const char* key, double value);
