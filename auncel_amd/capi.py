@@ -39,6 +39,7 @@ SYMBOLS = [
     "amd_ivf_selector_combine", "amd_ivf_range_search_selected", "amd_ivf_range_search_preassigned_selected",
     "amd_ivf_submit_search_resident_selected",
     "amd_ivf_search_exact", "amd_ivf_search_exact_resident", "amd_ivf_last_exact", "amd_ivf_last_exact_detail",
+    "amd_ivf_search_exact_selected", "amd_ivf_search_exact_resident_selected",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -527,6 +528,22 @@ class Handle:
         D = np.empty((n, k), np.float32)
         I = np.empty((n, k), np.int64)
         _chk(lib().amd_ivf_search_exact_resident(self._h, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k), _f(D), _i(I)))
+        return D, I
+
+    def search_exact_selected(self, selector, x, k):
+        """search_exact over the selector's members only (include/auncel_amd.h: amd_ivf_search_exact_selected): search_exact of
+        subset(the same selector), bit for bit, without the second index"""
+        x = f32(x)
+        n = x.shape[0]
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_exact_selected(self._h, selector._s, C.c_size_t(n), _f(x), C.c_size_t(k), _f(D), _i(I)))
+        return D, I
+
+    def search_exact_resident_selected(self, selector, start, n, k):
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_exact_resident_selected(self._h, selector._s, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k), _f(D), _i(I)))
         return D, I
 
     def last_exact(self):

@@ -1,8 +1,9 @@
 // The host side of the exact search over the whole index (include/auncel_amd.h: amd_ivf_search_exact): what the entry points refuse
 // before anything touches a device, and the one rule that says when a query's result can be read off its sorted candidates (DESIGN.md
-// 13), and the keep rule of the fp16 list pass over float lists.  Plain C++, nothing of the device in it: the kernels of ivf_exact.hip
-// and the host read the same definitions, and it builds on its own (tests/cpp/exact_args_main.cpp and exact_float_main.cpp, which
-// are what the address and undefined-behaviour sanitizers are pointed at).
+// 13), the keep rule of the fp16 list pass over float lists, and what the forms under an id selector add: their checks, the seed's
+// nprobe and the mask of a block's live slots.  Plain C++, nothing of the device in it: the kernels of ivf_exact.hip
+// and the host read the same definitions, and it builds on its own (tests/cpp/exact_args_main.cpp, exact_float_main.cpp and
+// exact_selected_main.cpp, which are what the address and undefined-behaviour sanitizers are pointed at).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -27,6 +28,34 @@ inline std::string exact_args_error(bool have_handle, bool have_queries, size_t 
     if (n && (!have_queries || !D || !I)) return w + "null argument";
     return std::string();
 }
+
+// ... of the forms that search under a selector (amd_ivf_search_exact_selected / _resident_selected): the same, and the selector must
+// be there.  Whether it is of this index and of the lists as they are now is the handle's to say (selector_words).
+inline std::string exact_selected_args_error(bool have_handle, bool have_selector, bool have_queries, size_t start, size_t n, size_t k,
+                                             const void* D, const void* I) {
+    if (have_handle && !have_selector) return std::string("exact search: null selector");
+    return exact_args_error(have_handle, have_queries, start, n, k, D, I);
+}
+
+// The seed's nprobe under a selector that keeps `kept` of `ntotal` entries: `seed` lists hold seed x ntotal / nlist entries on
+// average and so seed x kept / nlist members; ceil(seed x ntotal / kept) lists hold as many members as `seed` lists hold entries.
+// kept = 0 (nothing to find) and a product beyond 64 bits: the largest value, which no nlist reaches.  The seed only sets a
+// threshold: any value gives the same result.
+inline uint64_t exact_selected_seed(uint64_t seed, uint64_t ntotal, uint64_t kept) {
+    if (kept == 0 || (ntotal && seed > UINT64_MAX / ntotal)) return UINT64_MAX;
+    const uint64_t p = seed * ntotal;
+    return p / kept + (p % kept != 0);
+}
+
+// The entries of a 32-slot block that a selected list pass may emit, bit m for slot m: the slot holds an entry (m < left, left = the
+// entries of the list from the block's first slot on) AND the selector keeps it (keep_half: the block's half of its keep word, bit m
+// for slot m).  The AND with the `left` mask does not lean on the keep words being zero past a list's end.
+EXACT_HD inline uint32_t exact_block_valid_mask(uint64_t left, uint32_t keep_half) {
+    const uint32_t live = left >= 32 ? 0xffffffffu : (((uint32_t)1 << left) - 1u);
+    return live & keep_half;
+}
+// the half of keep word `blk >> 1` that belongs to block `blk`
+EXACT_HD inline uint32_t exact_block_keep_half(uint64_t word, uint64_t blk) { return (uint32_t)(word >> (32 * (blk & 1))); }
 
 // A candidate's sort key: the order key of its distance (smaller = better, whatever the metric) above its global position.
 EXACT_HD inline uint64_t exact_key(uint32_t dist_key, uint32_t position) { return ((uint64_t)dist_key << 32) | position; }

@@ -39,11 +39,16 @@ struct IndexIVFFlat : IndexIVF {
     void search_exact(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const;
     void exact_info(uint64_t out[4]) const;
     void exact_detail(uint64_t out[4]) const;
+    /// search_exact over the members of `sel` only (include/auncel_amd.h: amd_ivf_search_exact_selected): the filtered ground truth,
+    /// bit for bit search_exact of an IndexIVFFlatSubset of the same selector.  The selectors and the kept bits are search_selected's:
+    /// the same selector used by both calls is made once (selector_passes); exact_info / exact_detail report the call.
+    void search_exact_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const IDSelector& sel) const;
     IndexIVFFlat(const IndexIVFFlat&) = delete;
     IndexIVFFlat& operator=(const IndexIVFFlat&) = delete;
     ~IndexIVFFlat() override;
 
    private:
+    amd_ivf_selector* device_selector(amd_ivf* g, const IDSelector& sel) const;
     mutable amd_ivf_selector* sel_ = nullptr;  // the kept selector, and what it was made from
     mutable size_t sel_version_ = 0;
     mutable int sel_kind_ = -1;

@@ -1284,10 +1284,8 @@ void IndexIVFFlat::selected_info(uint64_t out[4]) const {
     if (sel_) AMD(amd_ivf_selector_info(sel_, out));
 }
 
-void IndexIVFFlat::search_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const IDSelector& sel) const {
-    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(this) == nullptr, "search_selected of an IndexIVFFlatDedup is not implemented");
-    FAISS_THROW_IF_NOT_MSG(!tune && !training && !(t && t->time_tune), "search_selected is the plain fixed-nprobe search only");
-    FAISS_THROW_IF_NOT_MSG(max_codes == 0, "search_selected with max_codes is not implemented");
+// the engine's selector for `sel`: the kept one while the lists and the selector's parameters repeat, else a new pass over the ids
+amd_ivf_selector* IndexIVFFlat::device_selector(amd_ivf* g, const IDSelector& sel) const {
     int kind;
     idx_t a1 = 0, a2 = 0;
     std::vector<int64_t> ids;
@@ -1302,7 +1300,6 @@ void IndexIVFFlat::search_selected(idx_t n, const float* x, idx_t k, float* dist
     } else {
         FAISS_THROW_MSG("a search under this kind of IDSelector is not implemented");
     }
-    amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
     const bool kept = sel_ && sel_version_ == invlists->version && sel_kind_ == kind && sel_a1_ == a1 && sel_a2_ == a2 && sel_ids_ == ids;
     if (!kept) {
         if (sel_) amd_ivf_selector_destroy(sel_);
@@ -1315,7 +1312,15 @@ void IndexIVFFlat::search_selected(idx_t n, const float* x, idx_t k, float* dist
         sel_a2_ = a2;
         sel_ids_.swap(ids);
     }
-    AMD(amd_ivf_search_selected(g, sel_, (size_t)n, x, (size_t)k, nprobe, coarse_mode, distances, i64(labels)));
+    return sel_;
+}
+
+void IndexIVFFlat::search_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const IDSelector& sel) const {
+    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(this) == nullptr, "search_selected of an IndexIVFFlatDedup is not implemented");
+    FAISS_THROW_IF_NOT_MSG(!tune && !training && !(t && t->time_tune), "search_selected is the plain fixed-nprobe search only");
+    FAISS_THROW_IF_NOT_MSG(max_codes == 0, "search_selected with max_codes is not implemented");
+    amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
+    AMD(amd_ivf_search_selected(g, device_selector(g, sel), (size_t)n, x, (size_t)k, nprobe, coarse_mode, distances, i64(labels)));
 }
 
 // ------------------------------------------------------------------------------------- IndexIVFFlat::search_exact
@@ -1325,6 +1330,14 @@ void IndexIVFFlat::search_exact(idx_t n, const float* x, idx_t k, float* distanc
     FAISS_THROW_IF_NOT_MSG(max_codes == 0, "search_exact with max_codes is not implemented");
     amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
     AMD(amd_ivf_search_exact(g, (size_t)n, x, (size_t)k, distances, i64(labels)));
+}
+
+void IndexIVFFlat::search_exact_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const IDSelector& sel) const {
+    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(this) == nullptr, "search_exact_selected of an IndexIVFFlatDedup is not implemented");
+    FAISS_THROW_IF_NOT_MSG(!tune && !training && !(t && t->time_tune), "search_exact_selected is the plain search only");
+    FAISS_THROW_IF_NOT_MSG(max_codes == 0, "search_exact_selected with max_codes is not implemented");
+    amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
+    AMD(amd_ivf_search_exact_selected(g, device_selector(g, sel), (size_t)n, x, (size_t)k, distances, i64(labels)));
 }
 
 void IndexIVFFlat::exact_info(uint64_t out[4]) const { AMD(amd_ivf_last_exact(engine(), out)); }

@@ -5834,7 +5834,9 @@ uint32_t exact_cap() {
 // The queries idx[0 .. m) of d_x (all n of them when idx is null) the general way: search_preassigned over every list in
 // list-number order, with the keys made on the device, in slices that keep the key table small; rows written to their places in
 // (D, I).  Returns the heap updates the slices made (the only part of an exact call the reference's admission count exists for).
-size_t exact_general(amd_ivf* h, const float* d_x, const uint32_t* idx, size_t m, size_t k, float* D, int64_t* I, const IntRange& qr) {
+// keep: a selector's words -- the search is then over its members only, the path amd_ivf_search_preassigned_selected runs.
+size_t exact_general(amd_ivf* h, const float* d_x, const uint32_t* idx, size_t m, size_t k, float* D, int64_t* I, const IntRange& qr,
+                     const unsigned long long* keep) {
     const size_t nlist = h->nlist;
     const size_t slice = std::max<size_t>(1, std::min<size_t>(4096, ((size_t)4 << 20) / std::max<size_t>(nlist, 1)));
     std::vector<float> tD;
@@ -5855,11 +5857,11 @@ size_t exact_general(amd_ivf* h, const float* d_x, const uint32_t* idx, size_t m
         launch_identity_keys(h->w_ckeys.as<int64_t>(), c, (uint32_t)nlist, h->stream);
         const size_t before = h->stats_host[3];
         if (!idx) {
-            search_fixed_device(h, rows, c, k, nlist, h->w_ckeys.as<int64_t>(), D + o * k, I + o * k, 0, 0, qr);
+            search_fixed_device(h, rows, c, k, nlist, h->w_ckeys.as<int64_t>(), D + o * k, I + o * k, 0, 0, qr, keep);
         } else {
             tD.resize(c * k);
             tI.resize(c * k);
-            search_fixed_device(h, rows, c, k, nlist, h->w_ckeys.as<int64_t>(), tD.data(), tI.data(), 0, 0, qr);
+            search_fixed_device(h, rows, c, k, nlist, h->w_ckeys.as<int64_t>(), tD.data(), tI.data(), 0, 0, qr, keep);
             for (size_t j = 0; j < c; j++) {
                 memcpy(D + (size_t)idx[o + j] * k, tD.data() + j * k, k * sizeof(float));
                 memcpy(I + (size_t)idx[o + j] * k, tI.data() + j * k, k * sizeof(int64_t));
@@ -5872,14 +5874,21 @@ size_t exact_general(amd_ivf* h, const float* d_x, const uint32_t* idx, size_t m
 
 // one slice of an exact call: seed, list pass, selection, and the flagged queries the general way.  out: amd_ivf_last_exact's counts
 // (added to); returns the heap updates of the general-way part.
-size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int64_t* I, const IntRange& qr, uint64_t out[4]) {
+// sel: the call searches the selector's members only (checked by the caller: of this index, of the lists as they are).  The lists are
+// then "the lists with the non-members removed" in every stage: the seed's k-th distance is that of k members, the block table
+// carries the members' mask, and the general way searches under the same keep words.
+size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int64_t* I, const IntRange& qr, uint64_t out[4],
+                   const amd_ivf_selector* sel) {
     amd_ivf* index = ix(h);
     const size_t nlist = h->nlist;
     const uint64_t ntotal = index->h_list_off.size() == nlist + 1 ? index->h_list_off[nlist] : 0;
+    const uint64_t members = sel ? sel->info[1] : ntotal;
+    const unsigned long long* keep = sel ? sel->keep.as<unsigned long long>() : nullptr;
     const uint32_t cap = exact_cap();
     const uint64_t nblk = index->h_block_off.size() == nlist + 1 ? index->h_block_off[nlist] : 0;
+    if (sel && sel->keep.cap < nblk / 2 * 8) throw std::runtime_error("exact search: the selector is shorter than the lists");
     // the list pass runs on byte codes up to four K-steps, under the rule every byte scan runs under
-    const bool shape_ok = index->have_centroids && h->d <= 128 && nblk > 0 && ntotal < 0xffffffffull && k < cap && k <= ntotal;
+    const bool shape_ok = index->have_centroids && h->d <= 128 && nblk > 0 && ntotal < 0xffffffffull && k < cap && k <= members;
     const bool bytes = index->have_codes8 && h->allow_bytes && index->db_range.bytes_with(qr, (size_t)h->d);
     const bool pass = shape_ok && bytes;
     // ... and on the filter's fp16 copy of float lists, where lists and queries have a usable scale (ivf_filter.hip: no non-finite
@@ -5895,13 +5904,22 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         HIP_CHECK(stream_sync(s));
         pass16 = filter_half_scale(info, h->d) != 0.f;
     }
-    if (!pass && !pass16) {
-        out[2] += n;
-        return exact_general(h, d_x, nullptr, n, k, D, I, qr);
+    // ---- 1. seed: an ordinary fixed-nprobe search; its k-th distance is a distance of k stored entries, so the true k-th is within it.
+    // Under a selector it is the k-th among the members the seed saw; as `seed` lists hold too few of them when the selector is
+    // sparse, nprobe grows by ntotal / kept (exact_args.h) -- and a seed that would read every list is the whole search: the call
+    // then goes the general way (any seed gives the same result: this only decides which path computes it)
+    size_t seed = std::min<size_t>(nlist, (size_t)std::max(1.0, opt(h, OPT_EXACT_SEED_NPROBE, EXACT_SEED_DEFAULT)));
+    bool seed_ok = true;
+    if (sel) {
+        const uint64_t scaled = exact_selected_seed(seed, ntotal, members);
+        seed_ok = scaled < nlist;
+        seed = (size_t)std::min<uint64_t>(scaled, nlist);
     }
-    // ---- 1. seed: an ordinary fixed-nprobe search; its k-th distance is a distance of k stored entries, so the true k-th is within it
-    const size_t seed = std::min<size_t>(nlist, (size_t)std::max(1.0, opt(h, OPT_EXACT_SEED_NPROBE, EXACT_SEED_DEFAULT)));
-    search_full(h, d_x, n, k, seed, -1, D, I, qr);
+    if ((!pass && !pass16) || !seed_ok) {
+        out[2] += n;
+        return exact_general(h, d_x, nullptr, n, k, D, I, qr, keep);
+    }
+    search_full(h, d_x, n, k, seed, -1, D, I, qr, keep);
     const float* seed_D = h->last_direct_out ? static_cast<const float*>(device_view(D)) : h->w_D.as<float>();
     const int64_t* seed_I = h->last_direct_out ? static_cast<const int64_t*>(device_view(I)) : h->w_I.as<int64_t>();
     if (!seed_D || !seed_I) throw std::runtime_error("exact search: the seed's result is not on the device");
@@ -5914,7 +5932,11 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     h->w_ex_tot.ensure(6 * 8);
     h->w_ex_D.ensure(n * k * sizeof(float));
     h->w_ex_I.ensure(n * k * sizeof(int64_t));
-    launch_exact_blocks(index->d_list_off.as<uint64_t>(), index->d_block_off.as<uint64_t>(), (uint32_t)nlist, nblk, h->w_ex_blk.as<uint2>(), s);
+    if (sel)
+        launch_exact_blocks_keep(index->d_list_off.as<uint64_t>(), index->d_block_off.as<uint64_t>(), keep, (uint32_t)nlist, nblk,
+                                 h->w_ex_blk.as<uint2>(), s);
+    else
+        launch_exact_blocks(index->d_list_off.as<uint64_t>(), index->d_block_off.as<uint64_t>(), (uint32_t)nlist, nblk, h->w_ex_blk.as<uint2>(), s);
     HIP_CHECK(hipMemsetAsync(h->w_ex_cnt.p, 0, n * 4, s));
     HIP_CHECK(hipMemsetAsync(h->w_ex_tot.p, 0, 6 * 8, s));
     ExactScanArgs sa{};
@@ -5940,7 +5962,7 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
     if (pass) {
         if (timed) HIP_CHECK(hipEventRecord(ev[0], s));
-        launch_scan_all(sa, s);
+        launch_scan_all(sa, sel != nullptr, s);
     } else {
         // the fp16 query operands and FilterParams by the filter's own launches (the seed search may have left them; not every seed does)
         h->w_xf.ensure(n * (size_t)filter_steps(h->d) * 8 * sizeof(float));
@@ -5969,7 +5991,7 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         fa.cand = sa.cand;
         fa.cap = cap;
         if (timed) HIP_CHECK(hipEventRecord(ev[0], s));
-        launch_scan_all_f16(fa, s);
+        launch_scan_all_f16(fa, sel != nullptr, s);
         ExactRescoreArgs ra{};
         ra.n = (uint32_t)n;
         ra.cap = cap;
@@ -6025,10 +6047,10 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     for (size_t i = 0; i < n; i++)
         if (flag[i]) redo.push_back((uint32_t)i);
     if (redo.empty()) return 0;
-    return exact_general(h, d_x, redo.data(), redo.size(), k, D, I, qr);
+    return exact_general(h, d_x, redo.data(), redo.size(), k, D, I, qr, keep);
 }
 
-void exact_core(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int64_t* I, const IntRange& qr) {
+void exact_core(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int64_t* I, const IntRange& qr, const amd_ivf_selector* sel = nullptr) {
     upload_lists(h);  // (a pending journal is applied first, as every search does)
     amd_ivf* index = ix(h);
     const size_t nlist = h->nlist;
@@ -6037,7 +6059,7 @@ void exact_core(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int6
     for (int i = 0; i < 4; i++) st[i] = h->stats_host[i];
     uint64_t out[4] = {0, 0, 0, 0};
     size_t heap = 0;
-    if (ntotal == 0) {  // an empty index: the reference's padding for every query
+    if (ntotal == 0 || (sel && sel->info[1] == 0)) {  // an empty index, a selector without members: the reference's padding for every query
         std::fill(D, D + n * k, h->metric == METRIC_L2 ? FLT_MAX : -FLT_MAX);
         std::fill(I, I + n * k, (int64_t)-1);
         out[2] = n;
@@ -6045,10 +6067,11 @@ void exact_core(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int6
         const size_t slice = 8192;  // (bounds the candidate buffers: slice x cap x 8 bytes)
         for (size_t o = 0; o < n; o += slice) {
             const size_t c = std::min(slice, n - o);
-            heap += exact_slice(h, d_x + o * (size_t)h->dpad, c, k, D + o * k, I + o * k, qr, out);
+            heap += exact_slice(h, d_x + o * (size_t)h->dpad, c, k, D + o * k, I + o * k, qr, out, sel);
         }
     }
-    // the statistics of the call as the header states them: the seed searches leave no trace, the list pass has no admission count
+    // the statistics of the call as the header states them: the seed searches leave no trace, the list pass has no admission count;
+    // under a selector ndis counts the entries as the lists hold them, members or not (every one of them is read)
     h->stats_host[0] = st[0] + n;
     h->stats_host[1] = st[1] + n * nlist;
     h->stats_host[2] = st[2] + n * (size_t)ntotal;
@@ -6095,6 +6118,42 @@ int amd_ivf_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, size_t k
     WallClock wc(h->stream);
     reset_scan_counters(h);
     exact_core(h, q.d_x, n, k, D, I, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+// amd_ivf_search_exact / _resident over a selector's members only.  selector_words refuses a selector of another index and a stale one
+// from host state alone, before the device is asked for.
+int amd_ivf_search_exact_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, float* D, int64_t* I) {
+    API_BEGIN
+    const std::string bad = exact_selected_args_error(h != nullptr, s != nullptr, x != nullptr, 0, n, k, D, I);
+    if (!bad.empty()) throw EngineError(bad);
+    selector_words(h, s);
+    require_device();
+    use_device(h);
+    for (int i = 0; i < 4; i++) h->last_exact[i] = h->last_exact_detail[i] = 0;
+    if (n == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const QueryRows q = host_rows(h, x, n);
+    exact_core(h, q.d_x, n, k, D, I, q.range, s);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_exact_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t k, float* D, int64_t* I) {
+    API_BEGIN
+    const std::string bad = exact_selected_args_error(h != nullptr, s != nullptr, true, start, n, k, D, I);
+    if (!bad.empty()) throw EngineError(bad);
+    selector_words(h, s);
+    require_device();
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    for (int i = 0; i < 4; i++) h->last_exact[i] = h->last_exact_detail[i] = 0;
+    if (n == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    exact_core(h, q.d_x, n, k, D, I, q.range, s);
     finish_timing(h, wc.stop());
     API_END
 }

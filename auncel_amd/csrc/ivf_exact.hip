@@ -3,6 +3,8 @@
 // consecutive blocks, and a block that has been fetched is contracted with every query block of the tile before it is let go.
 //   scan_all_kernel      the list pass: emits, per query, every stored entry at or within the query's threshold (the k-th distance of
 //                        a seed search of the same lists) as (global position, distance)
+//   exact_blocks_keep_kernel  the block table of a call under an id selector: the mask of a block's slots that hold a MEMBER, so the
+//                        same pass (KEEP) emits members only with nothing added to its loop
 //   exact_select_kernel  a wave per query: the candidates in (distance, position) order; the result is read off them when no two
 //                        neighbours of the best k + 1 are equal (exact_args.h: exact_window_tied), else the query is flagged and
 //                        the caller searches it the general way
@@ -42,6 +44,26 @@ __global__ __launch_bounds__(256) void exact_blocks_kernel(const uint64_t* __res
     out[blk] = make_uint2((uint32_t)(list_off[lo] + p), (uint32_t)(left < 32 ? left : 32));
 }
 
+// The table of a call under a selector: (global position of the block's first slot, VALID MASK) -- bit m is set iff slot m holds an
+// entry and the selector keeps it (exact_args.h: exact_block_valid_mask).  keep: the selector's words, a bit per slot of the padded
+// layout, so block b's 32 bits are half b & 1 of word b >> 1.  The list pass reads the mask where it read the count: a non-member is
+// a slot behind the list's end to it, and nothing is added to its loop.
+__global__ __launch_bounds__(256) void exact_blocks_keep_kernel(const uint64_t* __restrict__ list_off, const uint64_t* __restrict__ block_off,
+                                                                const unsigned long long* __restrict__ keep, uint32_t nlist, uint64_t nblk,
+                                                                uint2* __restrict__ out) {
+    const uint64_t blk = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (blk >= nblk) return;
+    uint32_t lo = 0, hi = nlist;  // largest l with block_off[l] <= blk
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (block_off[mid] <= blk) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t p = (blk - block_off[lo]) * 32, size = list_off[lo + 1] - list_off[lo];
+    const uint64_t left = p < size ? size - p : 0;
+    out[blk] = make_uint2((uint32_t)(list_off[lo] + p), exact_block_valid_mask(left, exact_block_keep_half(keep[blk >> 1], blk)));
+}
+
 // keys[i][l] = l: the ranking under which the general way visits every list in list-number order
 __global__ __launch_bounds__(256) void identity_keys_kernel(int64_t* __restrict__ keys, uint64_t total, uint32_t nlist) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -56,7 +78,10 @@ __global__ __launch_bounds__(256) void identity_keys_kernel(int64_t* __restrict_
 // it is how a tie at the k-th is seen.  The pre-test is the pair kernel's strict one against T + 1 (L2: made even, so loosened by at
 // most one more) / T - 1 (IP); a register that passes it recomputes the distance and tests it exactly.  Slots behind a list's end
 // (ExactScanArgs::blk says how many of a block's 32 are entries) never pass: their bound is INT_MAX.
-template <int METRIC, int NKS>
+// KEEP (a call under a selector): blk.y is the mask of the slots that hold a MEMBER (exact_blocks_keep_kernel) and a slot is live iff
+// its bit is set -- a non-member is treated exactly as a slot behind the list's end: it emits nothing, takes no candidate slot and
+// moves no counter.  KEEP = false is the unfiltered pass, instruction for instruction what it was before the parameter existed.
+template <int METRIC, int NKS, bool KEEP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) void scan_all_kernel(ExactScanArgs a) {
     static_assert(NKS >= 1 && NKS <= 4, "query operands resident in registers");
     __shared__ int s_init[4][64];
@@ -149,7 +174,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
             for (int s = 0; s < NKS; s++) acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af1[s], b[s], acc1, 0, 0, 0);
         }
         // what the epilogue needs of the block's constants is taken before their registers are requested again
-        const bool vok = (uint32_t)m < biv.y;  // (a slot behind the list's end emits nothing)
+        const bool vok = KEEP ? ((biv.y >> m) & 1u) != 0 : (uint32_t)m < biv.y;  // (a slot behind the list's end, a non-member: nothing)
         int hc = !vok ? 0x7fffffff : METRIC == METRIC_L2 ? cyv >> 1 : -cyv;
         uint32_t pos = biv.x + (uint32_t)m;
         int cy;
@@ -205,7 +230,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
 // each and the selection drops what lies beyond the threshold.  Emitted: (global position, -).
 // Registers (hipcc -O3, gfx950, --save-temps): NJ = 8 is the largest form, 2 x 32 operand registers of the queries, 2 x 32 of the
 // blocks in flight, 2 x 16 accumulators; no instantiation uses scratch (DESIGN.md 13 has the table).
-template <int METRIC, int NJ>
+// KEEP: as in scan_all_kernel, blk.y is the members' mask; a non-member is never emitted, so it is never rescored either.
+template <int METRIC, int NJ, bool KEEP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_all_f16_kernel(ExactScanF16Args a) {
     static_assert(NJ == 4 || NJ == 6 || NJ == 8, "the piece counts of filter_steps16 up to 128 dimensions");
     constexpr bool L2 = METRIC == METRIC_L2;
@@ -277,7 +303,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, af1[j]), __builtin_bit_cast(v8h, b[j]), acc1, 0, 0, 0);
         }
         // what the epilogue needs of the block's constants is taken before their registers are requested again
-        const bool vok = (uint32_t)m < biv.y;  // (a slot behind the list's end emits nothing)
+        const bool vok = KEEP ? ((biv.y >> m) & 1u) != 0 : (uint32_t)m < biv.y;  // (a slot behind the list's end, a non-member: nothing)
         uint32_t pos = biv.x + (uint32_t)m;
         float yn;
         asm volatile("v_mov_b32 %0, %1" : "=v"(yn) : "v"(ynv));
@@ -430,6 +456,12 @@ void launch_exact_blocks(const uint64_t* list_off, const uint64_t* block_off, ui
     LAUNCH(exact_blocks_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, s, list_off, block_off, nlist, nblk, out);
 }
 
+void launch_exact_blocks_keep(const uint64_t* list_off, const uint64_t* block_off, const unsigned long long* keep, uint32_t nlist, uint64_t nblk,
+                              uint2* out, hipStream_t s) {
+    if (nblk == 0) return;
+    LAUNCH(exact_blocks_keep_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, s, list_off, block_off, keep, nlist, nblk, out);
+}
+
 void launch_identity_keys(int64_t* keys, size_t rows, uint32_t nlist, hipStream_t s) {
     const uint64_t total = (uint64_t)rows * nlist;
     if (total == 0) return;
@@ -445,46 +477,56 @@ uint32_t exact_slab_blocks(uint64_t nblk, uint32_t n) {
     return (uint32_t)std::min<uint64_t>(slab, 1u << 30);
 }
 
-void launch_scan_all(const ExactScanArgs& a, hipStream_t s) {
+void launch_scan_all(const ExactScanArgs& a, bool keep, hipStream_t s) {
     if (a.n == 0 || a.nblk == 0) return;
     const int ks = (int)mfma_ksteps(a.d);
     if (ks < 1 || ks > 4 || a.slab == 0 || (a.slab & 1) || (a.nblk & 1)) throw std::runtime_error("scan_all_kernel: shape not supported");
     const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + 255) / 256)), block(256);
     auto go = [&](auto kern) { LAUNCH(kern, grid, block, 0, s, a); };
-    if (a.metric == METRIC_L2) {
-        switch (ks) {
-            case 1: return go(scan_all_kernel<METRIC_L2, 1>);
-            case 2: return go(scan_all_kernel<METRIC_L2, 2>);
-            case 3: return go(scan_all_kernel<METRIC_L2, 3>);
-            default: return go(scan_all_kernel<METRIC_L2, 4>);
+    auto pick = [&](auto K) {
+        constexpr bool KEEP = decltype(K)::value;
+        if (a.metric == METRIC_L2) {
+            switch (ks) {
+                case 1: return go(scan_all_kernel<METRIC_L2, 1, KEEP>);
+                case 2: return go(scan_all_kernel<METRIC_L2, 2, KEEP>);
+                case 3: return go(scan_all_kernel<METRIC_L2, 3, KEEP>);
+                default: return go(scan_all_kernel<METRIC_L2, 4, KEEP>);
+            }
         }
-    }
-    switch (ks) {
-        case 1: return go(scan_all_kernel<METRIC_IP, 1>);
-        case 2: return go(scan_all_kernel<METRIC_IP, 2>);
-        case 3: return go(scan_all_kernel<METRIC_IP, 3>);
-        default: return go(scan_all_kernel<METRIC_IP, 4>);
-    }
+        switch (ks) {
+            case 1: return go(scan_all_kernel<METRIC_IP, 1, KEEP>);
+            case 2: return go(scan_all_kernel<METRIC_IP, 2, KEEP>);
+            case 3: return go(scan_all_kernel<METRIC_IP, 3, KEEP>);
+            default: return go(scan_all_kernel<METRIC_IP, 4, KEEP>);
+        }
+    };
+    if (keep) pick(std::true_type{});
+    else pick(std::false_type{});
 }
 
-void launch_scan_all_f16(const ExactScanF16Args& a, hipStream_t s) {
+void launch_scan_all_f16(const ExactScanF16Args& a, bool keep, hipStream_t s) {
     if (a.n == 0 || a.nblk == 0) return;
     const int J = a.d >= 1 && a.d <= 128 ? (int)filter_steps16(a.d) : 0;
     if (J == 0 || a.slab == 0 || (a.slab & 1) || (a.nblk & 1)) throw std::runtime_error("scan_all_f16_kernel: shape not supported");
     const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + 255) / 256)), block(256);
     auto go = [&](auto kern) { LAUNCH(kern, grid, block, 0, s, a); };
-    if (a.metric == METRIC_L2) {
-        switch (J) {
-            case 4: return go(scan_all_f16_kernel<METRIC_L2, 4>);
-            case 6: return go(scan_all_f16_kernel<METRIC_L2, 6>);
-            default: return go(scan_all_f16_kernel<METRIC_L2, 8>);
+    auto pick = [&](auto K) {
+        constexpr bool KEEP = decltype(K)::value;
+        if (a.metric == METRIC_L2) {
+            switch (J) {
+                case 4: return go(scan_all_f16_kernel<METRIC_L2, 4, KEEP>);
+                case 6: return go(scan_all_f16_kernel<METRIC_L2, 6, KEEP>);
+                default: return go(scan_all_f16_kernel<METRIC_L2, 8, KEEP>);
+            }
         }
-    }
-    switch (J) {
-        case 4: return go(scan_all_f16_kernel<METRIC_IP, 4>);
-        case 6: return go(scan_all_f16_kernel<METRIC_IP, 6>);
-        default: return go(scan_all_f16_kernel<METRIC_IP, 8>);
-    }
+        switch (J) {
+            case 4: return go(scan_all_f16_kernel<METRIC_IP, 4, KEEP>);
+            case 6: return go(scan_all_f16_kernel<METRIC_IP, 6, KEEP>);
+            default: return go(scan_all_f16_kernel<METRIC_IP, 8, KEEP>);
+        }
+    };
+    if (keep) pick(std::true_type{});
+    else pick(std::false_type{});
 }
 
 void launch_exact_rescore(const ExactRescoreArgs& a, hipStream_t s) {

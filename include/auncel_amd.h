@@ -153,7 +153,7 @@ int amd_ivf_selector_combine(int op, const amd_ivf_selector_t* a, const amd_ivf_
  * in order; a query that finds fewer than k members ends with the reference's padding.  The coarse ranking is h's own.  In
  * amd_ivf_stats, nheap_updates is the subset's (the admissions are the same sequence); ndis counts the entries of the probed lists
  * AS h HOLDS THEM, members or not: every one of them is scanned.
- * Fixed nprobe or a radius (below), ids.  Not offered under a selector: the adaptive rule (its traces are trained on the whole
+ * Fixed nprobe or a radius (below), every list (amd_ivf_search_exact_selected, further down), ids.  Not offered under a selector: the adaptive rule (its traces are trained on the whole
  * index), the scanner calls, store_pairs / max_codes, tickets of any search but amd_ivf_search_resident_selected, and one selector
  * per QUERY -- there is no entry point that takes a selector for any of them, so none can return an unfiltered answer.  -2 for a
  * null h / s, a selector of another index, a stale selector. */
@@ -231,12 +231,32 @@ int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t npro
  * emitted, out[2] candidates at or within the threshold (the fp16 pass: after rescoring, among the stored ones; the byte pass emits
  * nothing else: out[1]), out[3] the largest emitted count of any one query -- what the candidate slots have to hold.
  * AUNCEL_AMD_EXACT_CAP=<n> (a test knob, read once per process): candidate slots per query, 2..4096 (default 1024).
- * Not offered: d > 128 in the pass, selectors, tickets, store_pairs / max_codes, the adaptive rule -- there is no exact entry
- * point that takes any of them. */
+ * Not offered: d > 128 in the pass, tickets, store_pairs / max_codes, the adaptive rule -- there is no exact entry point that takes
+ * any of them.  (Selectors: below.) */
 int amd_ivf_search_exact(amd_ivf_t* h, size_t n, const float* x, size_t k, float* D, int64_t* I);
 int amd_ivf_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, float* D, int64_t* I);
 int amd_ivf_last_exact(amd_ivf_t* h, uint64_t out[4]);
 int amd_ivf_last_exact_detail(amd_ivf_t* h, uint64_t out[4]);
+/* amd_ivf_search_exact / _resident over the members of a selector only: the filtered ground truth.  (D, I) are, bit for bit, what
+ * amd_ivf_search_exact returns on amd_ivf_subset(h, the same selector); what amd_ivf_search_preassigned_selected returns with
+ * nprobe = nlist and every row of keys 0, 1, ..., nlist - 1; the reference's search_preassigned over every list in list-number order
+ * with the non-members removed -- padding included: a query with fewer than k members ends with id -1 and +-FLT_MAX.  Both work on
+ * amd_ivf_clone contexts; a pending journal is applied first (a selector made before it is then stale, as everywhere).
+ * How: the four stages above over "the lists with the non-members removed".  The seed searches under the selector, so
+ * its k-th distance is that of k members; its nprobe is ceil("exact_seed_nprobe" x ntotal / kept), as many lists as hold the
+ * members that "exact_seed_nprobe" lists hold entries.  The list pass reads a per-block mask of the slots that hold a member where it
+ * read the count of slots that hold an entry: a non-member emits nothing, takes no candidate slot, and over float lists is never
+ * rescored.  Equal distances count among members only.  The general way is amd_ivf_search_preassigned_selected's.
+ * The call goes the general way whole when the unfiltered call would, with k > kept in place of k > ntotal, and when the scaled seed
+ * reaches nlist (the seed would be the whole search); a selector without members is answered on the host with the padding.
+ * Returns -2 before the device is touched for everything amd_ivf_search_exact refuses, a null s, a selector of another index and a
+ * stale selector.
+ * amd_ivf_stats: nq += n, nlist += n x nlist, ndis += n x ntotal of h -- the entries as h holds them, members or not, as under every
+ * selector; nheap_updates by the general-way part only; the seed leaves no trace.  amd_ivf_last_exact / _detail report the call as
+ * they report an unfiltered one; candidates are members only.
+ * Not offered, because no entry point takes them: tickets, the adaptive rule, store_pairs / max_codes, a selector per query. */
+int amd_ivf_search_exact_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, float* D, int64_t* I);
+int amd_ivf_search_exact_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t k, float* D, int64_t* I);
 
 /* InvertedListScanner: set_query + set_list + scan_codes on a caller-owned raw binary heap
  * (simi/idxi, k entries, heapified by the caller as in tests/test_lowlevel_ivf.cpp:150-175);
