@@ -93,4 +93,33 @@ EXACT_HD inline bool exact_float_keep(bool l2, float C, float p, float yn, float
     return t >= bound;
 }
 
+// Which list pass serves a call (exact_slice): 0 none -- the general way whole --, 1 the byte pass, 2 the fp16 pass + rescoring,
+// 3 the workgroup-tiled ("wide") fp16 pass + rescoring.  shape: what every pass needs besides d (centroids for the seed, blocks,
+// ntotal < 2^32, k < cap, k <= members); bytes: the call runs on the lists' byte codes; float_ok: the filter's copies may be used
+// (filter_available: option "filter" != 0, float lists or byte codes not in use); the two options as booleans.  Up to 128
+// dimensions this is the rule that was there before the wide pass, whatever opt_wide says.  Beyond, only the wide pass exists:
+// byte-coded lists have no pass there, and 1024 is where the fp16 copy's row rule changes regime (ivf_filter.hip: half_scale_of).
+// What the caller still has to establish for 2 and 3: ensure_frag16 and a usable fp16 scale of the query rows.
+constexpr int EXACT_NARROW_MAX_D = 128, EXACT_WIDE_MAX_D = 1024;
+inline int exact_pass_kind(int d, bool shape, bool bytes, bool float_ok, bool opt_float, bool opt_wide) {
+    if (!shape || d < 1) return 0;
+    if (d <= EXACT_NARROW_MAX_D) return bytes ? 1 : (float_ok && opt_float ? 2 : 0);
+    if (d <= EXACT_WIDE_MAX_D) return !bytes && float_ok && opt_float && opt_wide ? 3 : 0;
+    return 0;
+}
+
+// The wide pass's tile (scan_all_wide_f16_kernel): four waves walk a slab in chunks of four consecutive blocks, wave w block w; the
+// query operand goes through LDS in stages of `sp` pieces.
+constexpr uint32_t EXACT_WIDE_QUERIES = 128, EXACT_WIDE_CHUNK = 4;
+// stages that cover J pieces
+EXACT_HD inline int exact_wide_stages(int J, int sp) { return (J + sp - 1) / sp; }
+// the slab of the narrow passes rounded up to whole chunks
+inline uint32_t exact_wide_slab(uint32_t slab) { return (slab + (EXACT_WIDE_CHUNK - 1)) & ~(EXACT_WIDE_CHUNK - 1); }
+// blocks of the chunk that starts at block c of a slab that ends before block B1 (c < B1): 4, or 2 in a stream's last chunk
+EXACT_HD inline uint32_t exact_wide_chunk_blocks(uint64_t c, uint64_t B1) {
+    return B1 - c < EXACT_WIDE_CHUNK ? (uint32_t)(B1 - c) : EXACT_WIDE_CHUNK;
+}
+// the block wave w computes in that chunk: its own, or -- where the chunk has none for it -- the chunk's first, result dropped
+EXACT_HD inline uint64_t exact_wide_wave_block(uint64_t c, uint64_t B1, uint32_t w) { return w < exact_wide_chunk_blocks(c, B1) ? c + w : c; }
+
 }  // namespace amdivf

@@ -87,6 +87,7 @@ enum OptId {
                         // by sending every list again (0)
     OPT_EXACT_SEED_NPROBE,  // amd_ivf_search_exact: nprobe of the seed search whose k-th distance is the list pass's threshold
     OPT_EXACT_FLOAT,        // amd_ivf_search_exact over float lists: 1 the fp16 matrix-core list pass + rescoring, 0 (the default) the general way
+    OPT_EXACT_WIDE,         // ... beyond 128 dimensions (up to 1024), with exact_float: 1 the workgroup-tiled fp16 list pass, 0 (the default) the general way
     N_OPT
 };
 struct OptSpec {
@@ -116,6 +117,7 @@ const OptSpec OPT_TABLE[N_OPT] = {
     {"incremental", "AUNCEL_AMD_INCREMENTAL", nullptr},
     {"exact_seed_nprobe", "AUNCEL_AMD_EXACT_SEED", nullptr},
     {"exact_float", "AUNCEL_AMD_EXACT_FLOAT", nullptr},
+    {"exact_wide", "AUNCEL_AMD_EXACT_WIDE", nullptr},
 };
 struct Options {
     // (atomic: amd_ivf_set_option on the owner may run while search contexts cloned from it are searching; a search reads the
@@ -4728,7 +4730,7 @@ static int opt_id(const char* key) {
 static double opt_default(OptId id) {
     switch (id) {
         case OPT_COARSE_TIES: case OPT_TIE_FIX: case OPT_PHASE_TIMING: return -1;
-        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: case OPT_EXACT_FLOAT: return 0;  // (0: chosen per search)
+        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: case OPT_EXACT_FLOAT: case OPT_EXACT_WIDE: return 0;  // (0: chosen per search)
         case OPT_ROUND_FIRST: return 12;
         case OPT_SCAN_PIPELINED: return 7;
         case OPT_FILTER: case OPT_COARSE_PICK: return 2;
@@ -5887,14 +5889,17 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     const uint32_t cap = exact_cap();
     const uint64_t nblk = index->h_block_off.size() == nlist + 1 ? index->h_block_off[nlist] : 0;
     if (sel && sel->keep.cap < nblk / 2 * 8) throw std::runtime_error("exact search: the selector is shorter than the lists");
-    // the list pass runs on byte codes up to four K-steps, under the rule every byte scan runs under
-    const bool shape_ok = index->have_centroids && h->d <= 128 && nblk > 0 && ntotal < 0xffffffffull && k < cap && k <= members;
+    // which list pass (exact_args.h: exact_pass_kind): byte codes up to four K-steps, under the rule every byte scan runs under ...
+    const bool shape_ok = index->have_centroids && nblk > 0 && ntotal < 0xffffffffull && k < cap && k <= members;
     const bool bytes = index->have_codes8 && h->allow_bytes && index->db_range.bytes_with(qr, (size_t)h->d);
-    const bool pass = shape_ok && bytes;
+    int kind = exact_pass_kind(h->d, shape_ok, bytes, filter_available(h, index, bytes), opt(h, OPT_EXACT_FLOAT, 0) != 0,
+                               opt(h, OPT_EXACT_WIDE, 0) != 0);
+    const bool pass = kind == 1;
     // ... and on the filter's fp16 copy of float lists, where lists and queries have a usable scale (ivf_filter.hip: no non-finite
-    // element, magnitudes within 2^+-24, no row tiny beside the largest -- which also keeps every reference distance finite)
+    // element, magnitudes within 2^+-24, no row tiny beside the largest -- which also keeps every reference distance finite);
+    // beyond 128 dimensions by the workgroup-tiled kernel, everything around the launch the same
     hipStream_t s = h->stream;
-    bool pass16 = !pass && shape_ok && filter_available(h, index, bytes) && opt(h, OPT_EXACT_FLOAT, 0) != 0 && ensure_frag16(index);
+    bool pass16 = kind >= 2 && ensure_frag16(index);
     if (pass16) {
         uint32_t info[4] = {0, 0, 0, 0};
         h->w_qinfo.ensure(16);
@@ -5904,6 +5909,8 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         HIP_CHECK(stream_sync(s));
         pass16 = filter_half_scale(info, h->d) != 0.f;
     }
+    if (!pass16 && kind >= 2) kind = 0;
+    const bool wide = kind == 3;
     // ---- 1. seed: an ordinary fixed-nprobe search; its k-th distance is a distance of k stored entries, so the true k-th is within it.
     // Under a selector it is the k-th among the members the seed saw; as `seed` lists hold too few of them when the selector is
     // sparse, nprobe grows by ntotal / kept (exact_args.h) -- and a seed that would read every list is the whole search: the call
@@ -5965,7 +5972,7 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         launch_scan_all(sa, sel != nullptr, s);
     } else {
         // the fp16 query operands and FilterParams by the filter's own launches (the seed search may have left them; not every seed does)
-        h->w_xf.ensure(n * (size_t)filter_steps(h->d) * 8 * sizeof(float));
+        h->w_xf.ensure(n * (size_t)filter_steps(h->d) * 8 * sizeof(float));  // (rows of 8 filter_steps16(d) floats: no more than this)
         h->w_xn.ensure(n * sizeof(float));
         h->w_fparams.ensure(2 * sizeof(FilterParams));
         HIP_CHECK(hipMemsetAsync(h->w_qinfo.p, 0, 16, s));
@@ -5977,7 +5984,7 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         fa.yn = index->d_yn.as<float>();
         fa.blk = sa.blk;
         fa.nblk = nblk;
-        fa.slab = sa.slab;
+        fa.slab = wide ? exact_wide_slab(sa.slab) : sa.slab;
         fa.xf = h->w_xf.as<float>();
         fa.xn = h->w_xn.as<float>();
         fa.params = h->w_fparams.as<FilterParams>();
@@ -5991,7 +5998,8 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         fa.cand = sa.cand;
         fa.cap = cap;
         if (timed) HIP_CHECK(hipEventRecord(ev[0], s));
-        launch_scan_all_f16(fa, sel != nullptr, s);
+        if (wide) launch_scan_all_wide_f16(fa, sel != nullptr, s);
+        else launch_scan_all_f16(fa, sel != nullptr, s);
         ExactRescoreArgs ra{};
         ra.n = (uint32_t)n;
         ra.cap = cap;
@@ -6034,11 +6042,11 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         float a = 0, b = 0;
         (void)hipEventElapsedTime(&a, ev[0], ev[1]);
         (void)hipEventElapsedTime(&b, ev[1], ev[2]);
-        fprintf(stderr, "[exact] n %zu k %zu seed %zu: pass%s %.3f ms, select %.3f ms\n", n, k, seed, pass ? "" : " (fp16 + rescoring)", a, b);
+        fprintf(stderr, "[exact] n %zu k %zu seed %zu: pass%s %.3f ms, select %.3f ms\n", n, k, seed, pass ? "" : wide ? " (wide fp16 + rescoring)" : " (fp16 + rescoring)", a, b);
         for (auto& e : ev) (void)hipEventDestroy(e);
     }
     for (int i = 0; i < 4; i++) out[i] += tot[i];
-    h->last_exact_detail[0] = std::max<uint64_t>(h->last_exact_detail[0], pass ? 1 : 2);
+    h->last_exact_detail[0] = std::max<uint64_t>(h->last_exact_detail[0], (uint64_t)kind);
     h->last_exact_detail[1] += tot[3];
     h->last_exact_detail[2] += tot[4];
     h->last_exact_detail[3] = std::max<uint64_t>(h->last_exact_detail[3], tot[5]);

@@ -346,6 +346,207 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
+// The fp16 list pass beyond 128 dimensions (option "exact_wide").  At J = filter_steps16(d) = 10 .. 64 pieces the
+// query operand no longer fits a wave's registers, so the tile is scan_filter_wide_kernel's (ivf_filter.hip), over the exact pass's
+// block stream.  Grid: (slabs of the block stream, tiles of 128 queries).  The four waves walk the slab in chunks of four
+// consecutive blocks; wave w owns block w of the chunk, whose pieces stream from HBM once, straight into a register ring of SP
+// pieces (the slot of piece j is refilled with piece j + SP right behind its MFMAs; behind a chunk's last stage the slots take the
+// first SP pieces of the wave's block of the NEXT chunk, so the ring stays full across chunks).  The tile's query operand -- up to
+// four query blocks of filter_queries16_kernel's rows, wave w staging the rows of query block w -- goes through LDS in stages of SP
+// pieces, double-buffered, one LDS-only barrier per stage; the stages do not depend on the chunk, so the stage written behind a
+// chunk's last is stage 0 again and the buffers simply alternate along the whole slab.  Four accumulator tiles per wave, the K
+// loop compiled per count of query blocks.  The per-query constants of the keep rule are written to LDS once per workgroup.  The
+// epilogue is scan_all_f16_kernel's: exact_float_keep (non-strict), the block table's count or (KEEP) members' mask, a ballot per
+// four registers, one returning atomic add per candidate, (position, -) stored while the slot is below cap.
+// Every wave runs the same sequence of loads, stages and barriers whatever its share (ivf_filter.hip says why: the compiler's wait
+// counts are exact only in straight-line code): a wave without a query block stages the tile's first row (nothing reads it), a wave
+// without a block in the stream's last chunk (nblk % 4 == 2) recomputes the chunk's first block and drops the result, a piece index
+// past J reads piece J - 1 and its stage slot is written as zero.  Nothing is read past nblk x J KiB of the copy or past row n - 1.
+// (lds_barrier, the stage load / write and the ring are the filter's, written out again here: there they are lambdas over that
+// kernel's locals, and ivf_filter.hip is left as it is.)
+#ifndef AUNCEL_EXACT_WIDE_SP
+#define AUNCEL_EXACT_WIDE_SP 6
+#endif
+constexpr int EXACT_WIDE_SP = AUNCEL_EXACT_WIDE_SP;
+constexpr int EXACT_WIDE_QB = (int)(EXACT_WIDE_QUERIES / 32);
+constexpr size_t EXACT_WIDE_STAGE_FLOATS = (size_t)EXACT_WIDE_QB * EXACT_WIDE_SP * 256;
+constexpr size_t EXACT_WIDE_LDS = 2 * EXACT_WIDE_STAGE_FLOATS * sizeof(float) + 2 * EXACT_WIDE_QUERIES * sizeof(float);
+static_assert(EXACT_WIDE_SP >= 2 && EXACT_WIDE_SP % 2 == 0 && EXACT_WIDE_SP <= 10, "pieces are taken in pairs; a stage is not longer than the fewest pieces");
+static_assert(2 * EXACT_WIDE_LDS <= 160 * 1024, "two workgroups per compute unit");
+// (explicitly global: a generic pointer makes these flat loads, which count on both wait counters and force full waits)
+typedef const v4f __attribute__((address_space(1)))* gv4f;
+
+// workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every global load in flight, which would drain the ring
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+template <int METRIC, bool KEEP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_all_wide_f16_kernel(ExactScanF16Args a) {
+    constexpr bool L2 = METRIC == METRIC_L2;
+    constexpr int QB = EXACT_WIDE_QB, SP = EXACT_WIDE_SP;
+    extern __shared__ __align__(16) unsigned char exact_wide_smem[];
+    float* s_a = reinterpret_cast<float*>(exact_wide_smem);  // [2 buffers][query block][piece of the stage][lane][4]
+    float* s_u = s_a + 2 * EXACT_WIDE_STAGE_FLOATS;
+    float* s_c = s_u + EXACT_WIDE_QUERIES;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int m = lane & 31, h = lane >> 5;
+    const int J = (int)filter_steps16(a.d);
+    const int S = exact_wide_stages(J, SP);
+    const size_t qstride = (size_t)J * 8;
+    const size_t block_floats = (size_t)J * 256;
+    const uint32_t qbase = blockIdx.y * EXACT_WIDE_QUERIES;
+    const uint64_t B0 = (uint64_t)blockIdx.x * a.slab;
+    const uint64_t B1 = B0 + a.slab < a.nblk ? B0 + a.slab : a.nblk;  // (slab: a multiple of 4; nblk is even)
+    if (qbase >= a.n || B0 >= B1) return;                            // (the same for the whole workgroup)
+    const uint32_t nq = a.n - qbase < EXACT_WIDE_QUERIES ? a.n - qbase : EXACT_WIDE_QUERIES;  // query slots of the tile that hold a query
+    const int nqb = (int)((nq + 31) >> 5);
+    const FilterParams fp = *a.params;
+    const float C = fp.C, ps = fp.ps;
+
+    // ---- per query slot, once for the slab: what the keep rule compares with; +inf where nothing may pass (no query, no threshold).
+    // (slot = thread & 127: the upper two waves write what the lower two write)
+    {
+        const uint32_t sl = threadIdx.x & (EXACT_WIDE_QUERIES - 1);
+        const bool sok = sl < nq;
+        const uint32_t q = qbase + (sok ? sl : 0u);
+        const size_t last = (size_t)q * a.k + (a.k - 1);
+        const float tau = a.seed_D[last], xn = a.xn[q];
+        const bool have = sok && a.seed_I[last] >= 0 && tau == tau;
+        s_u[sl] = have ? exact_float_bound(L2, C, xn, tau) : __builtin_inff();
+        s_c[sl] = exact_float_slack(L2, C, xn);
+    }
+    // ---- the query operand: this wave stages the rows of query block `wave`, lane (m, h) halves 16 j + 8 h .. + 7 of query slot
+    // 32 wave + m, piece j (a slot without a query: the tile's first row; its bound is +inf)
+    const uint32_t qslot = (uint32_t)wave * 32u + (uint32_t)m;
+    const float* qp = a.xf + (size_t)(qbase + (qslot < nq ? qslot : 0u)) * qstride + (size_t)h * 4;
+    v4f st[SP];
+    auto stage_load = [&](int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int jj = 0; jj < SP; jj++) {
+            const int j = s * SP + jj;
+            st[jj] = *(gv4f)(uintptr_t)(qp + 8 * (j < J ? j : J - 1));
+        }
+    };
+    auto stage_write = [&](int s, int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int jj = 0; jj < SP; jj++)  // (pieces that pad the last stage contribute 0 x y)
+            *reinterpret_cast<v4f*>(s_a + ((size_t)(buf * QB + wave) * SP + jj) * 256 + (size_t)lane * 4) =
+                s * SP + jj < J ? st[jj] : v4f{0.f, 0.f, 0.f, 0.f};
+    };
+    stage_load(0);
+    stage_write(0, 0);
+    // ---- this wave's block, a ring of SP pieces
+    const float* fbase = a.codes_frag + (size_t)lane * 4;
+    v4f br[SP];
+    {
+        const float* b0 = fbase + exact_wide_wave_block(B0, B1, (uint32_t)wave) * block_floats;
+#pragma unroll
+        for (int jj = 0; jj < SP; jj++) br[jj] = *(gv4f)(uintptr_t)(b0 + (size_t)jj * 256);  // (SP <= 10 <= J)
+    }
+    lds_barrier();  // stage 0 and the per-query constants are in LDS
+
+    auto run = [&](auto NQBc) __attribute__((always_inline)) {
+        constexpr int NQB = decltype(NQBc)::value;
+        int buf = 0;
+        for (uint64_t c = B0; c < B1; c += EXACT_WIDE_CHUNK) {
+            const bool active = (uint32_t)wave < exact_wide_chunk_blocks(c, B1);
+            const uint64_t cur = exact_wide_wave_block(c, B1, (uint32_t)wave);
+            const uint64_t cn = c + EXACT_WIDE_CHUNK < B1 ? c + EXACT_WIDE_CHUNK : c;  // (no next chunk: this one again, never used)
+            const float* bbase = fbase + cur * block_floats;
+            const float* nbase = fbase + exact_wide_wave_block(cn, B1, (uint32_t)wave) * block_floats;
+            const float yn = a.yn[cur * 32 + (uint64_t)m];
+            const uint2 bi = a.blk[cur];
+            v16f acc[NQB];
+#pragma unroll
+            for (int q = 0; q < NQB; q++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) acc[q][r] = 0.f;
+            v4f afA[NQB], afB[NQB];  // the query blocks' operands of an even and an odd piece, read from LDS one MFMA group ahead
+            auto load_a = [&](int bf, int jj, v4f (&af)[NQB]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int q = 0; q < NQB; q++) af[q] = *reinterpret_cast<const v4f*>(s_a + ((size_t)(bf * QB + q) * SP + jj) * 256 + (size_t)lane * 4);
+            };
+            auto mac = [&](const v4f (&af)[NQB], const v4f& bv) __attribute__((always_inline)) {
+#pragma unroll
+                for (int q = 0; q < NQB; q++)
+                    acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, af[q]), __builtin_bit_cast(v8h, bv), acc[q], 0, 0, 0);
+            };
+            for (int s = 0; s < S; s++) {
+                const bool lasts = s + 1 == S;
+                const int sn = lasts ? 0 : s + 1;  // (behind a chunk's last stage: stage 0, for the next chunk)
+                // the refill of ring slot jj: piece j + SP of this block (past J: J - 1 again, multiplied by a zero stage slot), or
+                // behind the last stage piece jj of the wave's block of the next chunk
+                auto refill = [&](int j, int jj, v4f& bv) __attribute__((always_inline)) {
+                    const float* src = lasts ? nbase + (size_t)jj * 256 : bbase + (size_t)(j + SP < J ? j + SP : J - 1) * 256;
+                    bv = *(gv4f)(uintptr_t)src;
+                };
+                stage_load(sn);
+#pragma unroll
+                for (int jj = 0; jj < SP; jj += 2) {
+                    const int j = s * SP + jj;
+                    if (jj == 0) load_a(buf, 0, afA);
+                    load_a(buf, jj + 1, afB);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mac(afA, br[jj]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    refill(j, jj, br[jj]);
+                    if (jj + 2 < SP) load_a(buf, jj + 2, afA);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mac(afB, br[jj + 1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    refill(j + 1, jj + 1, br[jj + 1]);
+                }
+                stage_write(sn, buf ^ 1);  // (last read one stage ago: every wave is past that barrier)
+                lds_barrier();
+                buf ^= 1;
+            }
+            // ---- epilogue: register 4 g + c of lane half h of tile qb belongs to query slot 32 qb + 8 g + 4 h + c, lane m to slot m
+            // of the block; a slot behind the list's end, a non-member, a block computed in another wave's stead: nothing
+            const bool vok = active && (KEEP ? ((bi.y >> m) & 1u) != 0 : (uint32_t)m < bi.y);
+            const uint32_t pos = bi.x + (uint32_t)m;
+            // (opaque per chunk: a tile's 64 query numbers, their tests against nq and the counter and buffer addresses do not change
+            // along the slab, and hoisted out of the chunk loop they were 64 vector and 128 scalar registers, spilled)
+            int h4 = 4 * h;
+            asm volatile("" : "+v"(h4));
+            static_for(std::make_integer_sequence<int, NQB>{}, [&](auto T) __attribute__((always_inline)) {
+                constexpr int qb = decltype(T)::value * 32;
+                static_for(std::make_integer_sequence<int, 4>{}, [&](auto G) __attribute__((always_inline)) {
+                    constexpr int g = decltype(G)::value;
+                    const v4f tu = *reinterpret_cast<const v4f*>(&s_u[qb + 8 * g + h4]);
+                    const v4f tc = *reinterpret_cast<const v4f*>(&s_c[qb + 8 * g + h4]);
+                    bool keep[4];
+                    bool any = false;
+#pragma unroll
+                    for (int c4 = 0; c4 < 4; c4++) {
+                        keep[c4] = vok && exact_float_keep(L2, C, ps * acc[qb / 32][4 * g + c4], yn, tu[c4], tc[c4]);  // (ps: a power of two, exact)
+                        any |= keep[c4];
+                    }
+                    if (__ballot(any) == 0) return;
+#pragma unroll
+                    for (int c4 = 0; c4 < 4; c4++) {
+                        const int sl = qb + 8 * g + h4 + c4;
+                        if (keep[c4] && (uint32_t)sl < nq) {
+                            const uint32_t q = qbase + (uint32_t)sl;
+                            const uint32_t slot = atomicAdd(&a.cnt[q], 1u);  // (beyond cap only the counter moves)
+                            if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = make_uint2(pos, 0u);
+                        }
+                    }
+                });
+            });
+        }
+    };
+    switch (nqb) {
+        case 1: run(std::integral_constant<int, 1>{}); break;
+        case 2: run(std::integral_constant<int, 2>{}); break;
+        case 3: run(std::integral_constant<int, 3>{}); break;
+        default: run(std::integral_constant<int, 4>{}); break;
+    }
+}
+
 // The candidates of the fp16 pass recomputed from the fp32 rows in the reference's rounding sequence (ivf_dev.h: exact_distance; as in
 // rescore_kernel four neighbouring lanes take one candidate, lane l running sum l, then (s0 + s1) + (s2 + s3)): the distance's bits
 // replace the candidate's second word.  A workgroup per query, 64 candidates a trip.
@@ -527,6 +728,25 @@ void launch_scan_all_f16(const ExactScanF16Args& a, bool keep, hipStream_t s) {
     };
     if (keep) pick(std::true_type{});
     else pick(std::false_type{});
+}
+
+void launch_scan_all_wide_f16(const ExactScanF16Args& a, bool keep, hipStream_t s) {
+    if (a.n == 0 || a.nblk == 0) return;
+    if (a.d <= EXACT_NARROW_MAX_D || a.d > EXACT_WIDE_MAX_D || a.slab == 0 || (a.slab & (EXACT_WIDE_CHUNK - 1)) || (a.nblk & 1))
+        throw std::runtime_error("scan_all_wide_f16_kernel: shape not supported");
+    const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + EXACT_WIDE_QUERIES - 1) / EXACT_WIDE_QUERIES)), block(256);
+    auto go = [&](auto kern) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXACT_WIDE_LDS);
+        if (e != hipSuccess) throw std::runtime_error(std::string("scan_all_wide_f16_kernel: cannot reserve LDS: ") + hipGetErrorString(e));
+        LAUNCH(kern, grid, block, EXACT_WIDE_LDS, s, a);
+    };
+    if (a.metric == METRIC_L2) {
+        if (keep) go(scan_all_wide_f16_kernel<METRIC_L2, true>);
+        else go(scan_all_wide_f16_kernel<METRIC_L2, false>);
+    } else {
+        if (keep) go(scan_all_wide_f16_kernel<METRIC_IP, true>);
+        else go(scan_all_wide_f16_kernel<METRIC_IP, false>);
+    }
 }
 
 void launch_exact_rescore(const ExactRescoreArgs& a, hipStream_t s) {

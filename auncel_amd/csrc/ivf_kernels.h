@@ -825,6 +825,9 @@ uint32_t exact_slab_blocks(uint64_t nblk, uint32_t n);
 // keep: a.blk is launch_exact_blocks_keep's table (the members' mask), else launch_exact_blocks' (the entries' count)
 void launch_scan_all(const ExactScanArgs& a, bool keep, hipStream_t s);
 void launch_scan_all_f16(const ExactScanF16Args& a, bool keep, hipStream_t s);
+// the same pass for 128 < d <= 1024 (option "exact_wide"): a workgroup tile of 128 queries x 4 blocks, the query operand through LDS;
+// a.slab is a multiple of 4 (exact_args.h: exact_wide_slab)
+void launch_scan_all_wide_f16(const ExactScanF16Args& a, bool keep, hipStream_t s);
 void launch_exact_rescore(const ExactRescoreArgs& a, hipStream_t s);
 void launch_exact_select(const ExactSelectArgs& a, hipStream_t s);
 

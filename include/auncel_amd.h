@@ -215,7 +215,12 @@ int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t npro
  * lost -- each emitted entry's distance is recomputed from the fp32 rows in the reference's rounding sequence, and the selection
  * drops what lies strictly beyond the threshold before it looks for equal distances.  Option "exact_float" = 1 switches it on;
  * without it such calls go the general way whole, as they always did.
- * A call goes the general way whole when it does not qualify: d > 128, k > ntotal, k >= the candidate slots, no centroids; for the
+ * Beyond 128 dimensions, up to 1024, the same pass exists as a workgroup tile (scan_all_wide_f16_kernel: 128 queries x 4 list blocks,
+ * the query operand through LDS); it serves a call when option "exact_wide" = 1 is set beside "exact_float" = 1 and every other
+ * condition of the fp16 pass holds, and amd_ivf_last_exact_detail then reports pass 3.  Still the general way whole: d > 1024, and
+ * byte-valued lists beyond 128 dimensions whose byte codes are in use (their general way is the int8 matrix-core scan already; with
+ * amd_ivf_set_byte_codes(h, 0), or queries outside the byte rule, they take the wide pass as float lists do).
+ * A call goes the general way whole when it does not qualify: d > 128 (d > 1024 or no "exact_wide" for the fp16 pass), k > ntotal, k >= the candidate slots, no centroids; for the
  * fp16 pass also option "exact_float" 0, option "filter" below 2, and lists or queries of the call without a usable fp16 scale (a non-finite element,
  * magnitudes outside 2^+-24, a row that is not all zero whose largest element is below 2^-12 of the matrix's).
  * Returns -2 before the device is touched for: a null h, k = 0, null x / D / I with n > 0, a resident range that wraps round; -2 for
@@ -227,11 +232,11 @@ int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t npro
  * because equal distances met, out[2] queries searched the general way for any other reason (candidate overflow, no full seed
  * result, the whole call not qualifying), out[3] candidates the list pass emitted (the fp16 pass: before rescoring), summed over
  * the call.
- * amd_ivf_last_exact_detail: out[0] the list pass the last exact call ran (0 none, 1 bytes, 2 fp16 + rescoring), out[1] candidates
+ * amd_ivf_last_exact_detail: out[0] the list pass the last exact call ran (0 none, 1 bytes, 2 fp16 + rescoring, 3 wide fp16 + rescoring), out[1] candidates
  * emitted, out[2] candidates at or within the threshold (the fp16 pass: after rescoring, among the stored ones; the byte pass emits
  * nothing else: out[1]), out[3] the largest emitted count of any one query -- what the candidate slots have to hold.
  * AUNCEL_AMD_EXACT_CAP=<n> (a test knob, read once per process): candidate slots per query, 2..4096 (default 1024).
- * Not offered: d > 128 in the pass, tickets, store_pairs / max_codes, the adaptive rule -- there is no exact entry point that takes
+ * Not offered: d > 128 in the pass unless option "exact_wide" asks for it (float lists up to d = 1024), tickets, store_pairs / max_codes, the adaptive rule -- there is no exact entry point that takes
  * any of them.  (Selectors: below.) */
 int amd_ivf_search_exact(amd_ivf_t* h, size_t n, const float* x, size_t k, float* D, int64_t* I);
 int amd_ivf_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, float* D, int64_t* I);
@@ -594,6 +599,9 @@ int amd_ivf_set_byte_codes(amd_ivf_t* h, int enable);
  *                     threshold (at most nlist; AUNCEL_AMD_EXACT_SEED is the environment's form).  Cannot change a result
  *   "exact_float"     amd_ivf_search_exact over float lists: 1 the fp16 matrix-core list pass with rescoring, 0 the general      0
  *                     way for the whole call (AUNCEL_AMD_EXACT_FLOAT is the environment's form).  Cannot change a result
+ *   "exact_wide"      ... beyond 128 dimensions (128 < d <= 1024), beside "exact_float" = 1: 1 the workgroup-tiled fp16 list     0
+ *                     pass with rescoring, 0 the general way for the whole call (AUNCEL_AMD_EXACT_WIDE is the environment's
+ *                     form).  Cannot change a result
  * amd_ivf_set_option(h, key, NAN) returns the key to "unset".  May be called while search contexts of the index are searching: a
  * search reads what shapes its launches once, when it starts, so the change takes effect with the searches that start after it. */
 int amd_ivf_set_option(amd_ivf_t* h, const char* key, double value);
