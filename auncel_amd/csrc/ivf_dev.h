@@ -169,6 +169,16 @@ template <int METRIC> __device__ __forceinline__ float exact_distance(const floa
     return (s0 + s1) + (s2 + s3);
 }
 
+// the list that holds 32-vector block `blk` of the fragment copies: the largest l with block_off[l] <= blk
+__device__ __forceinline__ uint32_t list_of_block(const uint64_t* block_off, uint32_t nlist, uint64_t blk) {
+    uint32_t lo = 0, hi = nlist;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (block_off[mid] <= blk) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
 
 template <int... I, class F> __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
     (f(std::integral_constant<int, I>{}), ...);

@@ -5939,11 +5939,7 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     h->w_ex_tot.ensure(6 * 8);
     h->w_ex_D.ensure(n * k * sizeof(float));
     h->w_ex_I.ensure(n * k * sizeof(int64_t));
-    if (sel)
-        launch_exact_blocks_keep(index->d_list_off.as<uint64_t>(), index->d_block_off.as<uint64_t>(), keep, (uint32_t)nlist, nblk,
-                                 h->w_ex_blk.as<uint2>(), s);
-    else
-        launch_exact_blocks(index->d_list_off.as<uint64_t>(), index->d_block_off.as<uint64_t>(), (uint32_t)nlist, nblk, h->w_ex_blk.as<uint2>(), s);
+    launch_exact_blocks(index->d_list_off.as<uint64_t>(), index->d_block_off.as<uint64_t>(), keep, (uint32_t)nlist, nblk, h->w_ex_blk.as<uint2>(), s);
     HIP_CHECK(hipMemsetAsync(h->w_ex_cnt.p, 0, n * 4, s));
     HIP_CHECK(hipMemsetAsync(h->w_ex_tot.p, 0, 6 * 8, s));
     ExactScanArgs sa{};

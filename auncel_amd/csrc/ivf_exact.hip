@@ -3,8 +3,8 @@
 // consecutive blocks, and a block that has been fetched is contracted with every query block of the tile before it is let go.
 //   scan_all_kernel      the list pass: emits, per query, every stored entry at or within the query's threshold (the k-th distance of
 //                        a seed search of the same lists) as (global position, distance)
-//   exact_blocks_keep_kernel  the block table of a call under an id selector: the mask of a block's slots that hold a MEMBER, so the
-//                        same pass (KEEP) emits members only with nothing added to its loop
+//   exact_blocks_kernel  the block table the pass reads; <KEEP>, of a call under an id selector: the mask of a block's slots that hold a
+//                        MEMBER, so the same pass (KEEP) emits members only with nothing added to its loop
 //   exact_select_kernel  a wave per query: the candidates in (distance, position) order; the result is read off them when no two
 //                        neighbours of the best k + 1 are equal (exact_args.h: exact_window_tied), else the query is flagged and
 //                        the caller searches it the general way
@@ -15,7 +15,7 @@
 #include <algorithm>
 
 #include "exact_args.h"
-#include "ivf_dev.h"
+#include "mfma_tile.h"
 
 namespace amdivf {
 
@@ -23,45 +23,24 @@ namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 
 // per 32-vector block of the fragment copy: (global position of its first slot, slots that hold an entry).  A list is padded to an
 // even number of blocks: the block in which a list ends holds fewer than 32 entries, the padding block behind it none.
-__global__ __launch_bounds__(256) void exact_blocks_kernel(const uint64_t* __restrict__ list_off, const uint64_t* __restrict__ block_off,
-                                                           uint32_t nlist, uint64_t nblk, uint2* __restrict__ out) {
-    const uint64_t blk = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (blk >= nblk) return;
-    uint32_t lo = 0, hi = nlist;  // largest l with block_off[l] <= blk
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (block_off[mid] <= blk) lo = mid;
-        else hi = mid;
-    }
-    const uint64_t p = (blk - block_off[lo]) * 32, size = list_off[lo + 1] - list_off[lo];
-    const uint64_t left = p < size ? size - p : 0;
-    out[blk] = make_uint2((uint32_t)(list_off[lo] + p), (uint32_t)(left < 32 ? left : 32));
-}
-
-// The table of a call under a selector: (global position of the block's first slot, VALID MASK) -- bit m is set iff slot m holds an
-// entry and the selector keeps it (exact_args.h: exact_block_valid_mask).  keep: the selector's words, a bit per slot of the padded
+// KEEP, the table of a call under a selector: (global position of the block's first slot, VALID MASK) -- bit m is set iff slot m holds
+// an entry and the selector keeps it (exact_args.h: exact_block_valid_mask).  keep: the selector's words, a bit per slot of the padded
 // layout, so block b's 32 bits are half b & 1 of word b >> 1.  The list pass reads the mask where it read the count: a non-member is
 // a slot behind the list's end to it, and nothing is added to its loop.
-__global__ __launch_bounds__(256) void exact_blocks_keep_kernel(const uint64_t* __restrict__ list_off, const uint64_t* __restrict__ block_off,
-                                                                const unsigned long long* __restrict__ keep, uint32_t nlist, uint64_t nblk,
-                                                                uint2* __restrict__ out) {
+template <bool KEEP>
+__global__ __launch_bounds__(256) void exact_blocks_kernel(const uint64_t* __restrict__ list_off, const uint64_t* __restrict__ block_off,
+                                                           uint32_t nlist, uint64_t nblk, uint2* __restrict__ out,
+                                                           const unsigned long long* __restrict__ keep) {
     const uint64_t blk = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (blk >= nblk) return;
-    uint32_t lo = 0, hi = nlist;  // largest l with block_off[l] <= blk
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (block_off[mid] <= blk) lo = mid;
-        else hi = mid;
-    }
+    const uint32_t lo = list_of_block(block_off, nlist, blk);
     const uint64_t p = (blk - block_off[lo]) * 32, size = list_off[lo + 1] - list_off[lo];
     const uint64_t left = p < size ? size - p : 0;
-    out[blk] = make_uint2((uint32_t)(list_off[lo] + p), exact_block_valid_mask(left, exact_block_keep_half(keep[blk >> 1], blk)));
+    const uint32_t y = KEEP ? exact_block_valid_mask(left, exact_block_keep_half(keep[blk >> 1], blk)) : (uint32_t)(left < 32 ? left : 32);
+    out[blk] = make_uint2((uint32_t)(list_off[lo] + p), y);
 }
 
 // keys[i][l] = l: the ranking under which the general way visits every list in list-number order
@@ -78,7 +57,7 @@ __global__ __launch_bounds__(256) void identity_keys_kernel(int64_t* __restrict_
 // it is how a tie at the k-th is seen.  The pre-test is the pair kernel's strict one against T + 1 (L2: made even, so loosened by at
 // most one more) / T - 1 (IP); a register that passes it recomputes the distance and tests it exactly.  Slots behind a list's end
 // (ExactScanArgs::blk says how many of a block's 32 are entries) never pass: their bound is INT_MAX.
-// KEEP (a call under a selector): blk.y is the mask of the slots that hold a MEMBER (exact_blocks_keep_kernel) and a slot is live iff
+// KEEP (a call under a selector): blk.y is the mask of the slots that hold a MEMBER (exact_blocks_kernel<true>) and a slot is live iff
 // its bit is set -- a non-member is treated exactly as a slot behind the list's end: it emits nothing, takes no candidate slot and
 // moves no counter.  KEEP = false is the unfiltered pass, instruction for instruction what it was before the parameter existed.
 template <int METRIC, int NKS, bool KEEP>
@@ -221,6 +200,45 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
     }
 }
 
+// What the two fp16 list passes below share: a query slot's constants and the epilogue of an accumulator tile.
+// A query slot's side of the keep rule: u = what an entry's side is compared with, +inf where nothing may pass (ok false: no query
+// in the slot, then q is any valid query; no threshold), c = the factor of |y|.  Returns (u, c).
+template <bool L2> __device__ __forceinline__ float2 exact_f16_slot(const ExactScanF16Args& a, float C, uint32_t q, bool ok) {
+    const size_t last = (size_t)q * a.k + (a.k - 1);
+    const float tau = a.seed_D[last], xn = a.xn[q];
+    const bool have = ok && a.seed_I[last] >= 0 && tau == tau;
+    return make_float2(have ? exact_float_bound(L2, C, xn, tau) : __builtin_inff(), exact_float_slack(L2, C, xn));
+}
+// The epilogue of one 32 x 32 accumulator tile: register 4 g + c of lane half h belongs to query slot QB0 + 8 g + 4 h + c of
+// qbase's nq (s_u, s_c: exact_f16_slot's values by slot), lane m to the entry at `pos` (vok: it may be emitted; yn: its norm).  Four
+// registers at a time, most hold nothing: exact_float_keep, a ballot, one returning atomic add per candidate.  h4 = 4 h.
+template <bool L2, int QB0>
+__device__ __forceinline__ void exact_f16_emit(const ExactScanF16Args& a, const v16f& acc, const float* s_u, const float* s_c, int h4, uint32_t qbase,
+                                               uint32_t nq, float C, float ps, bool vok, float yn, uint32_t pos) {
+    static_for(std::make_integer_sequence<int, 4>{}, [&](auto G) __attribute__((always_inline)) {
+        constexpr int g = decltype(G)::value;
+        const v4f tu = *reinterpret_cast<const v4f*>(&s_u[QB0 + 8 * g + h4]);
+        const v4f tc = *reinterpret_cast<const v4f*>(&s_c[QB0 + 8 * g + h4]);
+        bool keep[4];
+        bool any = false;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            keep[c] = vok && exact_float_keep(L2, C, ps * acc[4 * g + c], yn, tu[c], tc[c]);  // (ps: a power of two, exact)
+            any |= keep[c];
+        }
+        if (__ballot(any) == 0) return;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const int sl = QB0 + 8 * g + h4 + c;
+            if (keep[c] && (uint32_t)sl < nq) {
+                const uint32_t q = qbase + (uint32_t)sl;
+                const uint32_t slot = atomicAdd(&a.cnt[q], 1u);  // (beyond cap only the counter moves)
+                if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = make_uint2(pos, 0u);
+            }
+        }
+    });
+}
+
 // The list pass over float lists: the same grid, slabs, query tiles and block stream, on the fp16 copy the filter keeps (ivf_filter.hip:
 // a block is NJ pieces of 1 KiB, 16 dimensions each, in the operand order of v_mfma_f32_32x32x16_f16; the query rows are
 // filter_queries16_kernel's).  Wave w holds the A operands of its two query blocks -- NJ pieces of four registers each -- for the
@@ -255,12 +273,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- per query slot (slot = lane): what the keep rule compares with; +inf where nothing may pass (no query, no threshold)
     {
         const bool sok = (uint32_t)lane < nq;
-        const uint32_t q = qbase + (sok ? (uint32_t)lane : 0u);
-        const size_t last = (size_t)q * a.k + (a.k - 1);
-        const float tau = a.seed_D[last], xn = a.xn[q];
-        const bool have = sok && a.seed_I[last] >= 0 && tau == tau;
-        s_u[wave][lane] = have ? exact_float_bound(L2, C, xn, tau) : __builtin_inff();
-        s_c[wave][lane] = exact_float_slack(L2, C, xn);
+        const float2 uc = exact_f16_slot<L2>(a, C, qbase + (sok ? (uint32_t)lane : 0u), sok);
+        s_u[wave][lane] = uc.x;
+        s_c[wave][lane] = uc.y;
     }
     // ---- the A operands: lane (m, h) of query block g holds halves 16 j + 8 h .. + 7 of query slot 32 g + m, piece j
     v4f af0[NJ], af1[NJ];
@@ -311,34 +326,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __builtin_amdgcn_sched_barrier(0);
         fetch(b, ynv, biv, i + 2 < B1 ? i + 2 : i);  // (past the slab's end: its own block again, never used)
         __builtin_amdgcn_sched_barrier(0);
-        auto epilogue = [&](const v16f& acc, auto QB) {
-            constexpr int qb = decltype(QB)::value;
-            static_for(std::make_integer_sequence<int, 4>{}, [&](auto G) {
-                constexpr int g = decltype(G)::value;
-                // register 4 g + c of lane half h belongs to query slot qb + 8 g + 4 h + c: four registers at a time, most hold nothing
-                const v4f tu = *reinterpret_cast<const v4f*>(&s_u[wave][qb + 8 * g + 4 * h]);
-                const v4f tc = *reinterpret_cast<const v4f*>(&s_c[wave][qb + 8 * g + 4 * h]);
-                bool keep[4];
-                bool any = false;
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    keep[c] = vok && exact_float_keep(L2, C, ps * acc[4 * g + c], yn, tu[c], tc[c]);  // (ps: a power of two, exact)
-                    any |= keep[c];
-                }
-                if (__ballot(any) == 0) return;
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const int sl = qb + 8 * g + 4 * h + c;
-                    if (keep[c] && (uint32_t)sl < nq) {
-                        const uint32_t q = qbase + (uint32_t)sl;
-                        const uint32_t slot = atomicAdd(&a.cnt[q], 1u);  // (beyond cap only the counter moves)
-                        if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = make_uint2(pos, 0u);
-                    }
-                }
-            });
-        };
-        epilogue(acc0, std::integral_constant<int, 0>{});
-        if (two) epilogue(acc1, std::integral_constant<int, 32>{});
+        exact_f16_emit<L2, 0>(a, acc0, s_u[wave], s_c[wave], 4 * h, qbase, nq, C, ps, vok, yn, pos);
+        if (two) exact_f16_emit<L2, 32>(a, acc1, s_u[wave], s_c[wave], 4 * h, qbase, nq, C, ps, vok, yn, pos);
     };
     for (uint64_t i = B0; i < B1; i += 2) {
         step(b0, yn0, bi0, i);
@@ -358,30 +347,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // loop compiled per count of query blocks.  The per-query constants of the keep rule are written to LDS once per workgroup.  The
 // epilogue is scan_all_f16_kernel's: exact_float_keep (non-strict), the block table's count or (KEEP) members' mask, a ballot per
 // four registers, one returning atomic add per candidate, (position, -) stored while the slot is below cap.
-// Every wave runs the same sequence of loads, stages and barriers whatever its share (ivf_filter.hip says why: the compiler's wait
-// counts are exact only in straight-line code): a wave without a query block stages the tile's first row (nothing reads it), a wave
-// without a block in the stream's last chunk (nblk % 4 == 2) recomputes the chunk's first block and drops the result, a piece index
-// past J reads piece J - 1 and its stage slot is written as zero.  Nothing is read past nblk x J KiB of the copy or past row n - 1.
-// (lds_barrier, the stage load / write and the ring are the filter's, written out again here: there they are lambdas over that
-// kernel's locals, and ivf_filter.hip is left as it is.)
+// Straight-line code (mfma_tile.h says why): every wave runs the same loads, stages and barriers whatever its share -- a wave without
+// a query block stages the tile's first row (nothing reads it), a wave without a block in the stream's last chunk (nblk % 4 == 2)
+// recomputes the chunk's first block and drops the result, a piece index past J reads piece J - 1 and its stage slot is written as
+// zero.  Nothing is read past nblk x J KiB of the copy or past row n - 1.
 #ifndef AUNCEL_EXACT_WIDE_SP
-#define AUNCEL_EXACT_WIDE_SP 6
+#define AUNCEL_EXACT_WIDE_SP 6  // (as AUNCEL_FILTER_WIDE_SP, ivf_filter.hip: that kernel spilled at 8)
 #endif
 constexpr int EXACT_WIDE_SP = AUNCEL_EXACT_WIDE_SP;
 constexpr int EXACT_WIDE_QB = (int)(EXACT_WIDE_QUERIES / 32);
-constexpr size_t EXACT_WIDE_STAGE_FLOATS = (size_t)EXACT_WIDE_QB * EXACT_WIDE_SP * 256;
-constexpr size_t EXACT_WIDE_LDS = 2 * EXACT_WIDE_STAGE_FLOATS * sizeof(float) + 2 * EXACT_WIDE_QUERIES * sizeof(float);
+constexpr size_t EXACT_WIDE_LDS = wide_lds_bytes(EXACT_WIDE_QB, EXACT_WIDE_SP, 2);  // (the stages + bound and slack per query)
 static_assert(EXACT_WIDE_SP >= 2 && EXACT_WIDE_SP % 2 == 0 && EXACT_WIDE_SP <= 10, "pieces are taken in pairs; a stage is not longer than the fewest pieces");
 static_assert(2 * EXACT_WIDE_LDS <= 160 * 1024, "two workgroups per compute unit");
-// (explicitly global: a generic pointer makes these flat loads, which count on both wait counters and force full waits)
-typedef const v4f __attribute__((address_space(1)))* gv4f;
-
-// workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every global load in flight, which would drain the ring
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 template <int METRIC, bool KEEP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_all_wide_f16_kernel(ExactScanF16Args a) {
@@ -389,7 +366,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr int QB = EXACT_WIDE_QB, SP = EXACT_WIDE_SP;
     extern __shared__ __align__(16) unsigned char exact_wide_smem[];
     float* s_a = reinterpret_cast<float*>(exact_wide_smem);  // [2 buffers][query block][piece of the stage][lane][4]
-    float* s_u = s_a + 2 * EXACT_WIDE_STAGE_FLOATS;
+    float* s_u = s_a + 2 * wide_stage_floats(QB, SP);
     float* s_c = s_u + EXACT_WIDE_QUERIES;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -412,33 +389,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     {
         const uint32_t sl = threadIdx.x & (EXACT_WIDE_QUERIES - 1);
         const bool sok = sl < nq;
-        const uint32_t q = qbase + (sok ? sl : 0u);
-        const size_t last = (size_t)q * a.k + (a.k - 1);
-        const float tau = a.seed_D[last], xn = a.xn[q];
-        const bool have = sok && a.seed_I[last] >= 0 && tau == tau;
-        s_u[sl] = have ? exact_float_bound(L2, C, xn, tau) : __builtin_inff();
-        s_c[sl] = exact_float_slack(L2, C, xn);
+        const float2 uc = exact_f16_slot<L2>(a, C, qbase + (sok ? sl : 0u), sok);
+        s_u[sl] = uc.x;
+        s_c[sl] = uc.y;
     }
     // ---- the query operand: this wave stages the rows of query block `wave`, lane (m, h) halves 16 j + 8 h .. + 7 of query slot
     // 32 wave + m, piece j (a slot without a query: the tile's first row; its bound is +inf)
     const uint32_t qslot = (uint32_t)wave * 32u + (uint32_t)m;
-    const float* qp = a.xf + (size_t)(qbase + (qslot < nq ? qslot : 0u)) * qstride + (size_t)h * 4;
+    const WideTile<true, SP, QB> tile{s_a, a.xf + (size_t)(qbase + (qslot < nq ? qslot : 0u)) * qstride + (size_t)h * 4, J, wave, lane};
     v4f st[SP];
-    auto stage_load = [&](int s) __attribute__((always_inline)) {
-#pragma unroll
-        for (int jj = 0; jj < SP; jj++) {
-            const int j = s * SP + jj;
-            st[jj] = *(gv4f)(uintptr_t)(qp + 8 * (j < J ? j : J - 1));
-        }
-    };
-    auto stage_write = [&](int s, int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int jj = 0; jj < SP; jj++)  // (pieces that pad the last stage contribute 0 x y)
-            *reinterpret_cast<v4f*>(s_a + ((size_t)(buf * QB + wave) * SP + jj) * 256 + (size_t)lane * 4) =
-                s * SP + jj < J ? st[jj] : v4f{0.f, 0.f, 0.f, 0.f};
-    };
-    stage_load(0);
-    stage_write(0, 0);
+    tile.stage_load(0, st);
+    tile.stage_write(0, 0, st);
     // ---- this wave's block, a ring of SP pieces
     const float* fbase = a.codes_frag + (size_t)lane * 4;
     v4f br[SP];
@@ -465,43 +426,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int q = 0; q < NQB; q++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) acc[q][r] = 0.f;
-            v4f afA[NQB], afB[NQB];  // the query blocks' operands of an even and an odd piece, read from LDS one MFMA group ahead
-            auto load_a = [&](int bf, int jj, v4f (&af)[NQB]) __attribute__((always_inline)) {
-#pragma unroll
-                for (int q = 0; q < NQB; q++) af[q] = *reinterpret_cast<const v4f*>(s_a + ((size_t)(bf * QB + q) * SP + jj) * 256 + (size_t)lane * 4);
-            };
-            auto mac = [&](const v4f (&af)[NQB], const v4f& bv) __attribute__((always_inline)) {
-#pragma unroll
-                for (int q = 0; q < NQB; q++)
-                    acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, af[q]), __builtin_bit_cast(v8h, bv), acc[q], 0, 0, 0);
-            };
             for (int s = 0; s < S; s++) {
                 const bool lasts = s + 1 == S;
-                const int sn = lasts ? 0 : s + 1;  // (behind a chunk's last stage: stage 0, for the next chunk)
                 // the refill of ring slot jj: piece j + SP of this block (past J: J - 1 again, multiplied by a zero stage slot), or
                 // behind the last stage piece jj of the wave's block of the next chunk
                 auto refill = [&](int j, int jj, v4f& bv) __attribute__((always_inline)) {
                     const float* src = lasts ? nbase + (size_t)jj * 256 : bbase + (size_t)(j + SP < J ? j + SP : J - 1) * 256;
                     bv = *(gv4f)(uintptr_t)src;
                 };
-                stage_load(sn);
-#pragma unroll
-                for (int jj = 0; jj < SP; jj += 2) {
-                    const int j = s * SP + jj;
-                    if (jj == 0) load_a(buf, 0, afA);
-                    load_a(buf, jj + 1, afB);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mac(afA, br[jj]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    refill(j, jj, br[jj]);
-                    if (jj + 2 < SP) load_a(buf, jj + 2, afA);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mac(afB, br[jj + 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    refill(j + 1, jj + 1, br[jj + 1]);
-                }
-                stage_write(sn, buf ^ 1);  // (last read one stage ago: every wave is past that barrier)
-                lds_barrier();
+                tile.stage<NQB>(buf, s, lasts ? 0 : s + 1, st, acc, br, refill);  // (behind a chunk's last stage: stage 0, for the next chunk)
                 buf ^= 1;
             }
             // ---- epilogue: register 4 g + c of lane half h of tile qb belongs to query slot 32 qb + 8 g + 4 h + c, lane m to slot m
@@ -513,29 +446,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             int h4 = 4 * h;
             asm volatile("" : "+v"(h4));
             static_for(std::make_integer_sequence<int, NQB>{}, [&](auto T) __attribute__((always_inline)) {
-                constexpr int qb = decltype(T)::value * 32;
-                static_for(std::make_integer_sequence<int, 4>{}, [&](auto G) __attribute__((always_inline)) {
-                    constexpr int g = decltype(G)::value;
-                    const v4f tu = *reinterpret_cast<const v4f*>(&s_u[qb + 8 * g + h4]);
-                    const v4f tc = *reinterpret_cast<const v4f*>(&s_c[qb + 8 * g + h4]);
-                    bool keep[4];
-                    bool any = false;
-#pragma unroll
-                    for (int c4 = 0; c4 < 4; c4++) {
-                        keep[c4] = vok && exact_float_keep(L2, C, ps * acc[qb / 32][4 * g + c4], yn, tu[c4], tc[c4]);  // (ps: a power of two, exact)
-                        any |= keep[c4];
-                    }
-                    if (__ballot(any) == 0) return;
-#pragma unroll
-                    for (int c4 = 0; c4 < 4; c4++) {
-                        const int sl = qb + 8 * g + h4 + c4;
-                        if (keep[c4] && (uint32_t)sl < nq) {
-                            const uint32_t q = qbase + (uint32_t)sl;
-                            const uint32_t slot = atomicAdd(&a.cnt[q], 1u);  // (beyond cap only the counter moves)
-                            if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = make_uint2(pos, 0u);
-                        }
-                    }
-                });
+                constexpr int t = decltype(T)::value;
+                exact_f16_emit<L2, 32 * t>(a, acc[t], s_u, s_c, h4, qbase, nq, C, ps, vok, yn, pos);
             });
         }
     };
@@ -652,15 +564,12 @@ template <bool RESCORED> __global__ __launch_bounds__(64) void exact_select_kern
 
 }  // namespace
 
-void launch_exact_blocks(const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, uint64_t nblk, uint2* out, hipStream_t s) {
+void launch_exact_blocks(const uint64_t* list_off, const uint64_t* block_off, const unsigned long long* keep, uint32_t nlist, uint64_t nblk,
+                         uint2* out, hipStream_t s) {
     if (nblk == 0) return;
-    LAUNCH(exact_blocks_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, s, list_off, block_off, nlist, nblk, out);
-}
-
-void launch_exact_blocks_keep(const uint64_t* list_off, const uint64_t* block_off, const unsigned long long* keep, uint32_t nlist, uint64_t nblk,
-                              uint2* out, hipStream_t s) {
-    if (nblk == 0) return;
-    LAUNCH(exact_blocks_keep_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, s, list_off, block_off, keep, nlist, nblk, out);
+    const dim3 grid((unsigned)((nblk + 255) / 256)), block(256);
+    if (keep) LAUNCH(exact_blocks_kernel<true>, grid, block, 0, s, list_off, block_off, nlist, nblk, out, keep);
+    else LAUNCH(exact_blocks_kernel<false>, grid, block, 0, s, list_off, block_off, nlist, nblk, out, keep);
 }
 
 void launch_identity_keys(int64_t* keys, size_t rows, uint32_t nlist, hipStream_t s) {
@@ -678,31 +587,32 @@ uint32_t exact_slab_blocks(uint64_t nblk, uint32_t n) {
     return (uint32_t)std::min<uint64_t>(slab, 1u << 30);
 }
 
+// f(metric, keep as compile-time constants): the instantiation of a list pass for a call's metric and table variant
+template <class F> static void with_metric_keep(int metric, bool keep, F&& f) {
+    auto pick = [&](auto K) {
+        if (metric == METRIC_L2) f(std::integral_constant<int, METRIC_L2>{}, K);
+        else f(std::integral_constant<int, METRIC_IP>{}, K);
+    };
+    if (keep) pick(std::true_type{});
+    else pick(std::false_type{});
+}
+
 void launch_scan_all(const ExactScanArgs& a, bool keep, hipStream_t s) {
     if (a.n == 0 || a.nblk == 0) return;
     const int ks = (int)mfma_ksteps(a.d);
     if (ks < 1 || ks > 4 || a.slab == 0 || (a.slab & 1) || (a.nblk & 1)) throw std::runtime_error("scan_all_kernel: shape not supported");
     const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + 255) / 256)), block(256);
     auto go = [&](auto kern) { LAUNCH(kern, grid, block, 0, s, a); };
-    auto pick = [&](auto K) {
+    with_metric_keep(a.metric, keep, [&](auto M, auto K) {
+        constexpr int METRIC = decltype(M)::value;
         constexpr bool KEEP = decltype(K)::value;
-        if (a.metric == METRIC_L2) {
-            switch (ks) {
-                case 1: return go(scan_all_kernel<METRIC_L2, 1, KEEP>);
-                case 2: return go(scan_all_kernel<METRIC_L2, 2, KEEP>);
-                case 3: return go(scan_all_kernel<METRIC_L2, 3, KEEP>);
-                default: return go(scan_all_kernel<METRIC_L2, 4, KEEP>);
-            }
-        }
         switch (ks) {
-            case 1: return go(scan_all_kernel<METRIC_IP, 1, KEEP>);
-            case 2: return go(scan_all_kernel<METRIC_IP, 2, KEEP>);
-            case 3: return go(scan_all_kernel<METRIC_IP, 3, KEEP>);
-            default: return go(scan_all_kernel<METRIC_IP, 4, KEEP>);
+            case 1: return go(scan_all_kernel<METRIC, 1, KEEP>);
+            case 2: return go(scan_all_kernel<METRIC, 2, KEEP>);
+            case 3: return go(scan_all_kernel<METRIC, 3, KEEP>);
+            default: return go(scan_all_kernel<METRIC, 4, KEEP>);
         }
-    };
-    if (keep) pick(std::true_type{});
-    else pick(std::false_type{});
+    });
 }
 
 void launch_scan_all_f16(const ExactScanF16Args& a, bool keep, hipStream_t s) {
@@ -711,23 +621,15 @@ void launch_scan_all_f16(const ExactScanF16Args& a, bool keep, hipStream_t s) {
     if (J == 0 || a.slab == 0 || (a.slab & 1) || (a.nblk & 1)) throw std::runtime_error("scan_all_f16_kernel: shape not supported");
     const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + 255) / 256)), block(256);
     auto go = [&](auto kern) { LAUNCH(kern, grid, block, 0, s, a); };
-    auto pick = [&](auto K) {
+    with_metric_keep(a.metric, keep, [&](auto M, auto K) {
+        constexpr int METRIC = decltype(M)::value;
         constexpr bool KEEP = decltype(K)::value;
-        if (a.metric == METRIC_L2) {
-            switch (J) {
-                case 4: return go(scan_all_f16_kernel<METRIC_L2, 4, KEEP>);
-                case 6: return go(scan_all_f16_kernel<METRIC_L2, 6, KEEP>);
-                default: return go(scan_all_f16_kernel<METRIC_L2, 8, KEEP>);
-            }
-        }
         switch (J) {
-            case 4: return go(scan_all_f16_kernel<METRIC_IP, 4, KEEP>);
-            case 6: return go(scan_all_f16_kernel<METRIC_IP, 6, KEEP>);
-            default: return go(scan_all_f16_kernel<METRIC_IP, 8, KEEP>);
+            case 4: return go(scan_all_f16_kernel<METRIC, 4, KEEP>);
+            case 6: return go(scan_all_f16_kernel<METRIC, 6, KEEP>);
+            default: return go(scan_all_f16_kernel<METRIC, 8, KEEP>);
         }
-    };
-    if (keep) pick(std::true_type{});
-    else pick(std::false_type{});
+    });
 }
 
 void launch_scan_all_wide_f16(const ExactScanF16Args& a, bool keep, hipStream_t s) {
@@ -735,18 +637,12 @@ void launch_scan_all_wide_f16(const ExactScanF16Args& a, bool keep, hipStream_t 
     if (a.d <= EXACT_NARROW_MAX_D || a.d > EXACT_WIDE_MAX_D || a.slab == 0 || (a.slab & (EXACT_WIDE_CHUNK - 1)) || (a.nblk & 1))
         throw std::runtime_error("scan_all_wide_f16_kernel: shape not supported");
     const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + EXACT_WIDE_QUERIES - 1) / EXACT_WIDE_QUERIES)), block(256);
-    auto go = [&](auto kern) {
+    with_metric_keep(a.metric, keep, [&](auto M, auto K) {
+        auto kern = scan_all_wide_f16_kernel<decltype(M)::value, decltype(K)::value>;
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXACT_WIDE_LDS);
         if (e != hipSuccess) throw std::runtime_error(std::string("scan_all_wide_f16_kernel: cannot reserve LDS: ") + hipGetErrorString(e));
         LAUNCH(kern, grid, block, EXACT_WIDE_LDS, s, a);
-    };
-    if (a.metric == METRIC_L2) {
-        if (keep) go(scan_all_wide_f16_kernel<METRIC_L2, true>);
-        else go(scan_all_wide_f16_kernel<METRIC_L2, false>);
-    } else {
-        if (keep) go(scan_all_wide_f16_kernel<METRIC_IP, true>);
-        else go(scan_all_wide_f16_kernel<METRIC_IP, false>);
-    }
+    });
 }
 
 void launch_exact_rescore(const ExactRescoreArgs& a, hipStream_t s) {

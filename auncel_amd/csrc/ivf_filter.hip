@@ -40,7 +40,7 @@
 // with a non-finite element (no usable scale) make the whole call keep every candidate (C < 0 in FilterParams): slow, never wrong.
 // Survivors are recomputed from the fp32 rows as before, so results do not depend on which form filtered.
 #include "exact_args.h"
-#include "ivf_dev.h"
+#include "mfma_tile.h"
 
 #include <algorithm>
 #include <stdexcept>
@@ -52,12 +52,6 @@
 
 namespace amdivf {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-// (explicitly global: a generic pointer makes these flat loads, which count on both wait counters and force full waits)
-typedef const v4f __attribute__((address_space(1)))* gv4f;
-
 // ---------------------------------------------------------------------------------------------
 // fp32 lists (CSR rows, row stride dpad) -> fragment order: a list is a run of 32-vector blocks (block_off[l] = its first, an
 // even number of them as for the byte codes); a block is filter_steps(d) pieces of 64 lanes x 16 bytes, lane (v = l & 31,
@@ -66,12 +60,7 @@ typedef const v4f __attribute__((address_space(1)))* gv4f;
 __device__ __forceinline__ void frag32_from_f32_block(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
                                                              int d, int dpad, int metric, float* out, float* yn, uint64_t blk) {
     const int lane = threadIdx.x, v = lane & 31, h = lane >> 5;
-    uint32_t lo = 0, hi = nlist;  // largest l with block_off[l] <= blk
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (block_off[mid] <= blk) lo = mid;
-        else hi = mid;
-    }
+    const uint32_t lo = list_of_block(block_off, nlist, blk);
     const uint64_t pos = (blk - block_off[lo]) * 32 + v, size = list_off[lo + 1] - list_off[lo];
     const bool ok = pos < size;
     const float* src = codes + (list_off[lo] + (ok ? pos : 0)) * (uint64_t)dpad;
@@ -228,12 +217,7 @@ float filter_half_scale(const uint32_t info[4], int d) { return half_scale_of(in
 __device__ __forceinline__ void frag16_from_f32_block(const float* codes, const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist,
                                                              int d, int dpad, int metric, const uint32_t* info, float* out, float* yn, uint64_t blk) {
     const int lane = threadIdx.x, v = lane & 31, h = lane >> 5;
-    uint32_t lo = 0, hi = nlist;  // largest l with block_off[l] <= blk
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (block_off[mid] <= blk) lo = mid;
-        else hi = mid;
-    }
+    const uint32_t lo = list_of_block(block_off, nlist, blk);
     const uint64_t pos = (blk - block_off[lo]) * 32 + v, size = list_off[lo + 1] - list_off[lo];
     const bool ok = pos < size;
     const float* src = codes + (list_off[lo] + (ok ? pos : 0)) * (uint64_t)dpad;
@@ -470,15 +454,7 @@ __device__ __forceinline__ void filter_verdicts(const FilterScanArgs& a, const S
 // NJ != 0 (d <= 128), re-read from the (L2-resident) packed query matrix otherwise; B operand: the list in fragment order,
 // P pieces in flight.  Piece j feeds four v_mfma_f32_32x32x2_f32 (element i of both 4-vectors: k = lane half).
 // HALF: the fp16 form -- a piece is 16 dimensions (lane (m, h): elements 16 j + 8 h .. + 7) and feeds ONE
-// v_mfma_f32_32x32x16_f16; the bytes of a piece, and so every address below, are the same.
-template <bool HALF> __device__ __forceinline__ void filter_mac(v16f& acc, const v4f& av, const v4f& bv) {
-    if constexpr (HALF) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, av), __builtin_bit_cast(v8h, bv), acc, 0, 0, 0);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; e++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bv[e], acc, 0, 0, 0);
-    }
-}
+// v_mfma_f32_32x32x16_f16 (mfma_tile.h: filter_mac); the bytes of a piece, and so every address below, are the same.
 // (Occupancy is not what bounds this kernel: at NJ = 8 the compiler's free choice is 155 registers + 16 accumulators, two waves a SIMD;
 // asked for three it fits 153 without spilling, for four it spills 24 -- measured on the bench workload's fp32 form, threshold passes
 // per step: 1.78 / 1.78 / 2.18 ms at 2 / 3 / 4 waves, cfg 3 (NJ = 6) 0.88 / 0.88 / 0.95: profiles/r06_experiments.txt A.)
@@ -648,32 +624,23 @@ template <int METRIC, int NJ, bool HALF> __global__ __launch_bounds__(256) void 
 // w of the chunk -- its 32 vectors stream from HBM once, straight into its registers, through a ring of FILTER_WIDE_SP pieces --
 // against ALL the item's query blocks (up to 4 accumulator tiles); the query operand, which every wave needs, goes through
 // LDS in stages of FILTER_WIDE_SP pieces (wave w fetches the rows of query block w: register staging, the write of stage
-// s + 1 behind the MFMAs of stage s, one barrier per stage).  Two workgroups per CU: one's barriers, prologue and epilogue
-// run under the other's MFMAs.  Against the one-wave form (32 queries x 128 vectors per pass) this reads the list once
-// instead of once per query block and the query rows once per chunk instead of once per wave: PMC on the GIST-like
+// s + 1 behind the MFMAs of stage s, one barrier per stage) -- the tile of mfma_tile.h.  Two workgroups per CU: one's barriers,
+// prologue and epilogue run under the other's MFMAs.  Against the one-wave form (32 queries x 128 vectors per pass) this reads the
+// list once instead of once per query block and the query rows once per chunk instead of once per wave: PMC on the GIST-like
 // configuration (d = 960, 71 queries per list): 16 GB fetched per pass over 3.84 GB of lists before.
 constexpr int FILTER_WIDE_QB = FILTER_WIDE_QUERIES / 32;
 #ifndef AUNCEL_FILTER_WIDE_SP
 #define AUNCEL_FILTER_WIDE_SP 6  // (8 pieces: 376 registers where two waves per SIMD leave 256 -- 120 of them spilled, 6 GB of scratch traffic a pass)
 #endif
 constexpr int FILTER_WIDE_SP = AUNCEL_FILTER_WIDE_SP;
-constexpr size_t FILTER_WIDE_STAGE_FLOATS = (size_t)FILTER_WIDE_QB * FILTER_WIDE_SP * 256;
-constexpr size_t FILTER_WIDE_LDS = 2 * FILTER_WIDE_STAGE_FLOATS * sizeof(float) + 4 * FILTER_WIDE_QUERIES * sizeof(float);
+constexpr size_t FILTER_WIDE_LDS = wide_lds_bytes(FILTER_WIDE_QB, FILTER_WIDE_SP, 4);  // (the stages + four tables of a word per query)
 static_assert(FILTER_WIDE_VECTORS == 128, "one 32-vector block per wave of the workgroup");
-
-// workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every global load in flight (one counter for
-// loads and stores on this ISA), which would drain the list prefetch ring at every stage
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 template <int METRIC, bool HALF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_filter_wide_kernel(FilterScanArgs a) {
     extern __shared__ __align__(16) unsigned char wide_smem[];
     float* s_a = reinterpret_cast<float*>(wide_smem);  // [2 buffers][query block][piece of the stage][lane][4]
-    float* s_u = s_a + 2 * FILTER_WIDE_STAGE_FLOATS;
+    float* s_u = s_a + 2 * wide_stage_floats(FILTER_WIDE_QB, FILTER_WIDE_SP);
     float* s_c = s_u + FILTER_WIDE_QUERIES;
     uint32_t* s_row = reinterpret_cast<uint32_t*>(s_c + FILTER_WIDE_QUERIES);
     uint32_t* s_q = s_row + FILTER_WIDE_QUERIES;
@@ -719,27 +686,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             s_row[wave * 32 + m] = (uint32_t)row;
             s_q[wave * 32 + m] = qrow;
         }
-        // Every wave runs the same sequence of loads, stages and barriers whatever its share of the item (a wave without a
-        // query block stages row 0, one without a block of the chunk recomputes the first and drops the result): the
-        // compiler's wait counts are exact only in straight-line code -- with the loads under conditions it waited for the
-        // youngest load of the prefetch ring at every stage.
-        const float* qp = a.xf + (size_t)qrow * qstride + (size_t)h * 4;
+        // Straight-line code (mfma_tile.h): every wave runs the same loads, stages and barriers whatever its share of the item -- a
+        // wave without a query block stages row 0, one without a block of the chunk recomputes the first and drops the result.
+        const WideTile<HALF, SP, QB> tile{s_a, a.xf + (size_t)qrow * qstride + (size_t)h * 4, J, wave, lane};
         v4f st[SP];
-        auto stage_load = [&](int s) __attribute__((always_inline)) {
-#pragma unroll
-            for (int jj = 0; jj < SP; jj++) {
-                const int j = s * SP + jj;
-                st[jj] = *(gv4f)(uintptr_t)(qp + 8 * (j < J ? j : J - 1));
-            }
-        };
-        auto stage_write = [&](int s, int buf) __attribute__((always_inline)) {
-#pragma unroll
-            for (int jj = 0; jj < SP; jj++)  // (pieces that pad the last stage contribute 0 x y)
-                *reinterpret_cast<v4f*>(s_a + ((size_t)(buf * QB + wave) * SP + jj) * 256 + (size_t)lane * 4) =
-                    s * SP + jj < J ? st[jj] : v4f{0.f, 0.f, 0.f, 0.f};
-        };
-        stage_load(0);
-        stage_write(0, 0);
+        tile.stage_load(0, st);
+        tile.stage_write(0, 0, st);
         const uint32_t nblk = ((it.nvec + 63) >> 6) * 2;  // (pairs of blocks, as the lists are stored)
         const bool active = (uint32_t)wave < nblk;
         const float* bbase = a.codes_frag + ((size_t)it.vec_base + (active ? (uint32_t)wave : 0u)) * (size_t)J * 256 + (size_t)lane * 4;
@@ -767,44 +719,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         lds_barrier();  // stage 0 is in LDS
         auto run = [&](auto NQBc) __attribute__((always_inline)) {
             constexpr int NQB = decltype(NQBc)::value;
-            v4f afA[NQB], afB[NQB];  // the query blocks' operands of an even and an odd piece, read from LDS one MFMA group ahead
-            auto load_a = [&](int buf, int jj, v4f (&af)[NQB]) __attribute__((always_inline)) {
-#pragma unroll
-                for (int q = 0; q < NQB; q++)
-                    af[q] = *reinterpret_cast<const v4f*>(s_a + ((size_t)(buf * QB + q) * SP + jj) * 256 + (size_t)lane * 4);
-            };
-            auto mac = [&](const v4f (&af)[NQB], const v4f& bv) __attribute__((always_inline)) {
-                if constexpr (HALF) {
-#pragma unroll
-                    for (int q = 0; q < NQB; q++) filter_mac<true>(acc[q], af[q], bv);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; e++)
-#pragma unroll
-                        for (int q = 0; q < NQB; q++) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q][e], bv[e], acc[q], 0, 0, 0);
-                }
-            };
-            for (int s = 0; s < S; s++) {
-                const int buf = s & 1;
-                stage_load(s + 1);  // (behind the last stage: padding, written to the idle buffer and never read)
-#pragma unroll
-                for (int jj = 0; jj < SP; jj += 2) {
-                    const int j = s * SP + jj;
-                    if (jj == 0) load_a(buf, 0, afA);
-                    load_a(buf, jj + 1, afB);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mac(afA, br[jj]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    fetch_b(j + SP, br[jj]);
-                    if (jj + 2 < SP) load_a(buf, jj + 2, afA);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mac(afB, br[jj + 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    fetch_b(j + 1 + SP, br[jj + 1]);
-                }
-                stage_write(s + 1, buf ^ 1);  // (last read in stage s - 1: every wave is past that barrier)
-                lds_barrier();
-            }
+            // (stage s + 1 behind the last stage: padding, written to the idle buffer and never read)
+            for (int s = 0; s < S; s++)
+                tile.template stage<NQB>(s & 1, s, s + 1, st, acc, br, [&](int j, int, v4f& bv) __attribute__((always_inline)) { fetch_b(j + SP, bv); });
         };
         switch (nqb) {
             case 1: run(std::integral_constant<int, 1>{}); break;

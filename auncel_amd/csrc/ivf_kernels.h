@@ -760,7 +760,7 @@ struct ExactScanArgs {
     const uint8_t* codes_frag;    // lists in fragment order
     const int32_t* code_cy;       // per stored slot
     const uint2* blk;             // per block: (global position of its first slot, slots that hold an entry) -- launch_exact_blocks;
-                                  // under a selector (launch_exact_blocks_keep): (..., mask of the slots that hold a member)
+                                  // under a selector (its keep words passed): (..., mask of the slots that hold a member)
     uint64_t nblk;                // blocks of the copy (even)
     uint32_t slab;                // consecutive blocks per workgroup (even)
     const int8_t* queries8;       // signed query bytes, row stride ks * 32
@@ -816,13 +816,12 @@ struct ExactSelectArgs {
     unsigned long long* totals;   // [0..2] += queries by flag, [3] += candidates emitted, [4] += candidates at or within the threshold,
                                   // [5] = max of one query's emitted count (six words, zeroed by the caller)
 };
-void launch_exact_blocks(const uint64_t* list_off, const uint64_t* block_off, uint32_t nlist, uint64_t nblk, uint2* out, hipStream_t s);
-// the table of a call under a selector: out[b].y is the mask of block b's slots that hold a member (keep: the selector's words)
-void launch_exact_blocks_keep(const uint64_t* list_off, const uint64_t* block_off, const unsigned long long* keep, uint32_t nlist, uint64_t nblk,
-                              uint2* out, hipStream_t s);
+// keep (the selector's words) or null; with it, the table of a call under a selector: out[b].y is the mask of block b's slots that hold a member
+void launch_exact_blocks(const uint64_t* list_off, const uint64_t* block_off, const unsigned long long* keep, uint32_t nlist, uint64_t nblk,
+                         uint2* out, hipStream_t s);
 void launch_identity_keys(int64_t* keys, size_t rows, uint32_t nlist, hipStream_t s);  // keys[i][l] = l
 uint32_t exact_slab_blocks(uint64_t nblk, uint32_t n);
-// keep: a.blk is launch_exact_blocks_keep's table (the members' mask), else launch_exact_blocks' (the entries' count)
+// keep: a.blk is launch_exact_blocks' table under a selector (the members' mask), else the plain one (the entries' count)
 void launch_scan_all(const ExactScanArgs& a, bool keep, hipStream_t s);
 void launch_scan_all_f16(const ExactScanF16Args& a, bool keep, hipStream_t s);
 // the same pass for 128 < d <= 1024 (option "exact_wide"): a workgroup tile of 128 queries x 4 blocks, the query operand through LDS;
