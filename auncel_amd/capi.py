@@ -40,6 +40,7 @@ SYMBOLS = [
     "amd_ivf_submit_search_resident_selected",
     "amd_ivf_search_exact", "amd_ivf_search_exact_resident", "amd_ivf_last_exact", "amd_ivf_last_exact_detail",
     "amd_ivf_search_exact_selected", "amd_ivf_search_exact_resident_selected",
+    "amd_ivf_range_search_exact", "amd_ivf_range_search_exact_resident", "amd_ivf_range_search_exact_selected", "amd_ivf_last_range_exact",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -558,6 +559,43 @@ class Handle:
         the threshold after rescoring; the largest emitted count of one query)"""
         out = (C.c_uint64 * 4)()
         _chk(lib().amd_ivf_last_exact_detail(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def _range_results(self, lims):
+        n = len(lims) - 1
+        tot = int(lims[n])
+        labels = np.empty(max(tot, 1), np.int64)
+        dist = np.empty(max(tot, 1), np.float32)
+        _chk(lib().amd_ivf_range_results(self._h, _i(labels), _f(dist)))
+        return lims.astype(np.int64), labels[:tot], dist[:tot]
+
+    def range_search_exact(self, x, radius):
+        """every entry within the radius, over every list (include/auncel_amd.h: amd_ivf_range_search_exact): range_search with
+        nprobe = nlist and identity keys, bit for bit -> lims (n + 1), labels, distances"""
+        x = f32(x)
+        n = x.shape[0]
+        lims = np.zeros(n + 1, dtype=np.uintp)
+        _chk(lib().amd_ivf_range_search_exact(self._h, C.c_size_t(n), _f(x), C.c_float(radius), lims.ctypes.data_as(_szp)))
+        return self._range_results(lims)
+
+    def range_search_exact_resident(self, start, n, radius):
+        lims = np.zeros(n + 1, dtype=np.uintp)
+        _chk(lib().amd_ivf_range_search_exact_resident(self._h, C.c_size_t(start), C.c_size_t(n), C.c_float(radius), lims.ctypes.data_as(_szp)))
+        return self._range_results(lims)
+
+    def range_search_exact_selected(self, selector, x, radius):
+        """range_search_exact over the selector's members only"""
+        x = f32(x)
+        n = x.shape[0]
+        lims = np.zeros(n + 1, dtype=np.uintp)
+        _chk(lib().amd_ivf_range_search_exact_selected(self._h, selector._s, C.c_size_t(n), _f(x), C.c_float(radius), lims.ctypes.data_as(_szp)))
+        return self._range_results(lims)
+
+    def last_range_exact(self):
+        """(which list pass the last exact range call ran: 0 none, 1 bytes, 2 fp16 + rescoring, 3 wide fp16 + rescoring; queries
+        answered from the pass; queries searched the general way; the largest emitted candidate count of one query)"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_last_range_exact(self._h, out))
         return tuple(int(v) for v in out)
 
     def range_search(self, x, radius, nprobe, keys=None, coarse_mode=0):

@@ -1,9 +1,11 @@
 // The host side of the exact search over the whole index (include/auncel_amd.h: amd_ivf_search_exact): what the entry points refuse
 // before anything touches a device, and the one rule that says when a query's result can be read off its sorted candidates (DESIGN.md
 // 13), the keep rule of the fp16 list pass over float lists, and what the forms under an id selector add: their checks, the seed's
-// nprobe and the mask of a block's live slots.  Plain C++, nothing of the device in it: the kernels of ivf_exact.hip
-// and the host read the same definitions, and it builds on its own (tests/cpp/exact_args_main.cpp, exact_float_main.cpp and
-// exact_selected_main.cpp, which are what the address and undefined-behaviour sanitizers are pointed at).
+// nprobe and the mask of a block's live slots; of the exact range search (amd_ivf_range_search_exact) its checks, the threshold
+// the byte pass is given for a radius, the strict test and the candidates' key.  Plain C++, nothing of the device in it: the
+// kernels of ivf_exact.hip and the host read the same definitions, and it builds on its own (tests/cpp/exact_args_main.cpp,
+// exact_float_main.cpp, exact_selected_main.cpp and exact_range_main.cpp, which are what the address and undefined-behaviour
+// sanitizers are pointed at).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -95,7 +97,7 @@ EXACT_HD inline bool exact_float_keep(bool l2, float C, float p, float yn, float
 
 // Which list pass serves a call (exact_slice): 0 none -- the general way whole --, 1 the byte pass, 2 the fp16 pass + rescoring,
 // 3 the workgroup-tiled ("wide") fp16 pass + rescoring.  shape: what every pass needs besides d (centroids for the seed, blocks,
-// ntotal < 2^32, k < cap, k <= members); bytes: the call runs on the lists' byte codes; float_ok: the filter's copies may be used
+// ntotal < 2^32, k < cap, k <= members; the exact range search, which has no seed and no k: blocks and ntotal < 2^32); bytes: the call runs on the lists' byte codes; float_ok: the filter's copies may be used
 // (filter_available: option "filter" != 0, float lists or byte codes not in use); the two options as booleans.  Up to 128
 // dimensions this is the rule that was there before the wide pass, whatever opt_wide says.  Beyond, only the wide pass exists:
 // byte-coded lists have no pass there, and 1024 is where the fp16 copy's row rule changes regime (ivf_filter.hip: half_scale_of).
@@ -107,6 +109,42 @@ inline int exact_pass_kind(int d, bool shape, bool bytes, bool float_ok, bool op
     if (d <= EXACT_WIDE_MAX_D) return !bytes && float_ok && opt_float && opt_wide ? 3 : 0;
     return 0;
 }
+
+// ---- exact range search (amd_ivf_range_search_exact)
+// empty: the arguments are valid; else the message of the refusal.  As exact_args_error, with the lims where k-NN has (D, I): they are
+// written for every n, n = 0 included (lims[0] = 0).
+inline std::string exact_range_args_error(bool have_handle, bool have_queries, size_t start, size_t n, const void* lims) {
+    const std::string w("exact range search: ");
+    if (!have_handle) return w + "null handle";
+    if (!lims) return w + "null lims";
+    if (start + n < start) return w + "resident query range out of bounds";
+    if (n && !have_queries) return w + "null argument";
+    return std::string();
+}
+inline std::string exact_range_selected_args_error(bool have_handle, bool have_selector, bool have_queries, size_t start, size_t n, const void* lims) {
+    if (have_handle && !have_selector) return std::string("exact range search: null selector");
+    return exact_range_args_error(have_handle, have_queries, start, n, lims);
+}
+
+// The threshold the BYTE list pass is given for a radius.  scan_all_kernel emits nothing for a query whose threshold is NaN or beyond
+// 2^30 in magnitude, and works in 32-bit integers around it; a radius may be any float.  The byte rule bounds every distance the pass
+// can meet by d m^2 <= 2^24 in magnitude (L2: 0 <= dis; IP: |dis| <= d m^2), so a radius beyond +-2^28 decides like +-2^28: on the
+// full side every entry passes `dis <= 2^28` / `dis >= -2^28`, on the empty side none passes `dis <= -2^28` / `dis >= 2^28`.  Inside
+// the range the radius is returned as it is.  *none: the radius is NaN -- the reference's compare is false for every entry, there is
+// nothing to pass over the lists for.  The strict test behind the pass always uses the caller's radius, never this value.
+constexpr float EXACT_RANGE_CLAMP = 268435456.f;  // 2^28
+constexpr float EXACT_SCAN_GUARD = 1073741824.f;  // 2^30: scan_all_kernel's own limit
+inline float exact_range_threshold(float radius, bool* none) {
+    *none = radius != radius;
+    if (*none) return 0.f;
+    return radius > EXACT_RANGE_CLAMP ? EXACT_RANGE_CLAMP : radius < -EXACT_RANGE_CLAMP ? -EXACT_RANGE_CLAMP : radius;
+}
+// the reference's range test (C::cmp(radius, dis): CMax for L2, CMin for the inner product), strict on either side
+EXACT_HD inline bool exact_range_within(bool l2, float radius, float dis) { return l2 ? radius > dis : radius < dis; }
+// A range candidate's sort key: its global position (unique per stored entry: the order is determined) above its distance's bits;
+// invalid candidates take EXACT_RANGE_INVALID, which no valid key equals (a position is below 2^32 - 1: ntotal < 2^32 - 1).
+constexpr uint64_t EXACT_RANGE_INVALID = ~(uint64_t)0;
+EXACT_HD inline uint64_t exact_range_key(uint32_t position, uint32_t dist_bits) { return ((uint64_t)position << 32) | dist_bits; }
 
 // The wide pass's tile (scan_all_wide_f16_kernel): four waves walk a slab in chunks of four consecutive blocks, wave w block w; the
 // query operand goes through LDS in stages of `sp` pieces.

@@ -43,6 +43,13 @@ struct IndexIVFFlat : IndexIVF {
     /// bit for bit search_exact of an IndexIVFFlatSubset of the same selector.  The selectors and the kept bits are search_selected's:
     /// the same selector used by both calls is made once (selector_passes); exact_info / exact_detail report the call.
     void search_exact_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const IDSelector& sel) const;
+    /// every entry within `radius`, over every list (include/auncel_amd.h: amd_ivf_range_search_exact): bit for bit
+    /// range_search_preassigned with every row of keys = 0 .. nlist - 1, from one pass over the lists for all queries.  `result` is
+    /// made for n queries; it is filled as range_search fills it.  _selected: over the members of `sel` only (the kept selector is
+    /// search_selected's).  Not for an IndexIVFFlatDedup.  range_exact_info: the four counts of the last call (amd_ivf_last_range_exact).
+    void range_search_exact(idx_t n, const float* x, float radius, RangeSearchResult* result) const;
+    void range_search_exact_selected(idx_t n, const float* x, float radius, RangeSearchResult* result, const IDSelector& sel) const;
+    void range_exact_info(uint64_t out[4]) const;
     IndexIVFFlat(const IndexIVFFlat&) = delete;
     IndexIVFFlat& operator=(const IndexIVFFlat&) = delete;
     ~IndexIVFFlat() override;
@@ -105,6 +112,9 @@ struct IndexIVFFlatSubset : Index {
     void search_exact(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const;
     void exact_info(uint64_t out[4]) const;
     void exact_detail(uint64_t out[4]) const;
+    /// IndexIVFFlat::range_search_exact / range_exact_info over the subset's own lists
+    void range_search_exact(idx_t n, const float* x, float radius, RangeSearchResult* result) const;
+    void range_exact_info(uint64_t out[4]) const;
     bool device_bound() const override { return true; }
     amd_ivf* engine() const { return gpu_; }
 

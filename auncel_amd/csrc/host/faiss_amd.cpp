@@ -1350,6 +1350,42 @@ void IndexIVFFlatSubset::search_exact(idx_t n, const float* x, idx_t k, float* d
 void IndexIVFFlatSubset::exact_info(uint64_t out[4]) const { AMD(amd_ivf_last_exact(gpu_, out)); }
 void IndexIVFFlatSubset::exact_detail(uint64_t out[4]) const { AMD(amd_ivf_last_exact_detail(gpu_, out)); }
 
+// ------------------------------------------------------------------------------------- IndexIVFFlat::range_search_exact
+namespace {
+// the engine's offsets -> the counts do_allocation turns back into offsets, then the two result arrays
+void range_exact_results(amd_ivf* g, Index::idx_t n, RangeSearchResult* result) {
+    for (Index::idx_t i = 0; i < n; i++) result->lims[i] = result->lims[i + 1] - result->lims[i];
+    result->do_allocation();
+    AMD(amd_ivf_range_results(g, i64(result->labels), result->distances));
+}
+}  // namespace
+
+void IndexIVFFlat::range_search_exact(idx_t n, const float* x, float radius, RangeSearchResult* result) const {
+    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(this) == nullptr, "range_search_exact of an IndexIVFFlatDedup is not implemented");
+    FAISS_THROW_IF_NOT_MSG(result && result->lims, "range_search_exact needs a RangeSearchResult made for n queries");
+    amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
+    AMD(amd_ivf_range_search_exact(g, (size_t)n, x, radius, result->lims));
+    range_exact_results(g, n, result);
+}
+
+void IndexIVFFlat::range_search_exact_selected(idx_t n, const float* x, float radius, RangeSearchResult* result, const IDSelector& sel) const {
+    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(this) == nullptr, "range_search_exact_selected of an IndexIVFFlatDedup is not implemented");
+    FAISS_THROW_IF_NOT_MSG(result && result->lims, "range_search_exact_selected needs a RangeSearchResult made for n queries");
+    amd_ivf* g = engine();
+    AMD(amd_ivf_range_search_exact_selected(g, device_selector(g, sel), (size_t)n, x, radius, result->lims));
+    range_exact_results(g, n, result);
+}
+
+void IndexIVFFlat::range_exact_info(uint64_t out[4]) const { AMD(amd_ivf_last_range_exact(engine(), out)); }
+
+void IndexIVFFlatSubset::range_search_exact(idx_t n, const float* x, float radius, RangeSearchResult* result) const {
+    FAISS_THROW_IF_NOT_MSG(result && result->lims, "range_search_exact needs a RangeSearchResult made for n queries");
+    AMD(amd_ivf_range_search_exact(gpu_, (size_t)n, x, radius, result->lims));
+    range_exact_results(gpu_, n, result);
+}
+
+void IndexIVFFlatSubset::range_exact_info(uint64_t out[4]) const { AMD(amd_ivf_last_range_exact(gpu_, out)); }
+
 // ------------------------------------------------------------------------------------- IndexIVFFlatSubset
 void IndexIVFFlatSubset::cut(const IndexIVFFlat& src, int subset_type, idx_t a1, idx_t a2, const void* sel, size_t nsel) {
     FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(&src) == nullptr, "a subset of an IndexIVFFlatDedup is not implemented");

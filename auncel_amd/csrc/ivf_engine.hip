@@ -531,6 +531,10 @@ struct amd_ivf {
     DevBuf w_ex_blk, w_ex_cnt, w_ex_cand, w_ex_flag, w_ex_tot, w_ex_D, w_ex_I, w_ex_x, w_ex_idx;
     uint64_t last_exact[4] = {0, 0, 0, 0};
     uint64_t last_exact_detail[4] = {0, 0, 0, 0};  // amd_ivf_last_exact_detail: pass kind, emitted, within the threshold, largest per query
+    // amd_ivf_range_search_exact: the thresholds and "seed ids" the list pass reads, the valid counts of the collect, the runs' offsets
+    // and the contiguous result of the fill; the counts of the last call
+    DevBuf w_rx_thr, w_rx_id, w_rx_valid, w_rx_off, w_rx_lab, w_rx_dis;
+    uint64_t last_range_exact[4] = {0, 0, 0, 0};
     DevBuf w_limit;  // time-bounded search: per-slot end of the probe loop (plan_counts_kernel -> replay_kernel)
     DevBuf w_tie_rows;  // rankings re-run through the reference's heap because of equal distances (launch_heap_tie_order)
 
@@ -5874,30 +5878,15 @@ size_t exact_general(amd_ivf* h, const float* d_x, const uint32_t* idx, size_t m
     return heap;
 }
 
-// one slice of an exact call: seed, list pass, selection, and the flagged queries the general way.  out: amd_ivf_last_exact's counts
-// (added to); returns the heap updates of the general-way part.
-// sel: the call searches the selector's members only (checked by the caller: of this index, of the lists as they are).  The lists are
-// then "the lists with the non-members removed" in every stage: the seed's k-th distance is that of k members, the block table
-// carries the members' mask, and the general way searches under the same keep words.
-size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int64_t* I, const IntRange& qr, uint64_t out[4],
-                   const amd_ivf_selector* sel) {
-    amd_ivf* index = ix(h);
-    const size_t nlist = h->nlist;
-    const uint64_t ntotal = index->h_list_off.size() == nlist + 1 ? index->h_list_off[nlist] : 0;
-    const uint64_t members = sel ? sel->info[1] : ntotal;
-    const unsigned long long* keep = sel ? sel->keep.as<unsigned long long>() : nullptr;
-    const uint32_t cap = exact_cap();
-    const uint64_t nblk = index->h_block_off.size() == nlist + 1 ? index->h_block_off[nlist] : 0;
-    if (sel && sel->keep.cap < nblk / 2 * 8) throw std::runtime_error("exact search: the selector is shorter than the lists");
-    // which list pass (exact_args.h: exact_pass_kind): byte codes up to four K-steps, under the rule every byte scan runs under ...
-    const bool shape_ok = index->have_centroids && nblk > 0 && ntotal < 0xffffffffull && k < cap && k <= members;
+// Which list pass serves a slice of n queries -- of the exact k-NN call and of the exact range search alike: there is one rule
+// (exact_args.h: exact_pass_kind).  Byte codes up to four K-steps, under the rule every byte scan runs under; the filter's fp16 copy
+// of float lists where lists and queries have a usable scale (ivf_filter.hip: no non-finite element, magnitudes within 2^+-24, no
+// row tiny beside the largest -- which also keeps every reference distance finite), beyond 128 dimensions by the workgroup-tiled
+// kernel.  shape_ok: what the caller's pass needs besides (exact_pass_kind's `shape`).
+int exact_pick_pass(amd_ivf* h, amd_ivf* index, const float* d_x, size_t n, const IntRange& qr, bool shape_ok) {
     const bool bytes = index->have_codes8 && h->allow_bytes && index->db_range.bytes_with(qr, (size_t)h->d);
     int kind = exact_pass_kind(h->d, shape_ok, bytes, filter_available(h, index, bytes), opt(h, OPT_EXACT_FLOAT, 0) != 0,
                                opt(h, OPT_EXACT_WIDE, 0) != 0);
-    const bool pass = kind == 1;
-    // ... and on the filter's fp16 copy of float lists, where lists and queries have a usable scale (ivf_filter.hip: no non-finite
-    // element, magnitudes within 2^+-24, no row tiny beside the largest -- which also keeps every reference distance finite);
-    // beyond 128 dimensions by the workgroup-tiled kernel, everything around the launch the same
     hipStream_t s = h->stream;
     bool pass16 = kind >= 2 && ensure_frag16(index);
     if (pass16) {
@@ -5910,35 +5899,24 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         pass16 = filter_half_scale(info, h->d) != 0.f;
     }
     if (!pass16 && kind >= 2) kind = 0;
-    const bool wide = kind == 3;
-    // ---- 1. seed: an ordinary fixed-nprobe search; its k-th distance is a distance of k stored entries, so the true k-th is within it.
-    // Under a selector it is the k-th among the members the seed saw; as `seed` lists hold too few of them when the selector is
-    // sparse, nprobe grows by ntotal / kept (exact_args.h) -- and a seed that would read every list is the whole search: the call
-    // then goes the general way (any seed gives the same result: this only decides which path computes it)
-    size_t seed = std::min<size_t>(nlist, (size_t)std::max(1.0, opt(h, OPT_EXACT_SEED_NPROBE, EXACT_SEED_DEFAULT)));
-    bool seed_ok = true;
-    if (sel) {
-        const uint64_t scaled = exact_selected_seed(seed, ntotal, members);
-        seed_ok = scaled < nlist;
-        seed = (size_t)std::min<uint64_t>(scaled, nlist);
-    }
-    if ((!pass && !pass16) || !seed_ok) {
-        out[2] += n;
-        return exact_general(h, d_x, nullptr, n, k, D, I, qr, keep);
-    }
-    search_full(h, d_x, n, k, seed, -1, D, I, qr, keep);
-    const float* seed_D = h->last_direct_out ? static_cast<const float*>(device_view(D)) : h->w_D.as<float>();
-    const int64_t* seed_I = h->last_direct_out ? static_cast<const int64_t*>(device_view(I)) : h->w_I.as<int64_t>();
-    if (!seed_D || !seed_I) throw std::runtime_error("exact search: the seed's result is not on the device");
-    // ---- 2. list pass
+    return kind;
+}
+
+// The list pass of kind 1 .. 3 over every block for n queries whose thresholds are row q's last entry of (seed_D, seed_I) [n][k]
+// (an id < 0 there: no threshold, the query emits nothing): the block table (keep: a selector's words, the table then carries the
+// members' mask), the counters and totals zeroed, the pass, and behind an fp16 pass the rescoring.  Leaves the candidates in
+// w_ex_cnt / w_ex_cand ([n][cap]).  ev: null, or three events of which [0] is recorded in front of the pass and [1] behind it.
+void exact_run_pass(amd_ivf* h, amd_ivf* index, const float* d_x, size_t n, size_t k, const IntRange& qr, int kind, const float* seed_D,
+                    const int64_t* seed_I, const unsigned long long* keep, uint32_t cap, uint64_t nblk, hipEvent_t* ev) {
+    const size_t nlist = h->nlist;
+    const bool pass = kind == 1, wide = kind == 3;
+    hipStream_t s = h->stream;
     if (pass && !byte_queries(h, index, d_x, n, qr)) throw std::runtime_error("exact search: no byte view of the queries");
     h->w_ex_blk.ensure(nblk * sizeof(uint2));
     h->w_ex_cnt.ensure(n * 4);
     h->w_ex_cand.ensure(n * (size_t)cap * sizeof(uint2));
     h->w_ex_flag.ensure(n * 4);
     h->w_ex_tot.ensure(6 * 8);
-    h->w_ex_D.ensure(n * k * sizeof(float));
-    h->w_ex_I.ensure(n * k * sizeof(int64_t));
     launch_exact_blocks(index->d_list_off.as<uint64_t>(), index->d_block_off.as<uint64_t>(), keep, (uint32_t)nlist, nblk, h->w_ex_blk.as<uint2>(), s);
     HIP_CHECK(hipMemsetAsync(h->w_ex_cnt.p, 0, n * 4, s));
     HIP_CHECK(hipMemsetAsync(h->w_ex_tot.p, 0, 6 * 8, s));
@@ -5959,13 +5937,9 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     sa.cnt = h->w_ex_cnt.as<uint32_t>();
     sa.cand = h->w_ex_cand.as<uint2>();
     sa.cap = cap;
-    static const bool timed = getenv("AUNCEL_AMD_EXACT_TIMING") != nullptr;  // (scripts/exact_timing.py: the stages' share of a call)
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (timed)
-        for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
     if (pass) {
-        if (timed) HIP_CHECK(hipEventRecord(ev[0], s));
-        launch_scan_all(sa, sel != nullptr, s);
+        if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
+        launch_scan_all(sa, keep != nullptr, s);
     } else {
         // the fp16 query operands and FilterParams by the filter's own launches (the seed search may have left them; not every seed does)
         h->w_xf.ensure(n * (size_t)filter_steps(h->d) * 8 * sizeof(float));  // (rows of 8 filter_steps16(d) floats: no more than this)
@@ -5993,9 +5967,9 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         fa.cnt = sa.cnt;
         fa.cand = sa.cand;
         fa.cap = cap;
-        if (timed) HIP_CHECK(hipEventRecord(ev[0], s));
-        if (wide) launch_scan_all_wide_f16(fa, sel != nullptr, s);
-        else launch_scan_all_f16(fa, sel != nullptr, s);
+        if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
+        if (wide) launch_scan_all_wide_f16(fa, keep != nullptr, s);
+        else launch_scan_all_f16(fa, keep != nullptr, s);
         ExactRescoreArgs ra{};
         ra.n = (uint32_t)n;
         ra.cap = cap;
@@ -6007,7 +5981,62 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         ra.codes = index->d_codes.as<float>();
         launch_exact_rescore(ra, s);
     }
-    if (timed) HIP_CHECK(hipEventRecord(ev[1], s));
+    if (ev) HIP_CHECK(hipEventRecord(ev[1], s));
+}
+
+// AUNCEL_AMD_EXACT_TIMING (scripts/exact_timing.py, exact_range_timing.py): the stages' share of a call, by events
+bool exact_timed() {
+    static const bool timed = getenv("AUNCEL_AMD_EXACT_TIMING") != nullptr;
+    return timed;
+}
+
+// one slice of an exact call: seed, list pass, selection, and the flagged queries the general way.  out: amd_ivf_last_exact's counts
+// (added to); returns the heap updates of the general-way part.
+// sel: the call searches the selector's members only (checked by the caller: of this index, of the lists as they are).  The lists are
+// then "the lists with the non-members removed" in every stage: the seed's k-th distance is that of k members, the block table
+// carries the members' mask, and the general way searches under the same keep words.
+size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int64_t* I, const IntRange& qr, uint64_t out[4],
+                   const amd_ivf_selector* sel) {
+    amd_ivf* index = ix(h);
+    const size_t nlist = h->nlist;
+    const uint64_t ntotal = index->h_list_off.size() == nlist + 1 ? index->h_list_off[nlist] : 0;
+    const uint64_t members = sel ? sel->info[1] : ntotal;
+    const unsigned long long* keep = sel ? sel->keep.as<unsigned long long>() : nullptr;
+    const uint32_t cap = exact_cap();
+    const uint64_t nblk = index->h_block_off.size() == nlist + 1 ? index->h_block_off[nlist] : 0;
+    if (sel && sel->keep.cap < nblk / 2 * 8) throw std::runtime_error("exact search: the selector is shorter than the lists");
+    // which list pass (exact_pick_pass)
+    const bool shape_ok = index->have_centroids && nblk > 0 && ntotal < 0xffffffffull && k < cap && k <= members;
+    const int kind = exact_pick_pass(h, index, d_x, n, qr, shape_ok);
+    const bool pass = kind == 1, wide = kind == 3;
+    hipStream_t s = h->stream;
+    // ---- 1. seed: an ordinary fixed-nprobe search; its k-th distance is a distance of k stored entries, so the true k-th is within it.
+    // Under a selector it is the k-th among the members the seed saw; as `seed` lists hold too few of them when the selector is
+    // sparse, nprobe grows by ntotal / kept (exact_args.h) -- and a seed that would read every list is the whole search: the call
+    // then goes the general way (any seed gives the same result: this only decides which path computes it)
+    size_t seed = std::min<size_t>(nlist, (size_t)std::max(1.0, opt(h, OPT_EXACT_SEED_NPROBE, EXACT_SEED_DEFAULT)));
+    bool seed_ok = true;
+    if (sel) {
+        const uint64_t scaled = exact_selected_seed(seed, ntotal, members);
+        seed_ok = scaled < nlist;
+        seed = (size_t)std::min<uint64_t>(scaled, nlist);
+    }
+    if (kind == 0 || !seed_ok) {
+        out[2] += n;
+        return exact_general(h, d_x, nullptr, n, k, D, I, qr, keep);
+    }
+    search_full(h, d_x, n, k, seed, -1, D, I, qr, keep);
+    const float* seed_D = h->last_direct_out ? static_cast<const float*>(device_view(D)) : h->w_D.as<float>();
+    const int64_t* seed_I = h->last_direct_out ? static_cast<const int64_t*>(device_view(I)) : h->w_I.as<int64_t>();
+    if (!seed_D || !seed_I) throw std::runtime_error("exact search: the seed's result is not on the device");
+    // ---- 2. list pass
+    h->w_ex_D.ensure(n * k * sizeof(float));
+    h->w_ex_I.ensure(n * k * sizeof(int64_t));
+    const bool timed = exact_timed();
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (timed)
+        for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    exact_run_pass(h, index, d_x, n, k, qr, kind, seed_D, seed_I, keep, cap, nblk, timed ? ev : nullptr);
     // ---- 3. exact selection
     ExactSelectArgs ea{};
     ea.n = (uint32_t)n;
@@ -6016,8 +6045,8 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     ea.metric = h->metric;
     ea.rescored = pass ? 0 : 1;
     ea.seed_D = seed_D;
-    ea.cnt = sa.cnt;
-    ea.cand = sa.cand;
+    ea.cnt = h->w_ex_cnt.as<uint32_t>();
+    ea.cand = h->w_ex_cand.as<uint2>();
     ea.seed_I = seed_I;
     ea.ids = index->d_ids.as<int64_t>();
     ea.D = h->w_ex_D.as<float>();
@@ -6081,6 +6110,206 @@ void exact_core(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int6
     h->stats_host[2] = st[2] + n * (size_t)ntotal;
     h->stats_host[3] = st[3] + heap;
     for (int i = 0; i < 4; i++) h->last_exact[i] = out[i];
+}
+
+// ---- exact range search: the same pass with the radius as every query's threshold; no seed, no tie rule
+
+// a call's result while its slices add to it: per query its count, and the runs in query order
+struct RangeRuns {
+    std::vector<size_t> count;
+    std::vector<int64_t> labels;
+    std::vector<float> dist;
+};
+
+// The queries idx[0 .. m) of d_x (all of them when idx is null) the general way: range_core over every list in list-number order,
+// keys made on the device, in slices that keep the key table small (as exact_general).  count[j] = results of the j-th of them; their
+// runs are appended to (labels, dist) in that order.  range_core overwrites the handle's r_lims / r_labels / r_dist: the caller owns
+// no part of those while this runs.
+void range_exact_general(amd_ivf* h, const float* d_x, const uint32_t* idx, size_t m, float radius, const IntRange& qr,
+                         const unsigned long long* keep, size_t* count, std::vector<int64_t>& labels, std::vector<float>& dist) {
+    const size_t nlist = h->nlist;
+    const size_t slice = std::max<size_t>(1, std::min<size_t>(4096, ((size_t)4 << 20) / std::max<size_t>(nlist, 1)));
+    std::vector<size_t> lims;
+    for (size_t o = 0; o < m; o += slice) {
+        const size_t c = std::min(slice, m - o);
+        const float* rows = d_x + o * (size_t)h->dpad;
+        if (idx) {
+            h->w_ex_idx.ensure(c * 4);
+            h->w_ex_x.ensure(c * (size_t)h->dpad * sizeof(float));
+            HIP_CHECK(hipMemcpyAsync(h->w_ex_idx.p, idx + o, c * 4, hipMemcpyHostToDevice, h->stream));
+            launch_gather_rows(d_x, h->w_ex_idx.as<uint32_t>(), (uint32_t)c, (uint32_t)h->dpad, h->w_ex_x.as<float>(), h->stream);
+            HIP_CHECK(stream_sync(h->stream));  // (idx + o is the caller's pageable memory)
+            rows = h->w_ex_x.as<float>();
+        }
+        h->w_ckeys.ensure(c * nlist * 8);
+        launch_identity_keys(h->w_ckeys.as<int64_t>(), c, (uint32_t)nlist, h->stream);
+        lims.assign(c + 1, 0);
+        range_core(h, rows, c, radius, nlist, h->w_ckeys.as<int64_t>(), qr, lims.data(), keep);
+        for (size_t j = 0; j < c; j++) count[o + j] = lims[j + 1] - lims[j];
+        labels.insert(labels.end(), h->r_labels.begin(), h->r_labels.begin() + (ptrdiff_t)lims[c]);
+        dist.insert(dist.end(), h->r_dist.begin(), h->r_dist.begin() + (ptrdiff_t)lims[c]);
+    }
+}
+
+// One slice of an exact range call: list pass, collect, fill, and the queries with more candidates than slots the general way.
+// acc: the call's result, this slice's queries appended.  out: amd_ivf_last_range_exact's counts.
+void range_exact_slice(amd_ivf* h, const float* d_x, size_t n, float radius, const IntRange& qr, uint64_t out[4], const amd_ivf_selector* sel,
+                       RangeRuns& acc) {
+    amd_ivf* index = ix(h);
+    const size_t nlist = h->nlist;
+    const uint64_t ntotal = index->h_list_off.size() == nlist + 1 ? index->h_list_off[nlist] : 0;
+    const unsigned long long* keep = sel ? sel->keep.as<unsigned long long>() : nullptr;
+    const uint32_t cap = exact_cap();
+    const uint64_t nblk = index->h_block_off.size() == nlist + 1 ? index->h_block_off[nlist] : 0;
+    if (sel && sel->keep.cap < nblk / 2 * 8) throw std::runtime_error("exact range search: the selector is shorter than the lists");
+    const size_t q0 = acc.count.size();
+    acc.count.resize(q0 + n, 0);
+    // which list pass: the rule of the k-NN call; no seed, so no centroids are needed, and there is no k to fit the slots
+    const int kind = exact_pick_pass(h, index, d_x, n, qr, nblk > 0 && ntotal < 0xffffffffull);
+    if (kind == 0) {
+        out[2] += n;
+        range_exact_general(h, d_x, nullptr, n, radius, qr, keep, acc.count.data() + q0, acc.labels, acc.dist);
+        return;
+    }
+    out[0] = std::max<uint64_t>(out[0], (uint64_t)kind);
+    hipStream_t s = h->stream;
+    // ---- 1. list pass: k = 1, every query's threshold the radius -- for the byte pass brought inside what its integers hold
+    // (exact_args.h: exact_range_threshold; NaN never gets here) --, every query's "seed id" 0: it has a threshold
+    bool none = false;
+    const float thr = kind == 1 ? exact_range_threshold(radius, &none) : radius;
+    h->w_rx_thr.ensure(n * sizeof(float));
+    h->w_rx_id.ensure(n * sizeof(int64_t));
+    h->w_rx_valid.ensure(n * 4);
+    h->w_rx_off.ensure(n * 8);
+    launch_fill_f32(h->w_rx_thr.as<float>(), n, thr, s);
+    HIP_CHECK(hipMemsetAsync(h->w_rx_id.p, 0, n * sizeof(int64_t), s));
+    const bool timed = exact_timed();
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (timed)
+        for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    exact_run_pass(h, index, d_x, n, 1, qr, kind, h->w_rx_thr.as<float>(), h->w_rx_id.as<int64_t>(), keep, cap, nblk, timed ? ev : nullptr);
+    // ---- 2. collect: the strict test on the caller's radius, the reference's order
+    ExactRangeArgs ca{};
+    ca.n = (uint32_t)n;
+    ca.cap = cap;
+    ca.metric = h->metric;
+    ca.radius = radius;
+    ca.cnt = h->w_ex_cnt.as<uint32_t>();
+    ca.cand = h->w_ex_cand.as<uint2>();
+    ca.valid = h->w_rx_valid.as<uint32_t>();
+    ca.flag = h->w_ex_flag.as<uint32_t>();
+    ca.totals = h->w_ex_tot.as<unsigned long long>();
+    launch_exact_range_collect(ca, s);
+    if (timed) HIP_CHECK(hipEventRecord(ev[2], s));
+    std::vector<uint32_t> flag(n), valid(n);
+    unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(flag.data(), h->w_ex_flag.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(valid.data(), h->w_rx_valid.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(tot, h->w_ex_tot.p, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(stream_sync(s));
+    if (timed) {
+        float a = 0, b = 0;
+        (void)hipEventElapsedTime(&a, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&b, ev[1], ev[2]);
+        fprintf(stderr, "[range exact] n %zu: pass%s %.3f ms, collect %.3f ms\n", n, kind == 1 ? "" : kind == 3 ? " (wide fp16 + rescoring)" : " (fp16 + rescoring)", a, b);
+        for (auto& e : ev) (void)hipEventDestroy(e);
+    }
+    out[1] += tot[0];
+    out[2] += tot[2];
+    out[3] = std::max<uint64_t>(out[3], tot[5]);
+    // ---- 3. fill: the answered queries' runs, contiguous in query order
+    std::vector<uint64_t> off(n);
+    std::vector<uint32_t> redo;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = total;
+        if (flag[i]) redo.push_back((uint32_t)i);
+        else total += valid[i];
+    }
+    std::vector<int64_t> labels(total);
+    std::vector<float> dist(total);
+    if (total) {
+        h->w_rx_lab.ensure(total * sizeof(int64_t));
+        h->w_rx_dis.ensure(total * sizeof(float));
+        HIP_CHECK(hipMemcpyAsync(h->w_rx_off.p, off.data(), n * 8, hipMemcpyHostToDevice, s));
+        ExactRangeFillArgs fa{};
+        fa.n = (uint32_t)n;
+        fa.cap = cap;
+        fa.cand = ca.cand;
+        fa.valid = ca.valid;
+        fa.flag = ca.flag;
+        fa.off = h->w_rx_off.as<uint64_t>();
+        fa.ids = index->d_ids.as<int64_t>();
+        fa.labels = h->w_rx_lab.as<int64_t>();
+        fa.dist = h->w_rx_dis.as<float>();
+        launch_exact_range_fill(fa, s);
+        HIP_CHECK(hipMemcpyAsync(labels.data(), h->w_rx_lab.p, total * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(dist.data(), h->w_rx_dis.p, total * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(stream_sync(s));  // (off, labels and dist are pageable memory of this frame)
+    }
+    if (redo.empty()) {
+        for (size_t i = 0; i < n; i++) acc.count[q0 + i] = valid[i];
+        acc.labels.insert(acc.labels.end(), labels.begin(), labels.end());
+        acc.dist.insert(acc.dist.end(), dist.begin(), dist.end());
+        return;
+    }
+    // ---- 4. overflow: the flagged queries the general way (the pass's part is on the host by now: range_core may overwrite the
+    // handle's result), their runs spliced in at their places
+    std::vector<size_t> rcount(redo.size());
+    std::vector<int64_t> rlabels;
+    std::vector<float> rdist;
+    range_exact_general(h, d_x, redo.data(), redo.size(), radius, qr, keep, rcount.data(), rlabels, rdist);
+    size_t r = 0, rat = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (flag[i]) {
+            acc.count[q0 + i] = rcount[r];
+            acc.labels.insert(acc.labels.end(), rlabels.begin() + (ptrdiff_t)rat, rlabels.begin() + (ptrdiff_t)(rat + rcount[r]));
+            acc.dist.insert(acc.dist.end(), rdist.begin() + (ptrdiff_t)rat, rdist.begin() + (ptrdiff_t)(rat + rcount[r]));
+            rat += rcount[r++];
+        } else {
+            acc.count[q0 + i] = valid[i];
+            acc.labels.insert(acc.labels.end(), labels.begin() + (ptrdiff_t)off[i], labels.begin() + (ptrdiff_t)(off[i] + valid[i]));
+            acc.dist.insert(acc.dist.end(), dist.begin() + (ptrdiff_t)off[i], dist.begin() + (ptrdiff_t)(off[i] + valid[i]));
+        }
+    }
+}
+
+void range_exact_core(amd_ivf* h, const float* d_x, size_t n, float radius, size_t* lims, const IntRange& qr, const amd_ivf_selector* sel = nullptr) {
+    upload_lists(h);  // (a pending journal is applied first, as every search does)
+    amd_ivf* index = ix(h);
+    const size_t nlist = h->nlist;
+    const uint64_t ntotal = index->h_list_off.size() == nlist + 1 ? index->h_list_off[nlist] : 0;
+    size_t st[4];
+    for (int i = 0; i < 4; i++) st[i] = h->stats_host[i];
+    uint64_t out[4] = {0, 0, 0, 0};
+    RangeRuns acc;
+    // an empty index, a selector without members, a NaN radius (the reference's compare is false for every entry): nothing to launch
+    if (ntotal == 0 || (sel && sel->info[1] == 0) || radius != radius) {
+        acc.count.assign(n, 0);
+    } else {
+        const size_t slice = 8192;  // (bounds the candidate buffers: slice x cap x 8 bytes)
+        for (size_t o = 0; o < n; o += slice)
+            range_exact_slice(h, d_x + o * (size_t)h->dpad, std::min(slice, n - o), radius, qr, out, sel, acc);
+    }
+    h->r_lims.assign(n + 1, 0);
+    for (size_t i = 0; i < n; i++) h->r_lims[i + 1] = h->r_lims[i] + acc.count[i];
+    h->r_labels.swap(acc.labels);
+    h->r_dist.swap(acc.dist);
+    memcpy(lims, h->r_lims.data(), (n + 1) * sizeof(size_t));
+    // the statistics as the exact k-NN call states them; a range search admits nothing to a heap
+    h->stats_host[0] = st[0] + n;
+    h->stats_host[1] = st[1] + n * nlist;
+    h->stats_host[2] = st[2] + n * (size_t)ntotal;
+    h->stats_host[3] = st[3];
+    for (int i = 0; i < 4; i++) h->last_range_exact[i] = out[i];
+}
+
+// n = 0: lims[0] = 0 and an empty result, nothing else
+void range_exact_none(amd_ivf* h, size_t* lims) {
+    h->r_lims.assign(1, 0);
+    h->r_labels.clear();
+    h->r_dist.clear();
+    lims[0] = 0;
 }
 
 // a usable device before the handle is read (without one: -4, as every call)
@@ -6175,6 +6404,75 @@ int amd_ivf_last_exact_detail(amd_ivf_t* h, uint64_t out[4]) {
     if (!h || !out) throw EngineError("null argument");
     require_device();
     for (int i = 0; i < 4; i++) out[i] = h->last_exact_detail[i];
+    API_END
+}
+
+// Exact range search over the whole index: amd_ivf_range_search_preassigned with nprobe = nlist and identity keys,
+// bit for bit, from one list pass.  The result is fetched with amd_ivf_range_results, as every range search's.
+int amd_ivf_range_search_exact(amd_ivf_t* h, size_t n, const float* x, float radius, size_t* lims) {
+    API_BEGIN
+    const std::string bad = exact_range_args_error(h != nullptr, x != nullptr, 0, n, lims);
+    if (!bad.empty()) throw EngineError(bad);
+    require_device();
+    use_device(h);
+    for (int i = 0; i < 4; i++) h->last_range_exact[i] = 0;
+    if (n == 0) {
+        range_exact_none(h, lims);
+        return 0;
+    }
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const QueryRows q = host_rows(h, x, n);
+    range_exact_core(h, q.d_x, n, radius, lims, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_range_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, float radius, size_t* lims) {
+    API_BEGIN
+    const std::string bad = exact_range_args_error(h != nullptr, true, start, n, lims);
+    if (!bad.empty()) throw EngineError(bad);
+    require_device();
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    for (int i = 0; i < 4; i++) h->last_range_exact[i] = 0;
+    if (n == 0) {
+        range_exact_none(h, lims);
+        return 0;
+    }
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    range_exact_core(h, q.d_x, n, radius, lims, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+// ... over a selector's members only.  selector_words refuses a selector of another index and a stale one from host state alone.
+int amd_ivf_range_search_exact_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, float radius, size_t* lims) {
+    API_BEGIN
+    const std::string bad = exact_range_selected_args_error(h != nullptr, s != nullptr, x != nullptr, 0, n, lims);
+    if (!bad.empty()) throw EngineError(bad);
+    selector_words(h, s);
+    require_device();
+    use_device(h);
+    for (int i = 0; i < 4; i++) h->last_range_exact[i] = 0;
+    if (n == 0) {
+        range_exact_none(h, lims);
+        return 0;
+    }
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const QueryRows q = host_rows(h, x, n);
+    range_exact_core(h, q.d_x, n, radius, lims, q.range, s);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_last_range_exact(amd_ivf_t* h, uint64_t out[4]) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("null argument");
+    require_device();
+    for (int i = 0; i < 4; i++) out[i] = h->last_range_exact[i];
     API_END
 }
 

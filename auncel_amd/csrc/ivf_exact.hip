@@ -8,6 +8,9 @@
 //   exact_select_kernel  a wave per query: the candidates in (distance, position) order; the result is read off them when no two
 //                        neighbours of the best k + 1 are equal (exact_args.h: exact_window_tied), else the query is flagged and
 //                        the caller searches it the general way
+//   exact_range_collect_kernel / exact_range_fill_kernel  the exact range search (amd_ivf_range_search_exact): the same
+//                        passes with the radius as every query's threshold; a query's candidates tested strictly against the radius,
+//                        sorted by global position -- the reference's order -- and written out as (id, distance) runs
 // The arithmetic is scan_mfma_pair_kernel's (ivf_kernels.hip): v_mfma_i32_32x32x32_i8 on re-centred bytes, the threshold folded into
 // the accumulators' start values, a v_max3 pre-test in front of the epilogue.  Every distance is the same exact integer.
 #include <hip/hip_runtime.h>
@@ -562,7 +565,101 @@ template <bool RESCORED> __global__ __launch_bounds__(64) void exact_select_kern
     }
 }
 
+// Exact range search (amd_ivf_range_search_exact): a query's candidates -- what the list pass emitted for the radius
+// as threshold, in the order the atomics fell -- become the reference's run.  A candidate is valid iff the reference's strict compare
+// holds for the caller's radius on its distance (the byte pass's exact integer, or the rescored reference value); the key of a valid
+// one is its global position above its distance's bits, of any other the largest there is, and a bitonic network over the next power
+// of two puts the valid ones first, in position order: positions are unique, so that order is determined, and it is the reference's
+// (lists in list-number order, entries in position order).  The run is written back to the head of the query's slots.
+// One workgroup per query, in two forms that share the grid: 64 threads -- ONE wave -- take the queries with up to 256 candidates
+// (and mark the ones with more candidates than slots: flag 2, nothing sorted), 256 threads the ones beyond; the other form's
+// queries are left at once.  Every barrier is between two stages of the network in LDS; memory is read once, before the first, and
+// written once, behind the last.  totals: as exact_select_kernel's.
+constexpr uint32_t EXACT_RANGE_WAVE_MAX = 256;
+template <int THREADS> __global__ __launch_bounds__(THREADS) void exact_range_collect_kernel(ExactRangeArgs a) {
+    extern __shared__ unsigned long long s_rkey[];
+    __shared__ uint32_t s_valid;
+    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    const uint32_t emitted = a.cnt[q];
+    const bool over = emitted > a.cap, large = emitted > EXACT_RANGE_WAVE_MAX;
+    if (THREADS == 64 ? (large && !over) : (!large || over)) return;  // (the same for the whole workgroup)
+    uint32_t valid = 0;
+    if (!over && emitted) {
+        uint32_t P = 2;
+        while (P < emitted) P <<= 1;  // (<= the next power of two of cap: what the launch reserved)
+        if (t == 0) s_valid = 0;
+        const bool l2 = a.metric == METRIC_L2;
+        for (uint32_t i = t; i < P; i += THREADS) {
+            unsigned long long key = EXACT_RANGE_INVALID;
+            if (i < emitted) {
+                const uint2 c = a.cand[(size_t)q * a.cap + i];
+                if (exact_range_within(l2, a.radius, __uint_as_float(c.y))) key = exact_range_key(c.x, c.y);
+            }
+            s_rkey[i] = key;
+        }
+        for (uint32_t kk = 2; kk <= P; kk <<= 1)
+            for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
+                __syncthreads();
+                for (uint32_t i = t; i < P; i += THREADS) {
+                    const uint32_t l = i ^ j;
+                    if (l > i) {
+                        const unsigned long long x = s_rkey[i], y = s_rkey[l];
+                        if ((x > y) == ((i & kk) == 0)) {
+                            s_rkey[i] = y;
+                            s_rkey[l] = x;
+                        }
+                    }
+                }
+            }
+        __syncthreads();
+        // the valid run ends where the largest key begins (at most one thread sees the edge; none: no valid candidate)
+        for (uint32_t i = t; i < P; i += THREADS)
+            if (s_rkey[i] != EXACT_RANGE_INVALID && (i + 1 == P || s_rkey[i + 1] == EXACT_RANGE_INVALID)) s_valid = i + 1;
+        __syncthreads();
+        valid = s_valid;
+        for (uint32_t i = t; i < valid; i += THREADS) {
+            const unsigned long long key = s_rkey[i];
+            a.cand[(size_t)q * a.cap + i] = make_uint2((uint32_t)(key >> 32), (uint32_t)key);
+        }
+    }
+    if (t == 0) {
+        const uint32_t flag = over ? 2u : 0u;
+        a.valid[q] = valid;
+        a.flag[q] = flag;
+        atomicAdd(&a.totals[flag], 1ull);
+        atomicAdd(&a.totals[3], (unsigned long long)emitted);
+        atomicAdd(&a.totals[4], (unsigned long long)valid);
+        atomicMax(&a.totals[5], (unsigned long long)emitted);
+    }
+}
+
+// (id, distance) of every answered query's run, at the query's place in the call's result
+__global__ __launch_bounds__(64) void exact_range_fill_kernel(ExactRangeFillArgs a) {
+    const uint32_t q = blockIdx.x;
+    if (a.flag[q]) return;
+    const uint32_t n = a.valid[q];
+    const uint64_t at = a.off[q];
+    for (uint32_t j = threadIdx.x; j < n; j += 64) {
+        const uint2 c = a.cand[(size_t)q * a.cap + j];
+        a.labels[at + j] = a.ids[c.x];
+        a.dist[at + j] = __uint_as_float(c.y);
+    }
+}
+
 }  // namespace
+
+void launch_exact_range_collect(const ExactRangeArgs& a, hipStream_t s) {
+    if (a.n == 0) return;
+    uint32_t P = 2;
+    while (P < a.cap) P <<= 1;
+    LAUNCH(exact_range_collect_kernel<64>, dim3(a.n), dim3(64), (size_t)std::min(P, EXACT_RANGE_WAVE_MAX) * 8, s, a);
+    if (a.cap > EXACT_RANGE_WAVE_MAX) LAUNCH(exact_range_collect_kernel<256>, dim3(a.n), dim3(256), (size_t)P * 8, s, a);
+}
+
+void launch_exact_range_fill(const ExactRangeFillArgs& a, hipStream_t s) {
+    if (a.n == 0) return;
+    LAUNCH(exact_range_fill_kernel, dim3(a.n), dim3(64), 0, s, a);
+}
 
 void launch_exact_blocks(const uint64_t* list_off, const uint64_t* block_off, const unsigned long long* keep, uint32_t nlist, uint64_t nblk,
                          uint2* out, hipStream_t s) {

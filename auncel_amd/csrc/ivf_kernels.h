@@ -829,6 +829,32 @@ void launch_scan_all_f16(const ExactScanF16Args& a, bool keep, hipStream_t s);
 void launch_scan_all_wide_f16(const ExactScanF16Args& a, bool keep, hipStream_t s);
 void launch_exact_rescore(const ExactRescoreArgs& a, hipStream_t s);
 void launch_exact_select(const ExactSelectArgs& a, hipStream_t s);
+// Exact range search (amd_ivf_range_search_exact): what stands where the selection stands in the k-NN call.  collect: a query's
+// min(cnt, cap) candidates are tested against the radius with the reference's strict compare, sorted by global position -- the
+// reference's order: lists in list-number order, entries in position order -- and the valid run written back to the head of the
+// query's candidate slots.  fill: (id, distance) of the runs into one contiguous result, query q's at off[q].
+struct ExactRangeArgs {
+    uint32_t n, cap;
+    int metric;
+    float radius;                 // the caller's, never the clamped threshold of the byte pass
+    const uint32_t* cnt;          // candidates emitted per query (beyond cap only the counter moved)
+    uint2* cand;                  // [n][cap] (global position, distance bits): in, and out for the valid run
+    uint32_t* valid;              // [n] entries of the valid run (0 for a flagged query)
+    uint32_t* flag;               // [n] 0 answered, 2 more candidates than slots
+    unsigned long long* totals;   // as ExactSelectArgs::totals ([1] stays 0: a range result knows no tie)
+};
+struct ExactRangeFillArgs {
+    uint32_t n, cap;
+    const uint2* cand;
+    const uint32_t* valid;
+    const uint32_t* flag;         // a flagged query writes nothing
+    const uint64_t* off;          // [n] where query q's run starts in labels / dist
+    const int64_t* ids;           // per stored vector
+    int64_t* labels;
+    float* dist;
+};
+void launch_exact_range_collect(const ExactRangeArgs& a, hipStream_t s);
+void launch_exact_range_fill(const ExactRangeFillArgs& a, hipStream_t s);
 
 inline uint32_t subset_range_key(float x) {
     uint32_t u;

@@ -263,6 +263,38 @@ int amd_ivf_last_exact_detail(amd_ivf_t* h, uint64_t out[4]);
 int amd_ivf_search_exact_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, float* D, int64_t* I);
 int amd_ivf_search_exact_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t k, float* D, int64_t* I);
 
+/* ---- exact range search over the whole index ---------------------------------------------
+ * The range ground truth: lims, and the labels and distances amd_ivf_range_results then returns from the same handle, are, bit for
+ * bit, what amd_ivf_range_search_preassigned(h, n, x, radius, nprobe = nlist, keys, lims) returns when every row of keys is
+ * 0, 1, ..., nlist - 1: the reference's range_search_preassigned over every list -- per query the lists in list-number order and
+ * the entries in position order, an entry kept iff radius > dis (L2) / radius < dis (inner product) on the reference's distance.
+ * _resident: over resident queries [start, start + n).  _selected: over the selector's members only -- what
+ * amd_ivf_range_search_preassigned_selected returns with those keys, and what the unselected call returns on
+ * amd_ivf_subset(h, the same selector).  All forms work on amd_ivf_clone contexts; a pending journal is applied first.
+ * How: the list pass of amd_ivf_search_exact, chosen by the same rule (bytes; fp16 + rescoring with "exact_float";
+ * wide fp16 with "exact_wide") with the radius as every query's threshold.  No seed search: the radius is the threshold.  No tie
+ * rule and no second pass for tied queries: the reference keeps an entry whatever it met before.  The pass emits a superset
+ * (dis <= / >= threshold); exact_range_collect_kernel applies the strict test to the caller's radius, sorts a query's candidates by
+ * global position -- unique, so the order is determined, and the reference's -- and exact_range_fill_kernel writes ids and
+ * distances.  The byte pass is handed the radius clamped to +-2^28 (beyond every distance the byte rule allows); the test is
+ * always on the radius as passed, +-inf included.  A query with more candidates than slots (AUNCEL_AMD_EXACT_CAP, above) is
+ * searched the general way -- amd_ivf_range_search_preassigned(_selected) with identity keys made on the device -- and its run
+ * spliced into its place; a call that qualifies for no pass (the conditions above, less the ones on k and the centroids) goes that
+ * way whole.
+ * Answered without a launch: n = 0 (lims[0] = 0), an empty index, a selector without members, a NaN radius (the reference's compare
+ * is false for every entry): all lims 0, an empty result.
+ * Returns -2 before the device is touched for: a null h, null lims, null x with n > 0, a null s, a resident range that wraps round,
+ * a selector of another index, a stale selector; -2 for a resident range outside the resident queries.
+ * amd_ivf_stats: nq += n, nlist += n x nlist, ndis += n x ntotal of h (members or not); nheap_updates does not move.
+ * amd_ivf_last_range_exact: out[0] the list pass the last exact range call ran (0 none, 1 bytes, 2 fp16 + rescoring, 3 wide fp16 +
+ * rescoring), out[1] queries answered from the pass, out[2] queries searched the general way (candidate overflow, or the whole call
+ * not qualifying), out[3] the largest emitted candidate count of any one query.  A call answered without a launch reports zeros.
+ * Not offered: tickets, a radius or a selector per query, byte-coded lists beyond 128 dimensions in the pass, d > 1024. */
+int amd_ivf_range_search_exact(amd_ivf_t* h, size_t n, const float* x, float radius, size_t* lims);
+int amd_ivf_range_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, float radius, size_t* lims);
+int amd_ivf_range_search_exact_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, float radius, size_t* lims);
+int amd_ivf_last_range_exact(amd_ivf_t* h, uint64_t out[4]);
+
 /* InvertedListScanner: set_query + set_list + scan_codes on a caller-owned raw binary heap
  * (simi/idxi, k entries, heapified by the caller as in tests/test_lowlevel_ivf.cpp:150-175);
  * returns the number of heap updates in *nup  [IndexIVFFlat.cpp:101-137] */
