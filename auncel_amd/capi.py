@@ -555,8 +555,9 @@ class Handle:
         return tuple(int(v) for v in out)
 
     def last_exact_detail(self):
-        """(which list pass the last exact call ran: 0 none, 1 bytes, 2 fp16 + rescoring; candidates emitted; candidates at or within
-        the threshold after rescoring; the largest emitted count of one query)"""
+        """(which list pass the last exact call ran: 0 none, 1 bytes, 2 fp16 + rescoring, 3 wide fp16 + rescoring (option
+        "exact_wide"), 4 wide bytes (option "exact_wide_bytes"); candidates emitted; candidates at or within the threshold after
+        rescoring; the largest emitted count of one query)"""
         out = (C.c_uint64 * 4)()
         _chk(lib().amd_ivf_last_exact_detail(self._h, out))
         return tuple(int(v) for v in out)
@@ -592,7 +593,7 @@ class Handle:
         return self._range_results(lims)
 
     def last_range_exact(self):
-        """(which list pass the last exact range call ran: 0 none, 1 bytes, 2 fp16 + rescoring, 3 wide fp16 + rescoring; queries
+        """(which list pass the last exact range call ran: 0 none, 1 bytes, 2 fp16 + rescoring, 3 wide fp16 + rescoring, 4 wide bytes; queries
         answered from the pass; queries searched the general way; the largest emitted candidate count of one query)"""
         out = (C.c_uint64 * 4)()
         _chk(lib().amd_ivf_last_range_exact(self._h, out))

@@ -4,7 +4,7 @@
 // nprobe and the mask of a block's live slots; of the exact range search (amd_ivf_range_search_exact) its checks, the threshold
 // the byte pass is given for a radius, the strict test and the candidates' key.  Plain C++, nothing of the device in it: the
 // kernels of ivf_exact.hip and the host read the same definitions, and it builds on its own (tests/cpp/exact_args_main.cpp,
-// exact_float_main.cpp, exact_selected_main.cpp and exact_range_main.cpp, which are what the address and undefined-behaviour
+// exact_float_main.cpp, exact_selected_main.cpp, exact_range_main.cpp and exact_wide_bytes_main.cpp, which are what the address and undefined-behaviour
 // sanitizers are pointed at).
 #pragma once
 #include <cstddef>
@@ -96,11 +96,11 @@ EXACT_HD inline bool exact_float_keep(bool l2, float C, float p, float yn, float
 }
 
 // Which list pass serves a call (exact_slice): 0 none -- the general way whole --, 1 the byte pass, 2 the fp16 pass + rescoring,
-// 3 the workgroup-tiled ("wide") fp16 pass + rescoring.  shape: what every pass needs besides d (centroids for the seed, blocks,
+// 3 the workgroup-tiled ("wide") fp16 pass + rescoring (4, the wide byte pass: exact_pass_kind_bytes below).  shape: what every pass needs besides d (centroids for the seed, blocks,
 // ntotal < 2^32, k < cap, k <= members; the exact range search, which has no seed and no k: blocks and ntotal < 2^32); bytes: the call runs on the lists' byte codes; float_ok: the filter's copies may be used
 // (filter_available: option "filter" != 0, float lists or byte codes not in use); the two options as booleans.  Up to 128
 // dimensions this is the rule that was there before the wide pass, whatever opt_wide says.  Beyond, only the wide pass exists:
-// byte-coded lists have no pass there, and 1024 is where the fp16 copy's row rule changes regime (ivf_filter.hip: half_scale_of).
+// byte-coded lists have no pass there by this rule, and 1024 is where the fp16 copy's row rule changes regime (ivf_filter.hip: half_scale_of).
 // What the caller still has to establish for 2 and 3: ensure_frag16 and a usable fp16 scale of the query rows.
 constexpr int EXACT_NARROW_MAX_D = 128, EXACT_WIDE_MAX_D = 1024;
 inline int exact_pass_kind(int d, bool shape, bool bytes, bool float_ok, bool opt_float, bool opt_wide) {
@@ -109,6 +109,16 @@ inline int exact_pass_kind(int d, bool shape, bool bytes, bool float_ok, bool op
     if (d <= EXACT_WIDE_MAX_D) return !bytes && float_ok && opt_float && opt_wide ? 3 : 0;
     return 0;
 }
+// ... with the byte pass beyond 128 dimensions (scan_all_wide_i8_kernel): 4 exactly when the shape holds, the call
+// runs on the lists' byte codes, 128 < d <= 1024 and option "exact_wide_bytes" is set; in every other case exact_pass_kind's answer.
+// Where it says 4 that answer was 0 (byte-coded lists have no fp16 pass), so no answer of 1, 2 or 3 changes, and the option is
+// independent of the two above.  A byte pass like 1: byte_queries, no fp16 operands, no rescoring.
+inline int exact_pass_kind_bytes(int d, bool shape, bool bytes, bool float_ok, bool opt_float, bool opt_wide, bool opt_wide_bytes) {
+    if (shape && bytes && d > EXACT_NARROW_MAX_D && d <= EXACT_WIDE_MAX_D && opt_wide_bytes) return 4;
+    return exact_pass_kind(d, shape, bytes, float_ok, opt_float, opt_wide);
+}
+// the passes whose candidates carry the byte scans' exact integer distance
+inline bool exact_kind_is_bytes(int kind) { return kind == 1 || kind == 4; }
 
 // ---- exact range search (amd_ivf_range_search_exact)
 // empty: the arguments are valid; else the message of the refusal.  As exact_args_error, with the lims where k-NN has (D, I): they are
@@ -126,7 +136,7 @@ inline std::string exact_range_selected_args_error(bool have_handle, bool have_s
     return exact_range_args_error(have_handle, have_queries, start, n, lims);
 }
 
-// The threshold the BYTE list pass is given for a radius.  scan_all_kernel emits nothing for a query whose threshold is NaN or beyond
+// The threshold the BYTE list passes are given for a radius.  scan_all_kernel (and scan_all_wide_i8_kernel) emits nothing for a query whose threshold is NaN or beyond
 // 2^30 in magnitude, and works in 32-bit integers around it; a radius may be any float.  The byte rule bounds every distance the pass
 // can meet by d m^2 <= 2^24 in magnitude (L2: 0 <= dis; IP: |dis| <= d m^2), so a radius beyond +-2^28 decides like +-2^28: on the
 // full side every entry passes `dis <= 2^28` / `dis >= -2^28`, on the empty side none passes `dis <= -2^28` / `dis >= 2^28`.  Inside
@@ -146,7 +156,7 @@ EXACT_HD inline bool exact_range_within(bool l2, float radius, float dis) { retu
 constexpr uint64_t EXACT_RANGE_INVALID = ~(uint64_t)0;
 EXACT_HD inline uint64_t exact_range_key(uint32_t position, uint32_t dist_bits) { return ((uint64_t)position << 32) | dist_bits; }
 
-// The wide pass's tile (scan_all_wide_f16_kernel): four waves walk a slab in chunks of four consecutive blocks, wave w block w; the
+// The wide passes' tile (scan_all_wide_f16_kernel, scan_all_wide_i8_kernel): four waves walk a slab in chunks of four consecutive blocks, wave w block w; the
 // query operand goes through LDS in stages of `sp` pieces.
 constexpr uint32_t EXACT_WIDE_QUERIES = 128, EXACT_WIDE_CHUNK = 4;
 // stages that cover J pieces

@@ -88,6 +88,7 @@ enum OptId {
     OPT_EXACT_SEED_NPROBE,  // amd_ivf_search_exact: nprobe of the seed search whose k-th distance is the list pass's threshold
     OPT_EXACT_FLOAT,        // amd_ivf_search_exact over float lists: 1 the fp16 matrix-core list pass + rescoring, 0 (the default) the general way
     OPT_EXACT_WIDE,         // ... beyond 128 dimensions (up to 1024), with exact_float: 1 the workgroup-tiled fp16 list pass, 0 (the default) the general way
+    OPT_EXACT_WIDE_BYTES,   // amd_ivf_search_exact over byte-coded lists beyond 128 dimensions (up to 1024): 1 the workgroup-tiled byte list pass, 0 (the default) the general way
     N_OPT
 };
 struct OptSpec {
@@ -118,6 +119,7 @@ const OptSpec OPT_TABLE[N_OPT] = {
     {"exact_seed_nprobe", "AUNCEL_AMD_EXACT_SEED", nullptr},
     {"exact_float", "AUNCEL_AMD_EXACT_FLOAT", nullptr},
     {"exact_wide", "AUNCEL_AMD_EXACT_WIDE", nullptr},
+    {"exact_wide_bytes", "AUNCEL_AMD_EXACT_WIDE_BYTES", nullptr},
 };
 struct Options {
     // (atomic: amd_ivf_set_option on the owner may run while search contexts cloned from it are searching; a search reads the
@@ -4734,7 +4736,7 @@ static int opt_id(const char* key) {
 static double opt_default(OptId id) {
     switch (id) {
         case OPT_COARSE_TIES: case OPT_TIE_FIX: case OPT_PHASE_TIMING: return -1;
-        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: case OPT_EXACT_FLOAT: case OPT_EXACT_WIDE: return 0;  // (0: chosen per search)
+        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: case OPT_EXACT_FLOAT: case OPT_EXACT_WIDE: case OPT_EXACT_WIDE_BYTES: return 0;  // (0: chosen per search)
         case OPT_ROUND_FIRST: return 12;
         case OPT_SCAN_PIPELINED: return 7;
         case OPT_FILTER: case OPT_COARSE_PICK: return 2;
@@ -5879,16 +5881,18 @@ size_t exact_general(amd_ivf* h, const float* d_x, const uint32_t* idx, size_t m
 }
 
 // Which list pass serves a slice of n queries -- of the exact k-NN call and of the exact range search alike: there is one rule
-// (exact_args.h: exact_pass_kind).  Byte codes up to four K-steps, under the rule every byte scan runs under; the filter's fp16 copy
+// (exact_args.h: exact_pass_kind_bytes, which is exact_pass_kind() but for its answer 4).  Byte codes up to four K-steps -- with option "exact_wide_bytes" up to 1024 dimensions, by the
+// workgroup-tiled byte kernel --, under the rule every byte scan runs under; the filter's fp16 copy
 // of float lists where lists and queries have a usable scale (ivf_filter.hip: no non-finite element, magnitudes within 2^+-24, no
 // row tiny beside the largest -- which also keeps every reference distance finite), beyond 128 dimensions by the workgroup-tiled
 // kernel.  shape_ok: what the caller's pass needs besides (exact_pass_kind's `shape`).
 int exact_pick_pass(amd_ivf* h, amd_ivf* index, const float* d_x, size_t n, const IntRange& qr, bool shape_ok) {
     const bool bytes = index->have_codes8 && h->allow_bytes && index->db_range.bytes_with(qr, (size_t)h->d);
-    int kind = exact_pass_kind(h->d, shape_ok, bytes, filter_available(h, index, bytes), opt(h, OPT_EXACT_FLOAT, 0) != 0,
-                               opt(h, OPT_EXACT_WIDE, 0) != 0);
+    int kind = exact_pass_kind_bytes(h->d, shape_ok, bytes, filter_available(h, index, bytes), opt(h, OPT_EXACT_FLOAT, 0) != 0,
+                                     opt(h, OPT_EXACT_WIDE, 0) != 0, opt(h, OPT_EXACT_WIDE_BYTES, 0) != 0);
     hipStream_t s = h->stream;
-    bool pass16 = kind >= 2 && ensure_frag16(index);
+    const bool want16 = kind == 2 || kind == 3;
+    bool pass16 = want16 && ensure_frag16(index);
     if (pass16) {
         uint32_t info[4] = {0, 0, 0, 0};
         h->w_qinfo.ensure(16);
@@ -5898,18 +5902,18 @@ int exact_pick_pass(amd_ivf* h, amd_ivf* index, const float* d_x, size_t n, cons
         HIP_CHECK(stream_sync(s));
         pass16 = filter_half_scale(info, h->d) != 0.f;
     }
-    if (!pass16 && kind >= 2) kind = 0;
+    if (!pass16 && want16) kind = 0;
     return kind;
 }
 
-// The list pass of kind 1 .. 3 over every block for n queries whose thresholds are row q's last entry of (seed_D, seed_I) [n][k]
+// The list pass of kind 1 .. 4 over every block for n queries whose thresholds are row q's last entry of (seed_D, seed_I) [n][k]
 // (an id < 0 there: no threshold, the query emits nothing): the block table (keep: a selector's words, the table then carries the
 // members' mask), the counters and totals zeroed, the pass, and behind an fp16 pass the rescoring.  Leaves the candidates in
 // w_ex_cnt / w_ex_cand ([n][cap]).  ev: null, or three events of which [0] is recorded in front of the pass and [1] behind it.
 void exact_run_pass(amd_ivf* h, amd_ivf* index, const float* d_x, size_t n, size_t k, const IntRange& qr, int kind, const float* seed_D,
                     const int64_t* seed_I, const unsigned long long* keep, uint32_t cap, uint64_t nblk, hipEvent_t* ev) {
     const size_t nlist = h->nlist;
-    const bool pass = kind == 1, wide = kind == 3;
+    const bool pass = exact_kind_is_bytes(kind), wide = kind == 3;
     hipStream_t s = h->stream;
     if (pass && !byte_queries(h, index, d_x, n, qr)) throw std::runtime_error("exact search: no byte view of the queries");
     h->w_ex_blk.ensure(nblk * sizeof(uint2));
@@ -5939,7 +5943,12 @@ void exact_run_pass(amd_ivf* h, amd_ivf* index, const float* d_x, size_t n, size
     sa.cap = cap;
     if (pass) {
         if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
-        launch_scan_all(sa, keep != nullptr, s);
+        if (kind == 4) {
+            sa.slab = exact_wide_slab(sa.slab);
+            launch_scan_all_wide_i8(sa, keep != nullptr, s);
+        } else {
+            launch_scan_all(sa, keep != nullptr, s);
+        }
     } else {
         // the fp16 query operands and FilterParams by the filter's own launches (the seed search may have left them; not every seed does)
         h->w_xf.ensure(n * (size_t)filter_steps(h->d) * 8 * sizeof(float));  // (rows of 8 filter_steps16(d) floats: no more than this)
@@ -6008,7 +6017,7 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     // which list pass (exact_pick_pass)
     const bool shape_ok = index->have_centroids && nblk > 0 && ntotal < 0xffffffffull && k < cap && k <= members;
     const int kind = exact_pick_pass(h, index, d_x, n, qr, shape_ok);
-    const bool pass = kind == 1, wide = kind == 3;
+    const bool pass = exact_kind_is_bytes(kind), wide = kind == 3;
     hipStream_t s = h->stream;
     // ---- 1. seed: an ordinary fixed-nprobe search; its k-th distance is a distance of k stored entries, so the true k-th is within it.
     // Under a selector it is the k-th among the members the seed saw; as `seed` lists hold too few of them when the selector is
@@ -6067,7 +6076,7 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         float a = 0, b = 0;
         (void)hipEventElapsedTime(&a, ev[0], ev[1]);
         (void)hipEventElapsedTime(&b, ev[1], ev[2]);
-        fprintf(stderr, "[exact] n %zu k %zu seed %zu: pass%s %.3f ms, select %.3f ms\n", n, k, seed, pass ? "" : wide ? " (wide fp16 + rescoring)" : " (fp16 + rescoring)", a, b);
+        fprintf(stderr, "[exact] n %zu k %zu seed %zu: pass%s %.3f ms, select %.3f ms\n", n, k, seed, kind == 4 ? " (wide bytes)" : pass ? "" : wide ? " (wide fp16 + rescoring)" : " (fp16 + rescoring)", a, b);
         for (auto& e : ev) (void)hipEventDestroy(e);
     }
     for (int i = 0; i < 4; i++) out[i] += tot[i];
@@ -6176,7 +6185,7 @@ void range_exact_slice(amd_ivf* h, const float* d_x, size_t n, float radius, con
     // ---- 1. list pass: k = 1, every query's threshold the radius -- for the byte pass brought inside what its integers hold
     // (exact_args.h: exact_range_threshold; NaN never gets here) --, every query's "seed id" 0: it has a threshold
     bool none = false;
-    const float thr = kind == 1 ? exact_range_threshold(radius, &none) : radius;
+    const float thr = exact_kind_is_bytes(kind) ? exact_range_threshold(radius, &none) : radius;
     h->w_rx_thr.ensure(n * sizeof(float));
     h->w_rx_id.ensure(n * sizeof(int64_t));
     h->w_rx_valid.ensure(n * 4);
@@ -6211,7 +6220,7 @@ void range_exact_slice(amd_ivf* h, const float* d_x, size_t n, float radius, con
         float a = 0, b = 0;
         (void)hipEventElapsedTime(&a, ev[0], ev[1]);
         (void)hipEventElapsedTime(&b, ev[1], ev[2]);
-        fprintf(stderr, "[range exact] n %zu: pass%s %.3f ms, collect %.3f ms\n", n, kind == 1 ? "" : kind == 3 ? " (wide fp16 + rescoring)" : " (fp16 + rescoring)", a, b);
+        fprintf(stderr, "[range exact] n %zu: pass%s %.3f ms, collect %.3f ms\n", n, kind == 4 ? " (wide bytes)" : kind == 1 ? "" : kind == 3 ? " (wide fp16 + rescoring)" : " (fp16 + rescoring)", a, b);
         for (auto& e : ev) (void)hipEventDestroy(e);
     }
     out[1] += tot[0];

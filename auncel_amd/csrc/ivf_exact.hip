@@ -3,6 +3,7 @@
 // consecutive blocks, and a block that has been fetched is contracted with every query block of the tile before it is let go.
 //   scan_all_kernel      the list pass: emits, per query, every stored entry at or within the query's threshold (the k-th distance of
 //                        a seed search of the same lists) as (global position, distance)
+//   scan_all_wide_i8_kernel  the same pass for byte lists of 128 < d <= 1024 (option "exact_wide_bytes"): the query operand through LDS
 //   exact_blocks_kernel  the block table the pass reads; <KEEP>, of a call under an id selector: the mask of a block's slots that hold a
 //                        MEMBER, so the same pass (KEEP) emits members only with nothing added to its loop
 //   exact_select_kernel  a wave per query: the candidates in (distance, position) order; the result is read off them when no two
@@ -462,6 +463,238 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
+// The byte list pass beyond 128 dimensions (option "exact_wide_bytes"): scan_all_kernel's arithmetic and epilogue on
+// scan_all_wide_f16_kernel's tile.  At J = mfma_ksteps(d) = 5 .. 32 pieces of 32 dimensions the query operand no longer fits a wave's
+// registers.  Grid: (slabs of the block stream, tiles of 128 queries).  The four waves walk the slab in chunks of four consecutive
+// blocks; wave w owns block w of the chunk, whose J pieces of 1 KiB stream from the byte fragments once, straight into a register
+// ring of SP pieces (the slot of piece j is refilled with piece j + SP right behind its MFMAs; behind a chunk's last stage with the
+// first SP pieces of the wave's block of the next chunk).  The query operand -- up to four query blocks of byte_queries' rows, wave w
+// staging the rows of query block w -- goes through LDS in stages of SP pieces, double-buffered, one LDS-only barrier per stage.
+// Per-query threshold, start value, u and cx are written to LDS once per workgroup, with scan_all_kernel's rules: no full seed
+// result, a NaN or a threshold beyond 2^30 in magnitude => nothing passes.  The epilogue is scan_all_kernel's: start values folded
+// into the accumulators, a v_max3 pre-test, the exact non-strict re-test, the block table's count or (KEEP) members' mask, one
+// returning atomic add per candidate, (position, float(dis)) stored while the slot is below cap.
+// Straight-line code (mfma_tile.h says why): every wave runs the same loads, stages and barriers -- a wave without a query block
+// stages the tile's first row (nothing reads it), a wave without a block in the stream's last chunk recomputes the chunk's first
+// block and drops the result, a piece index past J reads piece J - 1 and its stage slot is written as zero.  Nothing is read past
+// nblk x J KiB of the fragments or past row n - 1.
+// Every partial sum stays within int32.  A re-centred byte is in [-128, 127], so a product is at most 2^14 in magnitude and a dot
+// product over d <= 1024 dimensions, complete or partial, at most 2^24.  The start value is -(u >> 1) (L2) or -u (IP) with
+// u = cx - (T + 1) or (T - 1) - cx, |T| <= 2^30 and |cx| <= 2^24 (L2: a sum of d squares) or < 2^25 (IP: 128 sum - 16384 d), so it is
+// below 2^30 + 2^25 + 2 in magnitude -- the value of a slot without a threshold is -2^30 --, and start value + partial sum below
+// 2^30 + 2^25 + 2^24 + 2 < 2^31.  The epilogue undoes the start value first: acc + (u >> 1) / acc + u is x.y itself, and the
+// distance is the byte scans' integer, at most 2^24 under the byte rule d m^2 <= 2^24.
+typedef const v4i __attribute__((address_space(1)))* gv4i;
+#ifndef AUNCEL_EXACT_WIDE_I8_SP
+#define AUNCEL_EXACT_WIDE_I8_SP 6  // (the fp16 tile's; a stage is not longer than the fewest pieces, J = 5, rounded up to a pair)
+#endif
+constexpr int EXACT_WIDE_I8_SP = AUNCEL_EXACT_WIDE_I8_SP;
+constexpr size_t exact_wide_i8_stage_ints(int QB, int SP) { return (size_t)QB * SP * 256; }
+// (the stages + start value, cx, u and T per query)
+constexpr size_t EXACT_WIDE_I8_LDS = (2 * exact_wide_i8_stage_ints(EXACT_WIDE_QB, EXACT_WIDE_I8_SP) + 4 * (size_t)EXACT_WIDE_QUERIES) * sizeof(int);
+static_assert(EXACT_WIDE_I8_SP >= 2 && EXACT_WIDE_I8_SP % 2 == 0 && EXACT_WIDE_I8_SP <= 6, "pieces are taken in pairs; the ring's first fill reads pieces 0 .. SP - 1 of J >= 5 (past J: J - 1)");
+static_assert(2 * EXACT_WIDE_I8_LDS <= 160 * 1024, "two workgroups per compute unit");
+
+// A wave's hold on the byte query operand of a tile of J pieces (WideTile's counterpart for the byte scans' row layout: a lane's
+// pieces are contiguous, 16 bytes each): qp = its lane's part of the row it stages (row stride 32 J bytes, + 16 J h).
+template <int SP, int QB> struct WideTileI8 {
+    int* s_a;  // [2 buffers][query block][piece of the stage][lane][4]
+    const int8_t* qp;
+    int J, wave, lane;
+
+    __device__ __forceinline__ int* slot(int buf, int qb, int jj) const { return s_a + ((size_t)(buf * QB + qb) * SP + jj) * 256 + (size_t)lane * 4; }
+    __device__ __forceinline__ void stage_load(int s, v4i (&st)[SP]) const {
+#pragma unroll
+        for (int jj = 0; jj < SP; jj++) {
+            const int j = s * SP + jj;
+            st[jj] = *(gv4i)(uintptr_t)(qp + 16 * (j < J ? j : J - 1));
+        }
+    }
+    // (pieces that pad the last stage contribute 0 x y)
+    __device__ __forceinline__ void stage_write(int s, int buf, const v4i (&st)[SP]) const {
+#pragma unroll
+        for (int jj = 0; jj < SP; jj++) *reinterpret_cast<v4i*>(slot(buf, wave, jj)) = s * SP + jj < J ? st[jj] : v4i{0, 0, 0, 0};
+    }
+    template <int NQB> __device__ __forceinline__ void load_a(int buf, int jj, v4i (&af)[NQB]) const {
+#pragma unroll
+        for (int q = 0; q < NQB; q++) af[q] = *reinterpret_cast<const v4i*>(slot(buf, q, jj));
+    }
+    template <int NQB> static __device__ __forceinline__ void mac(v16i* acc, const v4i (&af)[NQB], const v4i& bv) {
+#pragma unroll
+        for (int q = 0; q < NQB; q++) acc[q] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[q], bv, acc[q], 0, 0, 0);
+    }
+    // one stage, as WideTile::stage: stage sn loaded in front and written to the other buffer behind, the operands of an even and an
+    // odd piece read from LDS one MFMA group ahead, refill(j, jj, br[jj]) right behind the MFMAs of piece j = s SP + jj, one barrier
+    template <int NQB, class Refill> __device__ __forceinline__ void stage(int buf, int s, int sn, v4i (&st)[SP], v16i* acc, v4i (&br)[SP], Refill&& refill) const {
+        v4i afA[NQB], afB[NQB];
+        stage_load(sn, st);
+#pragma unroll
+        for (int jj = 0; jj < SP; jj += 2) {
+            const int j = s * SP + jj;
+            if (jj == 0) load_a(buf, 0, afA);
+            load_a(buf, jj + 1, afB);
+            __builtin_amdgcn_sched_barrier(0);
+            mac<NQB>(acc, afA, br[jj]);
+            __builtin_amdgcn_sched_barrier(0);
+            refill(j, jj, br[jj]);
+            if (jj + 2 < SP) load_a(buf, jj + 2, afA);
+            __builtin_amdgcn_sched_barrier(0);
+            mac<NQB>(acc, afB, br[jj + 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            refill(j + 1, jj + 1, br[jj + 1]);
+        }
+        stage_write(sn, buf ^ 1, st);
+        lds_barrier();
+    }
+};
+
+template <int METRIC, bool KEEP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_all_wide_i8_kernel(ExactScanArgs a) {
+    constexpr int QB = EXACT_WIDE_QB, SP = EXACT_WIDE_I8_SP;
+    extern __shared__ __align__(16) unsigned char exact_wide_i8_smem[];
+    int* s_a = reinterpret_cast<int*>(exact_wide_i8_smem);
+    int* s_init = s_a + 2 * exact_wide_i8_stage_ints(QB, SP);
+    int* s_cx = s_init + EXACT_WIDE_QUERIES;
+    int* s_u = s_cx + EXACT_WIDE_QUERIES;
+    int* s_T = s_u + EXACT_WIDE_QUERIES;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int m = lane & 31, h = lane >> 5;
+    const int J = (int)mfma_ksteps(a.d);
+    const int S = exact_wide_stages(J, SP);
+    const size_t qstride = (size_t)J * 32;
+    const size_t block_bytes = (size_t)J * 1024;
+    const uint32_t qbase = blockIdx.y * EXACT_WIDE_QUERIES;
+    const uint64_t B0 = (uint64_t)blockIdx.x * a.slab;
+    const uint64_t B1 = B0 + a.slab < a.nblk ? B0 + a.slab : a.nblk;  // (slab: a multiple of 4; nblk is even)
+    if (qbase >= a.n || B0 >= B1) return;                            // (the same for the whole workgroup)
+    const uint32_t nq = a.n - qbase < EXACT_WIDE_QUERIES ? a.n - qbase : EXACT_WIDE_QUERIES;  // query slots of the tile that hold a query
+    const int nqb = (int)((nq + 31) >> 5);
+
+    // ---- per query slot, once for the slab: threshold and start value, as scan_all_kernel (slot = thread & 127: the upper two
+    // waves write what the lower two write)
+    {
+        const uint32_t sl = threadIdx.x & (EXACT_WIDE_QUERIES - 1);
+        const bool sok = sl < nq;
+        const uint32_t q = qbase + (sok ? sl : 0u);
+        const int cx = a.query_cx[q];
+        const size_t last = (size_t)q * a.k + (a.k - 1);
+        const float tau = a.seed_D[last];
+        const bool have = sok && a.seed_I[last] >= 0 && tau == tau && fabsf(tau) <= 1073741824.f;
+        int T = METRIC == METRIC_L2 ? -1 : 0x7fffffff, u = 0, init = -1073741824;  // (no threshold: nothing passes either test)
+        if (have) {
+            if (METRIC == METRIC_L2) {
+                T = (int)floorf(tau);          // dis <= tau <=> dis <= floor(tau) <=> dis < T + 1
+                u = (cx - (T + 1)) & ~1;       // keep <=> 2 x.y - |y|^2 > |x|^2 - (T + 1) >= u
+                init = -(u >> 1);
+            } else {
+                T = (int)ceilf(tau);           // dis >= tau <=> dis >= ceil(tau) <=> dis > T - 1
+                u = (T - 1) - cx;              // keep <=> x.y + cy > (T - 1) - cx
+                init = -u;
+            }
+        }
+        s_init[sl] = init;
+        s_cx[sl] = cx;
+        s_u[sl] = u;
+        s_T[sl] = T;
+    }
+    // ---- the query operand: this wave stages the rows of query block `wave`, lane (m, h) bytes 16 J h + 16 j .. + 15 of query slot
+    // 32 wave + m, piece j (a slot without a query: the tile's first row; nothing of its accumulators is emitted)
+    const uint32_t qslot = (uint32_t)wave * 32u + (uint32_t)m;
+    const WideTileI8<SP, QB> tile{s_a, a.queries8 + (size_t)(qbase + (qslot < nq ? qslot : 0u)) * qstride + (size_t)h * (size_t)(16 * J), J, wave, lane};
+    v4i st[SP];
+    tile.stage_load(0, st);
+    tile.stage_write(0, 0, st);
+    // ---- this wave's block, a ring of SP pieces
+    const uint8_t* fbase = a.codes_frag + (size_t)lane * 16;
+    v4i br[SP];
+    {
+        const uint8_t* b0 = fbase + exact_wide_wave_block(B0, B1, (uint32_t)wave) * block_bytes;
+#pragma unroll
+        for (int jj = 0; jj < SP; jj++) br[jj] = *(gv4i)(uintptr_t)(b0 + (size_t)(jj < J ? jj : J - 1) * 1024);  // (J = 5: slot 5 is multiplied by zero)
+    }
+    lds_barrier();  // stage 0 and the per-query constants are in LDS
+
+    auto run = [&](auto NQBc) __attribute__((always_inline)) {
+        constexpr int NQB = decltype(NQBc)::value;
+        int buf = 0;
+        for (uint64_t c = B0; c < B1; c += EXACT_WIDE_CHUNK) {
+            const bool active = (uint32_t)wave < exact_wide_chunk_blocks(c, B1);
+            const uint64_t cur = exact_wide_wave_block(c, B1, (uint32_t)wave);
+            const uint64_t cn = c + EXACT_WIDE_CHUNK < B1 ? c + EXACT_WIDE_CHUNK : c;  // (no next chunk: this one again, never used)
+            const uint8_t* bbase = fbase + cur * block_bytes;
+            const uint8_t* nbase = fbase + exact_wide_wave_block(cn, B1, (uint32_t)wave) * block_bytes;
+            const int cy = a.code_cy[cur * 32 + (uint64_t)m];
+            const uint2 bi = a.blk[cur];
+            // register 4 g + c of lane half h of tile t belongs to query slot 32 t + 8 g + 4 h + c: the start values, LDS -> accumulator
+            v16i acc[NQB];
+#pragma unroll
+            for (int t = 0; t < NQB; t++)
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const v4i t0 = *reinterpret_cast<const v4i*>(&s_init[32 * t + 8 * g + 4 * h]);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) acc[t][4 * g + e] = t0[e];
+                }
+            for (int s = 0; s < S; s++) {
+                const bool lasts = s + 1 == S;
+                // the refill of ring slot jj: piece j + SP of this block (past J: J - 1 again, multiplied by a zero stage slot), or
+                // behind the last stage piece jj of the wave's block of the next chunk
+                auto refill = [&](int j, int jj, v4i& bv) __attribute__((always_inline)) {
+                    const uint8_t* src = lasts ? nbase + (size_t)(jj < J ? jj : J - 1) * 1024 : bbase + (size_t)(j + SP < J ? j + SP : J - 1) * 1024;
+                    bv = *(gv4i)(uintptr_t)src;
+                };
+                tile.template stage<NQB>(buf, s, lasts ? 0 : s + 1, st, acc, br, refill);  // (behind a chunk's last stage: stage 0, for the next chunk)
+                buf ^= 1;
+            }
+            // ---- epilogue: lane m holds slot m of the block; a slot behind the list's end, a non-member, a block computed in another
+            // wave's stead: nothing (the bound no accumulator exceeds)
+            const bool vok = active && (KEEP ? ((bi.y >> m) & 1u) != 0 : (uint32_t)m < bi.y);
+            const int hc = !vok ? 0x7fffffff : METRIC == METRIC_L2 ? cy >> 1 : -cy;
+            const uint32_t pos = bi.x + (uint32_t)m;
+            // (opaque per chunk, as in scan_all_wide_f16_kernel: nothing of the epilogue's addressing is hoisted out of the chunk loop)
+            int h4 = 4 * h;
+            asm volatile("" : "+v"(h4));
+            static_for(std::make_integer_sequence<int, NQB>{}, [&](auto TT) __attribute__((always_inline)) {
+                constexpr int qb = 32 * decltype(TT)::value;
+                const v16i& ac = acc[decltype(TT)::value];
+                static_for(std::make_integer_sequence<int, 2>{}, [&](auto H) __attribute__((always_inline)) {
+                    constexpr int r0 = decltype(H)::value * 8;
+                    // eight registers at a time: their largest value against the bound first (v_max3): most groups hold no candidate
+                    int mx = max(max(ac[r0], ac[r0 + 1]), ac[r0 + 2]);
+                    mx = max(max(mx, ac[r0 + 3]), ac[r0 + 4]);
+                    mx = max(max(mx, ac[r0 + 5]), ac[r0 + 6]);
+                    mx = max(mx, ac[r0 + 7]);
+                    if (__ballot(mx > hc) == 0) return;
+                    static_for(std::make_integer_sequence<int, 8>{}, [&](auto R) __attribute__((always_inline)) {
+                        constexpr int reg = r0 + decltype(R)::value;
+                        constexpr int q0 = qb + (reg & 3) + 8 * (reg >> 2);  // query slot of lane half 0; half 1: q0 + 4
+                        if (ac[reg] > hc) {
+                            const int sl = q0 + h4;
+                            const int cq = s_cx[sl], uq = s_u[sl], Tq = s_T[sl];
+                            // the contraction itself: acc = x.y - floor(u / 2) (L2) | x.y - u (IP)
+                            const int t = METRIC == METRIC_L2 ? 2 * (ac[reg] + (uq >> 1)) - cy : ac[reg] + uq + cy;
+                            const int dis = METRIC == METRIC_L2 ? cq - t : cq + t;
+                            const bool keep = (uint32_t)sl < nq && (METRIC == METRIC_L2 ? dis <= Tq : dis >= Tq);
+                            if (keep) {
+                                const uint32_t q = qbase + (uint32_t)sl;
+                                const uint32_t slot = atomicAdd(&a.cnt[q], 1u);  // (beyond cap only the counter moves)
+                                if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = make_uint2(pos, __float_as_uint((float)dis));
+                            }
+                        }
+                    });
+                });
+            });
+        }
+    };
+    switch (nqb) {
+        case 1: run(std::integral_constant<int, 1>{}); break;
+        case 2: run(std::integral_constant<int, 2>{}); break;
+        case 3: run(std::integral_constant<int, 3>{}); break;
+        default: run(std::integral_constant<int, 4>{}); break;
+    }
+}
+
 // The candidates of the fp16 pass recomputed from the fp32 rows in the reference's rounding sequence (ivf_dev.h: exact_distance; as in
 // rescore_kernel four neighbouring lanes take one candidate, lane l running sum l, then (s0 + s1) + (s2 + s3)): the distance's bits
 // replace the candidate's second word.  A workgroup per query, 64 candidates a trip.
@@ -739,6 +972,19 @@ void launch_scan_all_wide_f16(const ExactScanF16Args& a, bool keep, hipStream_t 
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXACT_WIDE_LDS);
         if (e != hipSuccess) throw std::runtime_error(std::string("scan_all_wide_f16_kernel: cannot reserve LDS: ") + hipGetErrorString(e));
         LAUNCH(kern, grid, block, EXACT_WIDE_LDS, s, a);
+    });
+}
+
+void launch_scan_all_wide_i8(const ExactScanArgs& a, bool keep, hipStream_t s) {
+    if (a.n == 0 || a.nblk == 0) return;
+    if (a.d <= EXACT_NARROW_MAX_D || a.d > EXACT_WIDE_MAX_D || a.slab == 0 || (a.slab & (EXACT_WIDE_CHUNK - 1)) || (a.nblk & 1))
+        throw std::runtime_error("scan_all_wide_i8_kernel: shape not supported");
+    const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + EXACT_WIDE_QUERIES - 1) / EXACT_WIDE_QUERIES)), block(256);
+    with_metric_keep(a.metric, keep, [&](auto M, auto K) {
+        auto kern = scan_all_wide_i8_kernel<decltype(M)::value, decltype(K)::value>;
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXACT_WIDE_I8_LDS);
+        if (e != hipSuccess) throw std::runtime_error(std::string("scan_all_wide_i8_kernel: cannot reserve LDS: ") + hipGetErrorString(e));
+        LAUNCH(kern, grid, block, EXACT_WIDE_I8_LDS, s, a);
     });
 }
 

@@ -753,7 +753,7 @@ struct KeepArgs {
 void launch_keep_rows(const KeepArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------- exact search over the whole index (ivf_exact.hip)
-// The list pass of amd_ivf_search_exact: every query against every 32-vector block of the byte fragments (d <= 128), candidates at or
+// The list pass of amd_ivf_search_exact: every query against every 32-vector block of the byte fragments (d <= 128; launch_scan_all_wide_i8: up to 1024), candidates at or
 // within the query's threshold appended to the query's buffer.  seed_D / seed_I: the n x k result of a search of the same lists
 // (row q's last entry is the threshold; id < 0 there: the query has none and emits nothing).
 struct ExactScanArgs {
@@ -827,6 +827,9 @@ void launch_scan_all_f16(const ExactScanF16Args& a, bool keep, hipStream_t s);
 // the same pass for 128 < d <= 1024 (option "exact_wide"): a workgroup tile of 128 queries x 4 blocks, the query operand through LDS;
 // a.slab is a multiple of 4 (exact_args.h: exact_wide_slab)
 void launch_scan_all_wide_f16(const ExactScanF16Args& a, bool keep, hipStream_t s);
+// the byte pass for 128 < d <= 1024 (option "exact_wide_bytes"): the same tile on the byte fragments, launch_scan_all's arguments and
+// candidates (global position, the exact integer distance); a.slab is a multiple of 4 (exact_args.h: exact_wide_slab)
+void launch_scan_all_wide_i8(const ExactScanArgs& a, bool keep, hipStream_t s);
 void launch_exact_rescore(const ExactRescoreArgs& a, hipStream_t s);
 void launch_exact_select(const ExactSelectArgs& a, hipStream_t s);
 // Exact range search (amd_ivf_range_search_exact): what stands where the selection stands in the k-NN call.  collect: a query's

@@ -217,10 +217,14 @@ int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t npro
  * without it such calls go the general way whole, as they always did.
  * Beyond 128 dimensions, up to 1024, the same pass exists as a workgroup tile (scan_all_wide_f16_kernel: 128 queries x 4 list blocks,
  * the query operand through LDS); it serves a call when option "exact_wide" = 1 is set beside "exact_float" = 1 and every other
- * condition of the fp16 pass holds, and amd_ivf_last_exact_detail then reports pass 3.  Still the general way whole: d > 1024, and
- * byte-valued lists beyond 128 dimensions whose byte codes are in use (their general way is the int8 matrix-core scan already; with
- * amd_ivf_set_byte_codes(h, 0), or queries outside the byte rule, they take the wide pass as float lists do).
- * A call goes the general way whole when it does not qualify: d > 128 (d > 1024 or no "exact_wide" for the fp16 pass), k > ntotal, k >= the candidate slots, no centroids; for the
+ * condition of the fp16 pass holds, and amd_ivf_last_exact_detail then reports pass 3.
+ * Byte-valued lists beyond 128 dimensions, up to 1024, whose byte codes are in use have the byte pass on the same tile
+ * (scan_all_wide_i8_kernel: v_mfma_i32_32x32x32_i8 on the byte fragments the byte scans keep, exact integers, no rescoring); it
+ * serves a call when option "exact_wide_bytes" = 1 is set -- independent of "exact_float" and "exact_wide" -- and
+ * amd_ivf_last_exact_detail then reports pass 4.  Still the general way whole: d > 1024, and such lists without
+ * "exact_wide_bytes" (their general way is the int8 matrix-core scan already; with amd_ivf_set_byte_codes(h, 0), or queries
+ * outside the byte rule, the call is decided as one over float lists is: the wide fp16 pass if its options ask for it).
+ * A call goes the general way whole when it does not qualify: d > 128 (d > 1024, no "exact_wide" for the fp16 pass, no "exact_wide_bytes" for the byte pass), k > ntotal, k >= the candidate slots, no centroids; for the
  * fp16 pass also option "exact_float" 0, option "filter" below 2, and lists or queries of the call without a usable fp16 scale (a non-finite element,
  * magnitudes outside 2^+-24, a row that is not all zero whose largest element is below 2^-12 of the matrix's).
  * Returns -2 before the device is touched for: a null h, k = 0, null x / D / I with n > 0, a resident range that wraps round; -2 for
@@ -232,11 +236,11 @@ int amd_ivf_search(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t npro
  * because equal distances met, out[2] queries searched the general way for any other reason (candidate overflow, no full seed
  * result, the whole call not qualifying), out[3] candidates the list pass emitted (the fp16 pass: before rescoring), summed over
  * the call.
- * amd_ivf_last_exact_detail: out[0] the list pass the last exact call ran (0 none, 1 bytes, 2 fp16 + rescoring, 3 wide fp16 + rescoring), out[1] candidates
+ * amd_ivf_last_exact_detail: out[0] the list pass the last exact call ran (0 none, 1 bytes, 2 fp16 + rescoring, 3 wide fp16 + rescoring, 4 wide bytes), out[1] candidates
  * emitted, out[2] candidates at or within the threshold (the fp16 pass: after rescoring, among the stored ones; the byte pass emits
- * nothing else: out[1]), out[3] the largest emitted count of any one query -- what the candidate slots have to hold.
+ * nothing else: out[1]; so does the wide byte pass), out[3] the largest emitted count of any one query -- what the candidate slots have to hold.
  * AUNCEL_AMD_EXACT_CAP=<n> (a test knob, read once per process): candidate slots per query, 2..4096 (default 1024).
- * Not offered: d > 128 in the pass unless option "exact_wide" asks for it (float lists up to d = 1024), tickets, store_pairs / max_codes, the adaptive rule -- there is no exact entry point that takes
+ * Not offered: d > 128 in the pass unless option "exact_wide" (float lists up to d = 1024) or "exact_wide_bytes" (byte-coded lists up to d = 1024) asks for it, d > 1024, tickets, store_pairs / max_codes, the adaptive rule -- there is no exact entry point that takes
  * any of them.  (Selectors: below.) */
 int amd_ivf_search_exact(amd_ivf_t* h, size_t n, const float* x, size_t k, float* D, int64_t* I);
 int amd_ivf_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, float* D, int64_t* I);
@@ -272,11 +276,11 @@ int amd_ivf_search_exact_resident_selected(amd_ivf_t* h, const amd_ivf_selector_
  * amd_ivf_range_search_preassigned_selected returns with those keys, and what the unselected call returns on
  * amd_ivf_subset(h, the same selector).  All forms work on amd_ivf_clone contexts; a pending journal is applied first.
  * How: the list pass of amd_ivf_search_exact, chosen by the same rule (bytes; fp16 + rescoring with "exact_float";
- * wide fp16 with "exact_wide") with the radius as every query's threshold.  No seed search: the radius is the threshold.  No tie
+ * wide fp16 with "exact_wide"; wide bytes with "exact_wide_bytes") with the radius as every query's threshold.  No seed search: the radius is the threshold.  No tie
  * rule and no second pass for tied queries: the reference keeps an entry whatever it met before.  The pass emits a superset
  * (dis <= / >= threshold); exact_range_collect_kernel applies the strict test to the caller's radius, sorts a query's candidates by
  * global position -- unique, so the order is determined, and the reference's -- and exact_range_fill_kernel writes ids and
- * distances.  The byte pass is handed the radius clamped to +-2^28 (beyond every distance the byte rule allows); the test is
+ * distances.  The byte passes are handed the radius clamped to +-2^28 (beyond every distance the byte rule allows); the test is
  * always on the radius as passed, +-inf included.  A query with more candidates than slots (AUNCEL_AMD_EXACT_CAP, above) is
  * searched the general way -- amd_ivf_range_search_preassigned(_selected) with identity keys made on the device -- and its run
  * spliced into its place; a call that qualifies for no pass (the conditions above, less the ones on k and the centroids) goes that
@@ -287,9 +291,9 @@ int amd_ivf_search_exact_resident_selected(amd_ivf_t* h, const amd_ivf_selector_
  * a selector of another index, a stale selector; -2 for a resident range outside the resident queries.
  * amd_ivf_stats: nq += n, nlist += n x nlist, ndis += n x ntotal of h (members or not); nheap_updates does not move.
  * amd_ivf_last_range_exact: out[0] the list pass the last exact range call ran (0 none, 1 bytes, 2 fp16 + rescoring, 3 wide fp16 +
- * rescoring), out[1] queries answered from the pass, out[2] queries searched the general way (candidate overflow, or the whole call
+ * rescoring, 4 wide bytes), out[1] queries answered from the pass, out[2] queries searched the general way (candidate overflow, or the whole call
  * not qualifying), out[3] the largest emitted candidate count of any one query.  A call answered without a launch reports zeros.
- * Not offered: tickets, a radius or a selector per query, byte-coded lists beyond 128 dimensions in the pass, d > 1024. */
+ * Not offered: tickets, a radius or a selector per query, byte-coded lists beyond 128 dimensions in the pass unless option "exact_wide_bytes" asks for it, d > 1024. */
 int amd_ivf_range_search_exact(amd_ivf_t* h, size_t n, const float* x, float radius, size_t* lims);
 int amd_ivf_range_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, float radius, size_t* lims);
 int amd_ivf_range_search_exact_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, float radius, size_t* lims);
@@ -634,6 +638,10 @@ int amd_ivf_set_byte_codes(amd_ivf_t* h, int enable);
  *   "exact_wide"      ... beyond 128 dimensions (128 < d <= 1024), beside "exact_float" = 1: 1 the workgroup-tiled fp16 list     0
  *                     pass with rescoring, 0 the general way for the whole call (AUNCEL_AMD_EXACT_WIDE is the environment's
  *                     form).  Cannot change a result
+ *   "exact_wide_bytes" amd_ivf_search_exact over byte-coded lists beyond 128 dimensions (128 < d <= 1024): 1 the workgroup-tiled  0
+ *                     byte list pass (exact integers, no rescoring), 0 the general way for the whole call; independent of
+ *                     "exact_float" / "exact_wide" (AUNCEL_AMD_EXACT_WIDE_BYTES is the environment's form).  Cannot change a
+ *                     result
  * amd_ivf_set_option(h, key, NAN) returns the key to "unset".  May be called while search contexts of the index are searching: a
  * search reads what shapes its launches once, when it starts, so the change takes effect with the searches that start after it. */
 int amd_ivf_set_option(amd_ivf_t* h, const char* key, double value);
