@@ -14,6 +14,9 @@
 //                        sorted by global position -- the reference's order -- and written out as (id, distance) runs
 // The arithmetic is scan_mfma_pair_kernel's (ivf_kernels.hip): v_mfma_i32_32x32x32_i8 on re-centred bytes, the threshold folded into
 // the accumulators' start values, a v_max3 pre-test in front of the epilogue.  Every distance is the same exact integer.
+// What two passes share exists once: exact_i8_slot / exact_i8_emit (a query slot's constants, the epilogue of an accumulator tile)
+// for the two byte passes, exact_f16_slot / exact_f16_emit for the two fp16 passes, the workgroup
+// tile of both wide passes in mfma_tile.h, and launch_exact_wide.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,9 +27,6 @@
 namespace amdivf {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 // per 32-vector block of the fragment copy: (global position of its first slot, slots that hold an entry).  A list is padded to an
 // even number of blocks: the block in which a list ends holds fewer than 32 entries, the padding block behind it none.
@@ -51,6 +51,81 @@ __global__ __launch_bounds__(256) void exact_blocks_kernel(const uint64_t* __res
 __global__ __launch_bounds__(256) void identity_keys_kernel(int64_t* __restrict__ keys, uint64_t total, uint32_t nlist) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < total) keys[i] = (int64_t)(i % nlist);
+}
+
+// What the two byte list passes below share: a query slot's constants and the epilogue of an accumulator tile.
+// Every partial sum stays within int32.  A re-centred byte is in [-128, 127], so a product is at most 2^14 in magnitude and a dot
+// product over d <= 1024 dimensions, complete or partial, at most 2^24.  The start value is -(u >> 1) (L2) or -u (IP) with
+// u = cx - (T + 1) or (T - 1) - cx, |T| <= 2^30 and |cx| <= 2^24 (L2: a sum of d squares) or < 2^25 (IP: 128 sum - 16384 d), so it is
+// below 2^30 + 2^25 + 2 in magnitude -- the value of a slot without a threshold is -2^30 --, and start value + partial sum below
+// 2^30 + 2^25 + 2^24 + 2 < 2^31.  The epilogue undoes the start value first: acc + (u >> 1) / acc + u is x.y itself, and the
+// distance is the byte scans' integer, at most 2^24 under the byte rule d m^2 <= 2^24.
+// A query slot's threshold T, what the pre-test compares with (u) and the accumulators' start value (ok false: no query in the slot,
+// then q is any valid query).  No full seed result, a NaN or a threshold beyond 2^30 in magnitude: nothing passes either test.
+// Returns (init, cx, u, T).
+template <int METRIC> __device__ __forceinline__ int4 exact_i8_slot(const ExactScanArgs& a, uint32_t q, bool ok) {
+    const int cx = a.query_cx[q];
+    const size_t last = (size_t)q * a.k + (a.k - 1);
+    const float tau = a.seed_D[last];
+    const bool have = ok && a.seed_I[last] >= 0 && tau == tau && fabsf(tau) <= 1073741824.f;
+    int T = METRIC == METRIC_L2 ? -1 : 0x7fffffff, u = 0, init = -1073741824;
+    if (have) {
+        if (METRIC == METRIC_L2) {
+            T = (int)floorf(tau);          // dis <= tau <=> dis <= floor(tau) <=> dis < T + 1
+            u = (cx - (T + 1)) & ~1;       // keep <=> 2 x.y - |y|^2 > |x|^2 - (T + 1) >= u
+            init = -(u >> 1);
+        } else {
+            T = (int)ceilf(tau);           // dis >= tau <=> dis >= ceil(tau) <=> dis > T - 1
+            u = (T - 1) - cx;              // keep <=> x.y + cy > (T - 1) - cx
+            init = -u;
+        }
+    }
+    return make_int4(init, cx, u, T);
+}
+// The start of one 32 x 32 accumulator tile of the wide pass: register 4 g + c of lane half h belongs to query slot
+// QB0 + 8 g + 4 h + c, whose start value (s_init: exact_i8_slot's, by slot) goes from LDS into the accumulator.  h4 = 4 h.
+// (scan_all_kernel keeps its own fold of its two tiles: through this function, in a one-tile or a several-tile form, its sixteen
+// instantiations came out with other registers in 406 - 832 lines and missed the timing rule at one point: DESIGN.md 13.6)
+template <int QB0> __device__ __forceinline__ void exact_i8_start(v16i& acc, const int* s_init, int h4) {
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const v4i t = *reinterpret_cast<const v4i*>(&s_init[QB0 + 8 * g + h4]);
+#pragma unroll
+        for (int c = 0; c < 4; c++) acc[4 * g + c] = t[c];
+    }
+}
+// The epilogue of that tile for qbase's nq queries (s_cx, s_u, s_T: exact_i8_slot's values by slot); lane m holds the entry at `pos`,
+// cy its constant, hc the bound of the pre-test: cy >> 1 (L2) / -cy (IP), INT_MAX where nothing may be emitted.  Eight registers at
+// a time: their largest value against the bound first (v_max3), since most groups hold no candidate; a register that passes
+// recomputes the distance and tests it exactly, NON-strictly; one returning atomic add per candidate.
+template <int METRIC, int QB0>
+__device__ __forceinline__ void exact_i8_emit(const ExactScanArgs& a, const v16i& acc, const int* s_cx, const int* s_u, const int* s_T, int h4,
+                                              uint32_t qbase, uint32_t nq, int hc, int cy, uint32_t pos) {
+    static_for(std::make_integer_sequence<int, 2>{}, [&](auto H) __attribute__((always_inline)) {
+        constexpr int r0 = decltype(H)::value * 8;
+        int mx = max(max(acc[r0], acc[r0 + 1]), acc[r0 + 2]);
+        mx = max(max(mx, acc[r0 + 3]), acc[r0 + 4]);
+        mx = max(max(mx, acc[r0 + 5]), acc[r0 + 6]);
+        mx = max(mx, acc[r0 + 7]);
+        if (__ballot(mx > hc) == 0) return;
+        static_for(std::make_integer_sequence<int, 8>{}, [&](auto R) __attribute__((always_inline)) {
+            constexpr int reg = r0 + decltype(R)::value;
+            constexpr int q0 = QB0 + (reg & 3) + 8 * (reg >> 2);  // query slot of lane half 0; half 1: q0 + 4
+            if (acc[reg] > hc) {
+                const int sl = q0 + h4;
+                const int cq = s_cx[sl], uq = s_u[sl], Tq = s_T[sl];
+                // the contraction itself: acc = x.y - floor(u / 2) (L2) | x.y - u (IP)
+                const int t = METRIC == METRIC_L2 ? 2 * (acc[reg] + (uq >> 1)) - cy : acc[reg] + uq + cy;
+                const int dis = METRIC == METRIC_L2 ? cq - t : cq + t;
+                const bool keep = (uint32_t)sl < nq && (METRIC == METRIC_L2 ? dis <= Tq : dis >= Tq);
+                if (keep) {
+                    const uint32_t q = qbase + (uint32_t)sl;
+                    const uint32_t slot = atomicAdd(&a.cnt[q], 1u);  // (beyond cap only the counter moves)
+                    if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = make_uint2(pos, __float_as_uint((float)dis));
+                }
+            }
+        });
+    });
 }
 
 // The list pass.  Grid: (slabs of the block stream, tiles of 256 queries).  Wave w of a workgroup holds the A operands of query
@@ -87,27 +162,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
     // ---- per query slot (slot = lane): threshold and start value
     {
         const bool sok = (uint32_t)lane < nq;
-        const uint32_t q = qbase + (sok ? (uint32_t)lane : 0u);
-        const int cx = a.query_cx[q];
-        const size_t last = (size_t)q * a.k + (a.k - 1);
-        const float tau = a.seed_D[last];
-        const bool have = sok && a.seed_I[last] >= 0 && tau == tau && fabsf(tau) <= 1073741824.f;
-        int T = METRIC == METRIC_L2 ? -1 : 0x7fffffff, u = 0, init = -1073741824;  // (no threshold: nothing passes either test)
-        if (have) {
-            if (METRIC == METRIC_L2) {
-                T = (int)floorf(tau);          // dis <= tau <=> dis <= floor(tau) <=> dis < T + 1
-                u = (cx - (T + 1)) & ~1;       // keep <=> 2 x.y - |y|^2 > |x|^2 - (T + 1) >= u
-                init = -(u >> 1);
-            } else {
-                T = (int)ceilf(tau);           // dis >= tau <=> dis >= ceil(tau) <=> dis > T - 1
-                u = (T - 1) - cx;              // keep <=> x.y + cy > (T - 1) - cx
-                init = -u;
-            }
-        }
-        s_init[wave][lane] = init;
-        s_cx[wave][lane] = cx;
-        s_u[wave][lane] = u;
-        s_T[wave][lane] = T;
+        const int4 v = exact_i8_slot<METRIC>(a, qbase + (sok ? (uint32_t)lane : 0u), sok);
+        s_init[wave][lane] = v.x;
+        s_cx[wave][lane] = v.y;
+        s_u[wave][lane] = v.z;
+        s_T[wave][lane] = v.w;
     }
     // ---- the A operands: lane (m, h) of query block g holds the bytes of query slot 32 g + m
     v4i af0[NKS], af1[NKS];
@@ -166,37 +225,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         __builtin_amdgcn_sched_barrier(0);
         fetch(b, cyv, biv, i + 2 < B1 ? i + 2 : i);  // (past the slab's end: its own block again, never used)
         __builtin_amdgcn_sched_barrier(0);
-        auto epilogue = [&](const v16i& acc, auto QB) {
-            constexpr int qb = decltype(QB)::value;
-            static_for(std::make_integer_sequence<int, 2>{}, [&](auto H) {
-                constexpr int r0 = decltype(H)::value * 8;
-                // eight registers at a time: their largest value against the bound first (v_max3): most groups hold no candidate
-                int mx = max(max(acc[r0], acc[r0 + 1]), acc[r0 + 2]);
-                mx = max(max(mx, acc[r0 + 3]), acc[r0 + 4]);
-                mx = max(max(mx, acc[r0 + 5]), acc[r0 + 6]);
-                mx = max(mx, acc[r0 + 7]);
-                if (__ballot(mx > hc) == 0) return;
-                static_for(std::make_integer_sequence<int, 8>{}, [&](auto R) {
-                    constexpr int reg = r0 + decltype(R)::value;
-                    constexpr int q0 = qb + (reg & 3) + 8 * (reg >> 2);  // query slot of lane half 0; half 1: q0 + 4
-                    if (acc[reg] > hc) {
-                        const int sl = q0 + 4 * h;
-                        const int cq = s_cx[wave][sl], uq = s_u[wave][sl], Tq = s_T[wave][sl];
-                        // the contraction itself: acc = x.y - floor(u / 2) (L2) | x.y - u (IP)
-                        const int t = METRIC == METRIC_L2 ? 2 * (acc[reg] + (uq >> 1)) - cy : acc[reg] + uq + cy;
-                        const int dis = METRIC == METRIC_L2 ? cq - t : cq + t;
-                        const bool keep = (uint32_t)sl < nq && (METRIC == METRIC_L2 ? dis <= Tq : dis >= Tq);
-                        if (keep) {
-                            const uint32_t q = qbase + (uint32_t)sl;
-                            const uint32_t slot = atomicAdd(&a.cnt[q], 1u);  // (beyond cap only the counter moves)
-                            if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = make_uint2(pos, __float_as_uint((float)dis));
-                        }
-                    }
-                });
-            });
-        };
-        epilogue(acc0, std::integral_constant<int, 0>{});
-        if (two) epilogue(acc1, std::integral_constant<int, 32>{});
+        exact_i8_emit<METRIC, 0>(a, acc0, s_cx[wave], s_u[wave], s_T[wave], 4 * h, qbase, nq, hc, cy, pos);
+        if (two) exact_i8_emit<METRIC, 32>(a, acc1, s_cx[wave], s_u[wave], s_T[wave], 4 * h, qbase, nq, hc, cy, pos);
     };
     for (uint64_t i = B0; i < B1; i += 2) {
         step(b0, cy0, bi0, i);
@@ -370,7 +400,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr int QB = EXACT_WIDE_QB, SP = EXACT_WIDE_SP;
     extern __shared__ __align__(16) unsigned char exact_wide_smem[];
     float* s_a = reinterpret_cast<float*>(exact_wide_smem);  // [2 buffers][query block][piece of the stage][lane][4]
-    float* s_u = s_a + 2 * wide_stage_floats(QB, SP);
+    float* s_u = s_a + 2 * wide_stage_words(QB, SP);
     float* s_c = s_u + EXACT_WIDE_QUERIES;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -400,7 +430,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- the query operand: this wave stages the rows of query block `wave`, lane (m, h) halves 16 j + 8 h .. + 7 of query slot
     // 32 wave + m, piece j (a slot without a query: the tile's first row; its bound is +inf)
     const uint32_t qslot = (uint32_t)wave * 32u + (uint32_t)m;
-    const WideTile<true, SP, QB> tile{s_a, a.xf + (size_t)(qbase + (qslot < nq ? qslot : 0u)) * qstride + (size_t)h * 4, J, wave, lane};
+    const WideTile<TileFloat<true>, SP, QB> tile{s_a, a.xf + (size_t)(qbase + (qslot < nq ? qslot : 0u)) * qstride + (size_t)h * 4, J, wave, lane};
     v4f st[SP];
     tile.stage_load(0, st);
     tile.stage_write(0, 0, st);
@@ -470,90 +500,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ring of SP pieces (the slot of piece j is refilled with piece j + SP right behind its MFMAs; behind a chunk's last stage with the
 // first SP pieces of the wave's block of the next chunk).  The query operand -- up to four query blocks of byte_queries' rows, wave w
 // staging the rows of query block w -- goes through LDS in stages of SP pieces, double-buffered, one LDS-only barrier per stage.
-// Per-query threshold, start value, u and cx are written to LDS once per workgroup, with scan_all_kernel's rules: no full seed
-// result, a NaN or a threshold beyond 2^30 in magnitude => nothing passes.  The epilogue is scan_all_kernel's: start values folded
-// into the accumulators, a v_max3 pre-test, the exact non-strict re-test, the block table's count or (KEEP) members' mask, one
-// returning atomic add per candidate, (position, float(dis)) stored while the slot is below cap.
+// Per-query threshold, start value, u and cx are written to LDS once per workgroup (exact_i8_slot); the start values are folded into
+// the accumulators (exact_i8_start) and the epilogue is exact_i8_emit, with the block table's count or (KEEP) members' mask.
 // Straight-line code (mfma_tile.h says why): every wave runs the same loads, stages and barriers -- a wave without a query block
 // stages the tile's first row (nothing reads it), a wave without a block in the stream's last chunk recomputes the chunk's first
 // block and drops the result, a piece index past J reads piece J - 1 and its stage slot is written as zero.  Nothing is read past
 // nblk x J KiB of the fragments or past row n - 1.
-// Every partial sum stays within int32.  A re-centred byte is in [-128, 127], so a product is at most 2^14 in magnitude and a dot
-// product over d <= 1024 dimensions, complete or partial, at most 2^24.  The start value is -(u >> 1) (L2) or -u (IP) with
-// u = cx - (T + 1) or (T - 1) - cx, |T| <= 2^30 and |cx| <= 2^24 (L2: a sum of d squares) or < 2^25 (IP: 128 sum - 16384 d), so it is
-// below 2^30 + 2^25 + 2 in magnitude -- the value of a slot without a threshold is -2^30 --, and start value + partial sum below
-// 2^30 + 2^25 + 2^24 + 2 < 2^31.  The epilogue undoes the start value first: acc + (u >> 1) / acc + u is x.y itself, and the
-// distance is the byte scans' integer, at most 2^24 under the byte rule d m^2 <= 2^24.
-typedef const v4i __attribute__((address_space(1)))* gv4i;
 #ifndef AUNCEL_EXACT_WIDE_I8_SP
 #define AUNCEL_EXACT_WIDE_I8_SP 6  // (the fp16 tile's; a stage is not longer than the fewest pieces, J = 5, rounded up to a pair)
 #endif
 constexpr int EXACT_WIDE_I8_SP = AUNCEL_EXACT_WIDE_I8_SP;
-constexpr size_t exact_wide_i8_stage_ints(int QB, int SP) { return (size_t)QB * SP * 256; }
-// (the stages + start value, cx, u and T per query)
-constexpr size_t EXACT_WIDE_I8_LDS = (2 * exact_wide_i8_stage_ints(EXACT_WIDE_QB, EXACT_WIDE_I8_SP) + 4 * (size_t)EXACT_WIDE_QUERIES) * sizeof(int);
+constexpr size_t EXACT_WIDE_I8_LDS = wide_lds_bytes(EXACT_WIDE_QB, EXACT_WIDE_I8_SP, 4);  // (the stages + start value, cx, u and T per query)
 static_assert(EXACT_WIDE_I8_SP >= 2 && EXACT_WIDE_I8_SP % 2 == 0 && EXACT_WIDE_I8_SP <= 6, "pieces are taken in pairs; the ring's first fill reads pieces 0 .. SP - 1 of J >= 5 (past J: J - 1)");
 static_assert(2 * EXACT_WIDE_I8_LDS <= 160 * 1024, "two workgroups per compute unit");
-
-// A wave's hold on the byte query operand of a tile of J pieces (WideTile's counterpart for the byte scans' row layout: a lane's
-// pieces are contiguous, 16 bytes each): qp = its lane's part of the row it stages (row stride 32 J bytes, + 16 J h).
-template <int SP, int QB> struct WideTileI8 {
-    int* s_a;  // [2 buffers][query block][piece of the stage][lane][4]
-    const int8_t* qp;
-    int J, wave, lane;
-
-    __device__ __forceinline__ int* slot(int buf, int qb, int jj) const { return s_a + ((size_t)(buf * QB + qb) * SP + jj) * 256 + (size_t)lane * 4; }
-    __device__ __forceinline__ void stage_load(int s, v4i (&st)[SP]) const {
-#pragma unroll
-        for (int jj = 0; jj < SP; jj++) {
-            const int j = s * SP + jj;
-            st[jj] = *(gv4i)(uintptr_t)(qp + 16 * (j < J ? j : J - 1));
-        }
-    }
-    // (pieces that pad the last stage contribute 0 x y)
-    __device__ __forceinline__ void stage_write(int s, int buf, const v4i (&st)[SP]) const {
-#pragma unroll
-        for (int jj = 0; jj < SP; jj++) *reinterpret_cast<v4i*>(slot(buf, wave, jj)) = s * SP + jj < J ? st[jj] : v4i{0, 0, 0, 0};
-    }
-    template <int NQB> __device__ __forceinline__ void load_a(int buf, int jj, v4i (&af)[NQB]) const {
-#pragma unroll
-        for (int q = 0; q < NQB; q++) af[q] = *reinterpret_cast<const v4i*>(slot(buf, q, jj));
-    }
-    template <int NQB> static __device__ __forceinline__ void mac(v16i* acc, const v4i (&af)[NQB], const v4i& bv) {
-#pragma unroll
-        for (int q = 0; q < NQB; q++) acc[q] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[q], bv, acc[q], 0, 0, 0);
-    }
-    // one stage, as WideTile::stage: stage sn loaded in front and written to the other buffer behind, the operands of an even and an
-    // odd piece read from LDS one MFMA group ahead, refill(j, jj, br[jj]) right behind the MFMAs of piece j = s SP + jj, one barrier
-    template <int NQB, class Refill> __device__ __forceinline__ void stage(int buf, int s, int sn, v4i (&st)[SP], v16i* acc, v4i (&br)[SP], Refill&& refill) const {
-        v4i afA[NQB], afB[NQB];
-        stage_load(sn, st);
-#pragma unroll
-        for (int jj = 0; jj < SP; jj += 2) {
-            const int j = s * SP + jj;
-            if (jj == 0) load_a(buf, 0, afA);
-            load_a(buf, jj + 1, afB);
-            __builtin_amdgcn_sched_barrier(0);
-            mac<NQB>(acc, afA, br[jj]);
-            __builtin_amdgcn_sched_barrier(0);
-            refill(j, jj, br[jj]);
-            if (jj + 2 < SP) load_a(buf, jj + 2, afA);
-            __builtin_amdgcn_sched_barrier(0);
-            mac<NQB>(acc, afB, br[jj + 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            refill(j + 1, jj + 1, br[jj + 1]);
-        }
-        stage_write(sn, buf ^ 1, st);
-        lds_barrier();
-    }
-};
 
 template <int METRIC, bool KEEP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_all_wide_i8_kernel(ExactScanArgs a) {
     constexpr int QB = EXACT_WIDE_QB, SP = EXACT_WIDE_I8_SP;
     extern __shared__ __align__(16) unsigned char exact_wide_i8_smem[];
-    int* s_a = reinterpret_cast<int*>(exact_wide_i8_smem);
-    int* s_init = s_a + 2 * exact_wide_i8_stage_ints(QB, SP);
+    int* s_a = reinterpret_cast<int*>(exact_wide_i8_smem);  // [2 buffers][query block][piece of the stage][lane][4]
+    int* s_init = s_a + 2 * wide_stage_words(QB, SP);
     int* s_cx = s_init + EXACT_WIDE_QUERIES;
     int* s_u = s_cx + EXACT_WIDE_QUERIES;
     int* s_T = s_u + EXACT_WIDE_QUERIES;
@@ -571,37 +537,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const uint32_t nq = a.n - qbase < EXACT_WIDE_QUERIES ? a.n - qbase : EXACT_WIDE_QUERIES;  // query slots of the tile that hold a query
     const int nqb = (int)((nq + 31) >> 5);
 
-    // ---- per query slot, once for the slab: threshold and start value, as scan_all_kernel (slot = thread & 127: the upper two
-    // waves write what the lower two write)
+    // ---- per query slot, once for the slab: threshold and start value (slot = thread & 127: the upper two waves write what the
+    // lower two write)
     {
         const uint32_t sl = threadIdx.x & (EXACT_WIDE_QUERIES - 1);
         const bool sok = sl < nq;
-        const uint32_t q = qbase + (sok ? sl : 0u);
-        const int cx = a.query_cx[q];
-        const size_t last = (size_t)q * a.k + (a.k - 1);
-        const float tau = a.seed_D[last];
-        const bool have = sok && a.seed_I[last] >= 0 && tau == tau && fabsf(tau) <= 1073741824.f;
-        int T = METRIC == METRIC_L2 ? -1 : 0x7fffffff, u = 0, init = -1073741824;  // (no threshold: nothing passes either test)
-        if (have) {
-            if (METRIC == METRIC_L2) {
-                T = (int)floorf(tau);          // dis <= tau <=> dis <= floor(tau) <=> dis < T + 1
-                u = (cx - (T + 1)) & ~1;       // keep <=> 2 x.y - |y|^2 > |x|^2 - (T + 1) >= u
-                init = -(u >> 1);
-            } else {
-                T = (int)ceilf(tau);           // dis >= tau <=> dis >= ceil(tau) <=> dis > T - 1
-                u = (T - 1) - cx;              // keep <=> x.y + cy > (T - 1) - cx
-                init = -u;
-            }
-        }
-        s_init[sl] = init;
-        s_cx[sl] = cx;
-        s_u[sl] = u;
-        s_T[sl] = T;
+        const int4 v = exact_i8_slot<METRIC>(a, qbase + (sok ? sl : 0u), sok);
+        s_init[sl] = v.x;
+        s_cx[sl] = v.y;
+        s_u[sl] = v.z;
+        s_T[sl] = v.w;
     }
     // ---- the query operand: this wave stages the rows of query block `wave`, lane (m, h) bytes 16 J h + 16 j .. + 15 of query slot
     // 32 wave + m, piece j (a slot without a query: the tile's first row; nothing of its accumulators is emitted)
     const uint32_t qslot = (uint32_t)wave * 32u + (uint32_t)m;
-    const WideTileI8<SP, QB> tile{s_a, a.queries8 + (size_t)(qbase + (qslot < nq ? qslot : 0u)) * qstride + (size_t)h * (size_t)(16 * J), J, wave, lane};
+    const WideTile<TileI8, SP, QB> tile{s_a, a.queries8 + (size_t)(qbase + (qslot < nq ? qslot : 0u)) * qstride + (size_t)h * (size_t)(16 * J), J, wave, lane};
     v4i st[SP];
     tile.stage_load(0, st);
     tile.stage_write(0, 0, st);
@@ -626,16 +576,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const uint8_t* nbase = fbase + exact_wide_wave_block(cn, B1, (uint32_t)wave) * block_bytes;
             const int cy = a.code_cy[cur * 32 + (uint64_t)m];
             const uint2 bi = a.blk[cur];
-            // register 4 g + c of lane half h of tile t belongs to query slot 32 t + 8 g + 4 h + c: the start values, LDS -> accumulator
             v16i acc[NQB];
-#pragma unroll
-            for (int t = 0; t < NQB; t++)
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const v4i t0 = *reinterpret_cast<const v4i*>(&s_init[32 * t + 8 * g + 4 * h]);
-#pragma unroll
-                    for (int e = 0; e < 4; e++) acc[t][4 * g + e] = t0[e];
-                }
+            static_for(std::make_integer_sequence<int, NQB>{}, [&](auto T) __attribute__((always_inline)) {
+                exact_i8_start<32 * decltype(T)::value>(acc[decltype(T)::value], s_init, 4 * h);
+            });
             for (int s = 0; s < S; s++) {
                 const bool lasts = s + 1 == S;
                 // the refill of ring slot jj: piece j + SP of this block (past J: J - 1 again, multiplied by a zero stage slot), or
@@ -655,35 +599,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             // (opaque per chunk, as in scan_all_wide_f16_kernel: nothing of the epilogue's addressing is hoisted out of the chunk loop)
             int h4 = 4 * h;
             asm volatile("" : "+v"(h4));
-            static_for(std::make_integer_sequence<int, NQB>{}, [&](auto TT) __attribute__((always_inline)) {
-                constexpr int qb = 32 * decltype(TT)::value;
-                const v16i& ac = acc[decltype(TT)::value];
-                static_for(std::make_integer_sequence<int, 2>{}, [&](auto H) __attribute__((always_inline)) {
-                    constexpr int r0 = decltype(H)::value * 8;
-                    // eight registers at a time: their largest value against the bound first (v_max3): most groups hold no candidate
-                    int mx = max(max(ac[r0], ac[r0 + 1]), ac[r0 + 2]);
-                    mx = max(max(mx, ac[r0 + 3]), ac[r0 + 4]);
-                    mx = max(max(mx, ac[r0 + 5]), ac[r0 + 6]);
-                    mx = max(mx, ac[r0 + 7]);
-                    if (__ballot(mx > hc) == 0) return;
-                    static_for(std::make_integer_sequence<int, 8>{}, [&](auto R) __attribute__((always_inline)) {
-                        constexpr int reg = r0 + decltype(R)::value;
-                        constexpr int q0 = qb + (reg & 3) + 8 * (reg >> 2);  // query slot of lane half 0; half 1: q0 + 4
-                        if (ac[reg] > hc) {
-                            const int sl = q0 + h4;
-                            const int cq = s_cx[sl], uq = s_u[sl], Tq = s_T[sl];
-                            // the contraction itself: acc = x.y - floor(u / 2) (L2) | x.y - u (IP)
-                            const int t = METRIC == METRIC_L2 ? 2 * (ac[reg] + (uq >> 1)) - cy : ac[reg] + uq + cy;
-                            const int dis = METRIC == METRIC_L2 ? cq - t : cq + t;
-                            const bool keep = (uint32_t)sl < nq && (METRIC == METRIC_L2 ? dis <= Tq : dis >= Tq);
-                            if (keep) {
-                                const uint32_t q = qbase + (uint32_t)sl;
-                                const uint32_t slot = atomicAdd(&a.cnt[q], 1u);  // (beyond cap only the counter moves)
-                                if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = make_uint2(pos, __float_as_uint((float)dis));
-                            }
-                        }
-                    });
-                });
+            static_for(std::make_integer_sequence<int, NQB>{}, [&](auto T) __attribute__((always_inline)) {
+                constexpr int t = decltype(T)::value;
+                exact_i8_emit<METRIC, 32 * t>(a, acc[t], s_cx, s_u, s_T, h4, qbase, nq, hc, cy, pos);
             });
         }
     };
@@ -962,30 +880,26 @@ void launch_scan_all_f16(const ExactScanF16Args& a, bool keep, hipStream_t s) {
     });
 }
 
-void launch_scan_all_wide_f16(const ExactScanF16Args& a, bool keep, hipStream_t s) {
+// the launch of a wide pass (Args: its argument struct; pick(metric, keep): its instantiation; lds: its dynamic LDS)
+template <class Args, class Pick> static void launch_exact_wide(const char* name, size_t lds, const Args& a, bool keep, hipStream_t s, Pick&& pick) {
     if (a.n == 0 || a.nblk == 0) return;
     if (a.d <= EXACT_NARROW_MAX_D || a.d > EXACT_WIDE_MAX_D || a.slab == 0 || (a.slab & (EXACT_WIDE_CHUNK - 1)) || (a.nblk & 1))
-        throw std::runtime_error("scan_all_wide_f16_kernel: shape not supported");
+        throw std::runtime_error(std::string(name) + ": shape not supported");
     const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + EXACT_WIDE_QUERIES - 1) / EXACT_WIDE_QUERIES)), block(256);
     with_metric_keep(a.metric, keep, [&](auto M, auto K) {
-        auto kern = scan_all_wide_f16_kernel<decltype(M)::value, decltype(K)::value>;
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXACT_WIDE_LDS);
-        if (e != hipSuccess) throw std::runtime_error(std::string("scan_all_wide_f16_kernel: cannot reserve LDS: ") + hipGetErrorString(e));
-        LAUNCH(kern, grid, block, EXACT_WIDE_LDS, s, a);
+        void (*kern)(Args) = pick(M, K);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) throw std::runtime_error(std::string(name) + ": cannot reserve LDS: " + hipGetErrorString(e));
+        LAUNCH(kern, grid, block, lds, s, a);
     });
 }
 
+void launch_scan_all_wide_f16(const ExactScanF16Args& a, bool keep, hipStream_t s) {
+    launch_exact_wide("scan_all_wide_f16_kernel", EXACT_WIDE_LDS, a, keep, s, [](auto M, auto K) { return scan_all_wide_f16_kernel<decltype(M)::value, decltype(K)::value>; });
+}
+
 void launch_scan_all_wide_i8(const ExactScanArgs& a, bool keep, hipStream_t s) {
-    if (a.n == 0 || a.nblk == 0) return;
-    if (a.d <= EXACT_NARROW_MAX_D || a.d > EXACT_WIDE_MAX_D || a.slab == 0 || (a.slab & (EXACT_WIDE_CHUNK - 1)) || (a.nblk & 1))
-        throw std::runtime_error("scan_all_wide_i8_kernel: shape not supported");
-    const dim3 grid((unsigned)((a.nblk + a.slab - 1) / a.slab), (unsigned)((a.n + EXACT_WIDE_QUERIES - 1) / EXACT_WIDE_QUERIES)), block(256);
-    with_metric_keep(a.metric, keep, [&](auto M, auto K) {
-        auto kern = scan_all_wide_i8_kernel<decltype(M)::value, decltype(K)::value>;
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXACT_WIDE_I8_LDS);
-        if (e != hipSuccess) throw std::runtime_error(std::string("scan_all_wide_i8_kernel: cannot reserve LDS: ") + hipGetErrorString(e));
-        LAUNCH(kern, grid, block, EXACT_WIDE_I8_LDS, s, a);
-    });
+    launch_exact_wide("scan_all_wide_i8_kernel", EXACT_WIDE_I8_LDS, a, keep, s, [](auto M, auto K) { return scan_all_wide_i8_kernel<decltype(M)::value, decltype(K)::value>; });
 }
 
 void launch_exact_rescore(const ExactRescoreArgs& a, hipStream_t s) {

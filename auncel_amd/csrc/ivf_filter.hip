@@ -640,7 +640,7 @@ template <int METRIC, bool HALF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_filter_wide_kernel(FilterScanArgs a) {
     extern __shared__ __align__(16) unsigned char wide_smem[];
     float* s_a = reinterpret_cast<float*>(wide_smem);  // [2 buffers][query block][piece of the stage][lane][4]
-    float* s_u = s_a + 2 * wide_stage_floats(FILTER_WIDE_QB, FILTER_WIDE_SP);
+    float* s_u = s_a + 2 * wide_stage_words(FILTER_WIDE_QB, FILTER_WIDE_SP);
     float* s_c = s_u + FILTER_WIDE_QUERIES;
     uint32_t* s_row = reinterpret_cast<uint32_t*>(s_c + FILTER_WIDE_QUERIES);
     uint32_t* s_q = s_row + FILTER_WIDE_QUERIES;
@@ -688,7 +688,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         // Straight-line code (mfma_tile.h): every wave runs the same loads, stages and barriers whatever its share of the item -- a
         // wave without a query block stages row 0, one without a block of the chunk recomputes the first and drops the result.
-        const WideTile<HALF, SP, QB> tile{s_a, a.xf + (size_t)qrow * qstride + (size_t)h * 4, J, wave, lane};
+        const WideTile<TileFloat<HALF>, SP, QB> tile{s_a, a.xf + (size_t)qrow * qstride + (size_t)h * 4, J, wave, lane};
         v4f st[SP];
         tile.stage_load(0, st);
         tile.stage_write(0, 0, st);
