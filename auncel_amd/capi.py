@@ -38,6 +38,7 @@ SYMBOLS = [
     "amd_ivf_search_selected", "amd_ivf_search_preassigned_selected", "amd_ivf_search_resident_selected",
     "amd_ivf_selector_combine", "amd_ivf_range_search_selected", "amd_ivf_range_search_preassigned_selected",
     "amd_ivf_submit_search_resident_selected",
+    "amd_ivf_search_selected_each", "amd_ivf_search_preassigned_selected_each", "amd_ivf_search_resident_selected_each",
     "amd_ivf_search_exact", "amd_ivf_search_exact_resident", "amd_ivf_last_exact", "amd_ivf_last_exact_detail",
     "amd_ivf_search_exact_selected", "amd_ivf_search_exact_resident_selected",
     "amd_ivf_range_search_exact", "amd_ivf_range_search_exact_resident", "amd_ivf_range_search_exact_selected", "amd_ivf_last_range_exact",
@@ -452,6 +453,49 @@ class Handle:
         I = np.empty((n, k), np.int64)
         _chk(lib().amd_ivf_search_resident_selected(self._h, selector._s, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k), C.c_size_t(nprobe),
                                                     coarse_mode, _f(D), _i(I)))
+        return D, I
+
+    # ---- ... with a selector per query: a list of Selector objects of this index and, per query, the position of its selector in it
+    @staticmethod
+    def _each(sels, sel_of, n):
+        """the table (an array of amd_ivf_selector_t*) and sel_of as uint32: one entry per query, as the ABI reads them"""
+        table = (C.c_void_p * max(len(sels), 1))(*[s._s.value if s is not None else None for s in sels])
+        sel_of = np.asarray(sel_of)
+        if sel_of.shape != (n,):
+            raise ValueError(f"sel_of wants one selector number per query: shape {sel_of.shape}, {n} queries")
+        if n and (sel_of.min() < 0 or sel_of.max() > 0xffffffff):
+            raise ValueError("sel_of holds a number that is not a uint32")
+        sel_of = np.ascontiguousarray(sel_of, dtype=np.uint32)
+        return table, C.c_size_t(len(sels)), sel_of, sel_of.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def search_selected_each(self, sels, sel_of, x, k, nprobe, coarse_mode=0):
+        """search_selected with a selector per query: row i is searched under sels[sel_of[i]] (amd_ivf_search_selected_each)"""
+        x = f32(x)
+        n = x.shape[0]
+        table, nsel, sel_of, so = self._each(sels, sel_of, n)
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_selected_each(self._h, table, nsel, so, C.c_size_t(n), _f(x), C.c_size_t(k), C.c_size_t(nprobe), coarse_mode,
+                                                _f(D), _i(I)))
+        return D, I
+
+    def search_preassigned_selected_each(self, sels, sel_of, x, k, keys, coarse_dis=None):
+        x, keys = f32(x), i64(keys)
+        n, nprobe = keys.shape
+        table, nsel, sel_of, so = self._each(sels, sel_of, n)
+        cd = f32(coarse_dis) if coarse_dis is not None else None
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_preassigned_selected_each(self._h, table, nsel, so, C.c_size_t(n), _f(x), C.c_size_t(k), C.c_size_t(nprobe),
+                                                            _i(keys), _f(cd), _f(D), _i(I)))
+        return D, I
+
+    def search_resident_selected_each(self, sels, sel_of, start, n, k, nprobe, coarse_mode=0):
+        table, nsel, sel_of, so = self._each(sels, sel_of, n)
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        _chk(lib().amd_ivf_search_resident_selected_each(self._h, table, nsel, so, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k),
+                                                         C.c_size_t(nprobe), coarse_mode, _f(D), _i(I)))
         return D, I
 
     def range_search_selected(self, selector, x, radius, nprobe, keys=None, coarse_mode=0):

@@ -28,6 +28,13 @@ struct IndexIVFFlat : IndexIVF {
     /// selector's parameters repeat: selector_passes counts the passes made, selected_info() describes the one that is kept.
     /// Fixed nprobe, the plain search only (not tune / training / time_tune, no max_codes); not for an IndexIVFFlatDedup.
     void search_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const IDSelector& sel) const;
+    /// ... with a selector per query (amd_ivf_search_selected_each): query i is searched under *sels[sel_of[i]], sel_of[i] <
+    /// sels.size(); row i is what the call above returns for query i under that selector.  One coarse ranking and one pass over the
+    /// lists per round serve the whole batch.  The same preconditions.  The device selectors come from the same cache: one whose
+    /// parameters and lists repeat -- from an earlier table or from a call that took it alone -- is not made again
+    /// (selector_passes), and selectors of equal parameters share one.  The cache keeps up to 64 selectors of tables.
+    void search_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const std::vector<const IDSelector*>& sels,
+                         const uint32_t* sel_of) const;
     mutable size_t selector_passes = 0;
     /// {entries looked at, entries kept, host-to-device bytes, device bytes held} of the kept selector (zeros: none)
     void selected_info(uint64_t out[4]) const;
@@ -55,12 +62,17 @@ struct IndexIVFFlat : IndexIVF {
     ~IndexIVFFlat() override;
 
    private:
-    amd_ivf_selector* device_selector(amd_ivf* g, const IDSelector& sel) const;
-    mutable amd_ivf_selector* sel_ = nullptr;  // the kept selector, and what it was made from
-    mutable size_t sel_version_ = 0;
-    mutable int sel_kind_ = -1;
-    mutable idx_t sel_a1_ = 0, sel_a2_ = 0;
-    mutable std::vector<int64_t> sel_ids_;
+    /// single: the call takes one selector (the one kept for such calls is replaced when `sel` is new); else one of a table's
+    amd_ivf_selector* device_selector(amd_ivf* g, const IDSelector& sel, bool single = true) const;
+    struct KeptSelector {  // a device selector and what it was made from
+        amd_ivf_selector* s = nullptr;
+        size_t version = 0;
+        int kind = -1;
+        idx_t a1 = 0, a2 = 0;
+        std::vector<int64_t> ids;
+    };
+    mutable std::vector<KeptSelector> kept_;   // every device selector that is alive: sel_, and those made for a table
+    mutable amd_ivf_selector* sel_ = nullptr;  // the one kept for the calls that take one selector (selected_info)
 };
 
 /// faiss::IndexIVFFlatDedup (Auncel/IndexIVFFlat.h:62-107): equal vectors are stored once; `instances` maps the id that

@@ -1276,7 +1276,7 @@ void IndexIVF::copy_subset_to(IndexIVF& other, int subset_type, idx_t a1, idx_t 
 
 // ------------------------------------------------------------------------------------- IndexIVFFlat::search_selected
 IndexIVFFlat::~IndexIVFFlat() {
-    if (sel_) amd_ivf_selector_destroy(sel_);  // (before ~IndexIVF destroys the engine it was made on)
+    for (KeptSelector& e : kept_) amd_ivf_selector_destroy(e.s);  // (before ~IndexIVF destroys the engine they were made on)
 }
 
 void IndexIVFFlat::selected_info(uint64_t out[4]) const {
@@ -1284,8 +1284,9 @@ void IndexIVFFlat::selected_info(uint64_t out[4]) const {
     if (sel_) AMD(amd_ivf_selector_info(sel_, out));
 }
 
-// the engine's selector for `sel`: the kept one while the lists and the selector's parameters repeat, else a new pass over the ids
-amd_ivf_selector* IndexIVFFlat::device_selector(amd_ivf* g, const IDSelector& sel) const {
+// the engine's selector for `sel`: a kept one while the lists and the selector's parameters repeat, else a new pass over the ids.
+// The calls that take one selector keep one (sel_: a new one replaces it); the selectors of a table stay beside it.
+amd_ivf_selector* IndexIVFFlat::device_selector(amd_ivf* g, const IDSelector& sel, bool single) const {
     int kind;
     idx_t a1 = 0, a2 = 0;
     std::vector<int64_t> ids;
@@ -1300,19 +1301,32 @@ amd_ivf_selector* IndexIVFFlat::device_selector(amd_ivf* g, const IDSelector& se
     } else {
         FAISS_THROW_MSG("a search under this kind of IDSelector is not implemented");
     }
-    const bool kept = sel_ && sel_version_ == invlists->version && sel_kind_ == kind && sel_a1_ == a1 && sel_a2_ == a2 && sel_ids_ == ids;
-    if (!kept) {
-        if (sel_) amd_ivf_selector_destroy(sel_);
-        sel_ = nullptr;
-        AMD(amd_ivf_selector_create(g, kind, (int64_t)a1, (int64_t)a2, ids.empty() ? nullptr : ids.data(), ids.size(), &sel_));
-        selector_passes++;
-        sel_version_ = invlists->version;
-        sel_kind_ = kind;
-        sel_a1_ = a1;
-        sel_a2_ = a2;
-        sel_ids_.swap(ids);
-    }
-    return sel_;
+    auto drop = [&](size_t i) {
+        if (kept_[i].s == sel_) sel_ = nullptr;
+        amd_ivf_selector_destroy(kept_[i].s);
+        kept_.erase(kept_.begin() + (long)i);
+    };
+    for (size_t i = kept_.size(); i-- > 0;)  // (the lists changed: the engine would refuse them as stale)
+        if (kept_[i].version != invlists->version) drop(i);
+    for (const KeptSelector& e : kept_)
+        if (e.kind == kind && e.a1 == a1 && e.a2 == a2 && e.ids == ids) {
+            if (single) sel_ = e.s;
+            return e.s;
+        }
+    if (single)
+        for (size_t i = kept_.size(); i-- > 0;)
+            if (kept_[i].s == sel_) drop(i);
+    KeptSelector e;
+    AMD(amd_ivf_selector_create(g, kind, (int64_t)a1, (int64_t)a2, ids.empty() ? nullptr : ids.data(), ids.size(), &e.s));
+    selector_passes++;
+    e.version = invlists->version;
+    e.kind = kind;
+    e.a1 = a1;
+    e.a2 = a2;
+    e.ids.swap(ids);
+    kept_.push_back(std::move(e));
+    if (single) sel_ = kept_.back().s;
+    return kept_.back().s;
 }
 
 void IndexIVFFlat::search_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const IDSelector& sel) const {
@@ -1321,6 +1335,29 @@ void IndexIVFFlat::search_selected(idx_t n, const float* x, idx_t k, float* dist
     FAISS_THROW_IF_NOT_MSG(max_codes == 0, "search_selected with max_codes is not implemented");
     amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
     AMD(amd_ivf_search_selected(g, device_selector(g, sel), (size_t)n, x, (size_t)k, nprobe, coarse_mode, distances, i64(labels)));
+}
+
+void IndexIVFFlat::search_selected(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const std::vector<const IDSelector*>& sels,
+                                   const uint32_t* sel_of) const {
+    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(this) == nullptr, "search_selected of an IndexIVFFlatDedup is not implemented");
+    FAISS_THROW_IF_NOT_MSG(!tune && !training && !(t && t->time_tune), "search_selected is the plain fixed-nprobe search only");
+    FAISS_THROW_IF_NOT_MSG(max_codes == 0, "search_selected with max_codes is not implemented");
+    FAISS_THROW_IF_NOT_MSG(sel_of != nullptr || n == 0, "search_selected: null sel_of");
+    for (const IDSelector* s : sels) FAISS_THROW_IF_NOT_MSG(s != nullptr, "search_selected: a null selector in the table");
+    amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
+    // (room for this table: the selectors of earlier tables go, the one kept for single-selector calls stays)
+    constexpr size_t KEPT_MAX = 64;
+    if (kept_.size() + sels.size() > KEPT_MAX + 1)
+        for (size_t i = kept_.size(); i-- > 0;)
+            if (kept_[i].s != sel_) {
+                amd_ivf_selector_destroy(kept_[i].s);
+                kept_.erase(kept_.begin() + (long)i);
+            }
+    std::vector<const amd_ivf_selector_t*> table;
+    for (const IDSelector* s : sels) table.push_back(device_selector(g, *s, false));
+    const uint32_t none = 0;
+    AMD(amd_ivf_search_selected_each(g, table.data(), table.size(), sel_of ? sel_of : &none, (size_t)n, x, (size_t)k, nprobe, coarse_mode, distances,
+                                     i64(labels)));
 }
 
 // ------------------------------------------------------------------------------------- IndexIVFFlat::search_exact

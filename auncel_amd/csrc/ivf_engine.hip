@@ -493,6 +493,10 @@ struct amd_ivf {
     DevBuf w_seg_begin;
     DevBuf w_log, w_log_cnt, w_amb, w_tie_flag;  // sorted-array selection: admission logs, ambiguity marks, tie_fix flags
     DevBuf w_qstat;     // per query: lists scanned, heap updates (what a query searched again takes out of the statistics)
+    // a search under a selector per query (amd_ivf_search_*_selected_each): the keep-word base of every selector of the call, then
+    // the selector number of every query -- one block, as the host packed it
+    DevBuf w_keep_each;
+    std::vector<uint64_t> keep_each_host;
     DevBuf w_redo_x;    // rows of the queries searched again with the reference's coarse tie order (adaptive_core)
     DevBuf w_log_snap, w_fin_round, w_fix_pos, w_fix_val, w_fix_ref;  // tie_fix_kernel: per-round log counts, heaps replayed so far
     hipStream_t fix_stream = nullptr;            // tie_fix_kernel runs here, under the next round (= bg_stream)
@@ -1281,6 +1285,12 @@ std::vector<uint32_t> pack_query_tiles(amd_ivf* h, const float* d_queries, const
 }
 
 // ------------------------------------------------------------------------------------ rounds
+// A selector per query: the device copies of the call's table (nsel keep-word bases) and of sel_of (a selector number per query slot)
+struct KeepEach {
+    const unsigned long long* const* keeps = nullptr;
+    const uint32_t* sel_of = nullptr;
+    uint32_t nsel = 0;
+};
 // What a search hands to run_rounds_device: the queries and their coarse ranking on the device, and what the rounds do with them.
 struct RoundSpec {
     int k = 0;
@@ -1324,6 +1334,9 @@ struct RoundSpec {
     // ivf_subset.hip's mask.  Every round then carries a mask -- a dense round's is the keep words themselves, a threshold round's
     // the scan's marks narrowed by them (keep_rows_kernel) -- and every selection is the masked one.
     const unsigned long long* keep = nullptr;
+    // ... under a selector per QUERY (amd_ivf_search_*_selected_each; keep stays null): the device table of the call's keep-word
+    // bases and the selector number of every query slot (keep_rows_each_kernel); everything behind the mask is the same
+    KeepEach each{};
 };
 
 static bool dbg_timing() {
@@ -2454,11 +2467,37 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
         ka.write = thr_mode ? 0 : 1;
         return ka;
     };
+    // ... under a selector per query (base.each): the same place, the same hints; the rows by query (qsel -> slot -> sel_of)
+    const bool each = base.each.keeps != nullptr;
+    const bool selected = base.keep || each;
+    auto keep_each_args = [&](bool thr_mode, const uint32_t* counts, size_t round) {
+        KeepEachArgs ka{};
+        ka.nq_dev = counts ? nullptr : dcnt + CNT_ACTIVE;
+        ka.nq = counts ? counts[CNT_ACTIVE] : 0;
+        const uint32_t seen = hint_of(round, CNT_SEGMENTS);
+        ka.nseg_hint = (uint32_t)std::min<size_t>(seg_cap, seen ? (size_t)seen + seen / 8 + 4 : n * std::min<size_t>(total_nprobe, 64));
+        ka.probes = std::max<uint32_t>(1, std::min<uint32_t>(pa.round_len, (uint32_t)total_nprobe));  // (the round at hand: plan_round)
+        ka.nlist = (uint32_t)nlist;
+        ka.nsel = base.each.nsel;
+        ka.qsel = h->w_qsel.as<uint32_t>();
+        ka.seg_count = h->w_pl_cnt.as<uint32_t>();
+        ka.seg_begin = h->w_seg_begin.as<uint32_t>();
+        ka.seg_list = h->w_seg_list.as<int32_t>();
+        ka.seg_off = h->w_seg_off.as<uint64_t>();
+        ka.list_off = I->d_list_off.as<uint64_t>();
+        ka.block_off = I->d_block_off.as<uint64_t>();
+        ka.keeps = base.each.keeps;
+        ka.sel_of = base.each.sel_of;
+        ka.mask = h->w_mask.as<unsigned long long>();
+        ka.write = thr_mode ? 0 : 1;
+        return ka;
+    };
     // ---- the scan of a planned round.  counts == nullptr: sizes on the device (chained); else the counters read back.
     auto enqueue_scan = [&](bool thr_mode, const uint32_t* counts, size_t round) {
         if (counts && counts[CNT_PAIRS] == 0) return;
         size_t t = h->timer.begin(thr_mode ? CAT_SCAN_THR : CAT_SCAN, s);
         const KeepArgs ka = base.keep ? keep_args(thr_mode, counts, round) : KeepArgs{};
+        const KeepEachArgs kea = each ? keep_each_args(thr_mode, counts, round) : KeepEachArgs{};
         if (base.bytes) {
             // byte codes: one launch of scan_mfma_kernel (no query packing: the A operand is gathered from the query matrix)
             MfmaScanArgs ma{};
@@ -2535,7 +2574,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
             ensure_aux(h, 3, 3);
             HIP_CHECK(hipEventRecord(h->ev_fork, s));
             HIP_CHECK(hipStreamWaitEvent(h->aux[3], h->ev_fork, 0));
-            launch_scan_filter(fa, h->aux[3], base.keep ? &ka : nullptr);  // (the keep bits: before the survivors are rescored)
+            launch_scan_filter(fa, h->aux[3], base.keep ? &ka : nullptr, each ? &kea : nullptr);  // (the keep bits: before the survivors are rescored)
             h->filter_launches++;
             HIP_CHECK(hipEventRecord(h->ev_join[3], h->aux[3]));
             HIP_CHECK(hipStreamWaitEvent(s, h->ev_join[3], 0));
@@ -2590,6 +2629,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
                 }
         }
         if (base.keep && !(filter_ok && thr_mode && !base.bytes)) launch_keep_rows(ka, s);
+        if (each && !(filter_ok && thr_mode && !base.bytes)) launch_keep_rows_each(kea, s);
         h->timer.end(t, s);
     };
 
@@ -2648,7 +2688,7 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
         ra.round_probes = 0;
         ra.id_offset = base.id_offset;
         ra.dist = h->w_dist.as<float>();
-        ra.mask = thr_mode || base.keep ? h->w_mask.as<unsigned long long>() : nullptr;
+        ra.mask = thr_mode || selected ? h->w_mask.as<unsigned long long>() : nullptr;
         ra.thr = no_thr ? nullptr : h->w_thr.as<float>();
         ra.seg_off = h->w_seg_off.as<uint64_t>();
         ra.seg_list = h->w_seg_list.as<int32_t>();
@@ -3020,7 +3060,8 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
 // round is cheaper than a second pass over the lists (5000 queries, 10M x 128, nprobe 8: 2.7 vs 2.1 M queries/s;
 // nprobe 32: 1.1 vs 1.3).
 void search_fixed_device(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, const int64_t* d_keys, float* D,
-                         int64_t* I, int store_pairs, size_t max_codes, const IntRange& qr, const unsigned long long* keep = nullptr) {
+                         int64_t* I, int store_pairs, size_t max_codes, const IntRange& qr, const unsigned long long* keep = nullptr,
+                         const KeepEach* each = nullptr) {
     CallScope call_scope(h);
     upload_lists(h);
     init_state(h, n, k, false);
@@ -3032,6 +3073,7 @@ void search_fixed_device(amd_ivf* h, const float* d_x, size_t n, size_t k, size_
     base.d_ckeys = d_keys;
     base.coarse_stride = (uint32_t)nprobe;
     base.keep = keep;
+    if (each) base.each = *each;
     base.fused = h->allow_fused && ix(h)->db_range.fusable_with(qr, h->metric);
     base.bytes = byte_queries(h, ix(h), d_x, n, qr);
     ix(h)->last_arith = base.bytes ? 2 : base.fused ? 1 : 0;
@@ -3053,12 +3095,12 @@ void search_fixed_device(amd_ivf* h, const float* d_x, size_t n, size_t k, size_
 }
 
 void search_full(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I, const IntRange& qr,
-                 const unsigned long long* keep = nullptr) {
+                 const unsigned long long* keep = nullptr, const KeepEach* each = nullptr) {
     h->w_cdis.ensure(n * nprobe * 4);
     h->w_ckeys.ensure(n * nprobe * 8);
     coarse_dev(h, d_x, n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
                h->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric));
-    search_fixed_device(h, d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, qr, keep);
+    search_fixed_device(h, d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, qr, keep, each);
 }
 
 }  // namespace
@@ -5701,6 +5743,36 @@ const unsigned long long* selector_words(amd_ivf* h, const amd_ivf_selector* s) 
                           "amd_ivf_update_lists, amd_ivf_remove_ids); make a new one");
     return s->keep.as<unsigned long long>();
 }
+
+// A selector per query (amd_ivf_search_*_selected_each).  The refusals, from host state alone (selector_args.h): nothing has reached
+// the device and nothing of D / I has been written when one of them is thrown.
+void check_selector_each(const char* what, amd_ivf* h, const amd_ivf_selector* const* sels, size_t nsel, const uint32_t* sel_of, size_t n, const float* x,
+                         bool x_needed, const float* D, const int64_t* I) {
+    std::string bad = selector_each_null_error(what, h != nullptr, sels != nullptr, sel_of != nullptr, x != nullptr || !x_needed, D != nullptr, I != nullptr,
+                                               nsel, n);
+    if (!bad.empty()) throw EngineError(bad);
+    if (nsel >> 32) throw EngineError(std::string(what) + ": too many selectors");
+    std::vector<SelectorOperand> ops(nsel);
+    for (size_t j = 0; j < nsel; j++) ops[j] = sels[j] ? SelectorOperand{sels[j]->index, sels[j]->gen} : SelectorOperand{nullptr, 0};
+    bad = selector_each_error(what, ops.data(), nsel, sel_of, n, ix(h), ix(h)->layout_gen.load());
+    if (!bad.empty()) throw EngineError(bad);
+}
+// The call's table on the device: nsel keep-word bases, then sel_of, packed on the host and sent as one block with the call's other
+// small inputs (h2d_small).  The host copy lives in the handle: a block too large for the staging is read by the copy itself.
+KeepEach stage_selector_each(amd_ivf* h, const amd_ivf_selector* const* sels, size_t nsel, const uint32_t* sel_of, size_t n) {
+    const size_t words = nsel + (n + 1) / 2;
+    h->keep_each_host.assign(words, 0);
+    for (size_t j = 0; j < nsel; j++) h->keep_each_host[j] = (uint64_t) reinterpret_cast<uintptr_t>(sels[j]->keep.as<unsigned long long>());
+    memcpy(h->keep_each_host.data() + nsel, sel_of, n * 4);
+    h->w_keep_each.ensure(words * 8);
+    h2d_small(h, h->w_keep_each.p, h->keep_each_host.data(), words * 8, h->stream);
+    flush_h2d(h, h->stream);
+    KeepEach e;
+    e.keeps = h->w_keep_each.as<const unsigned long long*>();
+    e.sel_of = reinterpret_cast<const uint32_t*>(h->w_keep_each.as<uint64_t>() + nsel);
+    e.nsel = (uint32_t)nsel;
+    return e;
+}
 }  // namespace
 
 extern "C" {
@@ -5750,6 +5822,59 @@ int amd_ivf_search_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, 
     WallClock wc(h->stream);
     reset_scan_counters(h);
     search_full(h, q.d_x, n, k, nprobe, coarse_mode, D, I, q.range, keep);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+// The three calls above with a selector per query: the same bodies, the table and sel_of in place of the one selector's words
+int amd_ivf_search_selected_each(amd_ivf_t* h, const amd_ivf_selector_t* const* sels, size_t nsel, const uint32_t* sel_of, size_t n, const float* x,
+                                 size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I) {
+    API_BEGIN
+    check_selector_each("search_selected_each", h, sels, nsel, sel_of, n, x, n > 0, D, I);
+    use_device(h);
+    if (n == 0 || k == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const QueryRows q = host_rows(h, x, n);
+    const KeepEach each = stage_selector_each(h, sels, nsel, sel_of, n);
+    search_full(h, q.d_x, n, k, nprobe, coarse_mode, D, I, q.range, nullptr, &each);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_preassigned_selected_each(amd_ivf_t* h, const amd_ivf_selector_t* const* sels, size_t nsel, const uint32_t* sel_of, size_t n,
+                                             const float* x, size_t k, size_t nprobe, const int64_t* keys, const float* coarse_dis, float* D,
+                                             int64_t* I) {
+    API_BEGIN
+    (void)coarse_dis;  // (as in amd_ivf_search_preassigned)
+    check_selector_each("search_preassigned_selected_each", h, sels, nsel, sel_of, n, x, n > 0, D, I);
+    use_device(h);
+    if (n == 0 || k == 0) return 0;
+    if (!keys) throw EngineError("keys are required");
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const QueryRows q = host_rows(h, x, n);
+    const KeepEach each = stage_selector_each(h, sels, nsel, sel_of, n);
+    h->w_ckeys.ensure(n * nprobe * 8);
+    HIP_CHECK(hipMemcpyAsync(h->w_ckeys.p, keys, n * nprobe * 8, hipMemcpyHostToDevice, h->stream));
+    search_fixed_device(h, q.d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), D, I, 0, 0, q.range, nullptr, &each);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_resident_selected_each(amd_ivf_t* h, const amd_ivf_selector_t* const* sels, size_t nsel, const uint32_t* sel_of, size_t start,
+                                          size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I) {
+    API_BEGIN
+    check_selector_each("search_resident_selected_each", h, sels, nsel, sel_of, n, nullptr, false, D, I);
+    const std::string bad = selector_each_range_error("search_resident_selected_each", start, n, resident_owner(h)->n_resident);
+    if (!bad.empty()) throw EngineError(bad);
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    if (n == 0 || k == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const KeepEach each = stage_selector_each(h, sels, nsel, sel_of, n);
+    search_full(h, q.d_x, n, k, nprobe, coarse_mode, D, I, q.range, nullptr, &each);
     finish_timing(h, wc.stop());
     API_END
 }

@@ -751,15 +751,16 @@ uint32_t filter_item_vectors(int d) {
     return filter_steps(d) > 16 && !filter_narrow() ? FILTER_WIDE_VECTORS : mfma_chunk();
 }
 
-void launch_scan_filter(const FilterScanArgs& a, hipStream_t s, const KeepArgs* keep) {
+void launch_scan_filter(const FilterScanArgs& a, hipStream_t s, const KeepArgs* keep, const KeepEachArgs* keep_each) {
     if (a.nitems == 0 && !a.dev_nitems) return;
-    // the survivors' exact distances: all of them, or (keep) those of the selector's members
+    // the survivors' exact distances: all of them, or (keep / keep_each) those of the selector's members
     auto rescore = [&](auto resc, auto resc_keep) {
-        if (!keep) {
+        if (!keep && !keep_each) {
             LAUNCH(resc, dim3(resident_grid(4)), dim3(256), 0, s, a);
             return;
         }
-        launch_keep_rows(*keep, s);
+        if (keep) launch_keep_rows(*keep, s);
+        else launch_keep_rows_each(*keep_each, s);
         LAUNCH(resc_keep, dim3(resident_grid(4)), dim3(256), 0, s, a);
     };
     const unsigned nwg = (a.nitems + 3) / 4;

@@ -207,7 +207,9 @@ struct FilterParams {
 struct KeepArgs;
 // filter + rescoring, two launches; keep (a selected search, ivf_selector.hip): the keep bits are brought into the round's mask
 // words between the two, and the rescoring leaves out the survivors whose bit went
-void launch_scan_filter(const FilterScanArgs& a, hipStream_t s, const KeepArgs* keep = nullptr);
+// (keep_each: the same with a selector per query, keep_rows_each_kernel; at most one of the two is given)
+struct KeepEachArgs;
+void launch_scan_filter(const FilterScanArgs& a, hipStream_t s, const KeepArgs* keep = nullptr, const KeepEachArgs* keep_each = nullptr);
 // pieces of 16 dimensions per vector in the fp16 fragment order: the step counts the one-wave kernel is built for (4, 6, 8) or an
 // even count beyond 128 dimensions
 inline __host__ __device__ uint32_t filter_steps16(int d) {
@@ -751,6 +753,30 @@ struct KeepArgs {
     int write;
 };
 void launch_keep_rows(const KeepArgs& a, hipStream_t s);
+// ... with a selector per QUERY (amd_ivf_search_*_selected_each): the keep words of a row are those of its query's selector,
+// keeps[sel_of[slot]].  A round's rows of one query are consecutive (seg_begin / seg_count, by query slot, as the planner left them);
+// launch position p < the round's active queries stands for slot qsel[p] -- the table the selection kernels go through to the
+// query's row of D / I -- and sel_of is indexed by that slot, which is the caller's query number.
+struct KeepEachArgs {
+    const uint32_t* nq_dev;    // active queries of the round (device count), or null: nq
+    uint32_t nq;
+    uint32_t nseg_hint;        // rows expected: sizes the grid
+    uint32_t probes;           // P: waves dealt to a query, the round's probe count (a query with more rows takes several trips)
+    uint32_t nlist;
+    uint32_t nsel;
+    const uint32_t* qsel;      // [active] query slot of each launch position
+    const uint32_t* seg_count; // by slot: rows this round
+    const uint32_t* seg_begin; // by slot: first row
+    const int32_t* seg_list;
+    const uint64_t* seg_off;
+    const uint64_t* list_off;
+    const uint64_t* block_off;
+    const unsigned long long* const* keeps;  // [nsel] keep-word base of every selector of the call (device table)
+    const uint32_t* sel_of;    // by slot
+    unsigned long long* mask;
+    int write;
+};
+void launch_keep_rows_each(const KeepEachArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------- exact search over the whole index (ivf_exact.hip)
 // The list pass of amd_ivf_search_exact: every query against every 32-vector block of the byte fragments (d <= 128; launch_scan_all_wide_i8: up to 1024), candidates at or

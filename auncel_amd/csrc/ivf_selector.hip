@@ -70,6 +70,44 @@ template <bool WRITE> __global__ __launch_bounds__(256) void keep_rows_kernel(Ke
     }
 }
 
+// keep_rows_kernel with a selector per query (amd_ivf_search_*_selected_each).  The keep-word base of a row comes from the row's
+// query, and a round's rows of one query are consecutive, so no wave searches for its query: wave w stands for launch position
+// w / P and the query's row j = w % P (P = the round's probe count; a query that was given more rows -- a run of equal coarse
+// distances taken whole -- walks them P apart), idle when the query has fewer.  Position -> query: qsel, the table the selection
+// kernels go through to reach a query's row of D / I.  qsel[p] is the query's SLOT, which is its number in the caller's arrays --
+// a budget cut defers queries to a later pass and later rounds compact the unfinished ones, so position p of a round is not query p
+// -- and seg_count / seg_begin / sel_of are all indexed by that slot.  Two wave-uniform loads per row (selector number, base), then
+// the 8 bytes in and 8 out per lane and word of keep_rows_kernel.  No LDS, no atomics, no barrier.
+template <bool WRITE> __global__ __launch_bounds__(256) void keep_rows_each_kernel(KeepEachArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t nq = a.nq_dev ? *a.nq_dev : a.nq;
+    const uint32_t P = a.probes;
+    const unsigned long long total = (unsigned long long)nq * P, stride = (unsigned long long)gridDim.x * 4u;
+    for (unsigned long long w = (unsigned long long)blockIdx.x * 4u + wave; w < total; w += stride) {
+        const uint32_t slot = a.qsel[w / P];
+        const uint32_t cnt = a.seg_count[slot], begin = a.seg_begin[slot];
+        uint32_t j = (uint32_t)(w % P);
+        if (j >= cnt) continue;
+        const uint32_t sel = a.sel_of[slot];
+        if (sel >= a.nsel) continue;  // (refused on the host: never reached)
+        const unsigned long long* keep = a.keeps[sel];
+        for (; j < cnt; j += P) {
+            const uint32_t r = begin + j;
+            const int key = a.seg_list[r];
+            if (key < 0 || (uint32_t)key >= a.nlist) continue;  // (an absent probe: the row is empty)
+            const uint32_t n = (uint32_t)(a.list_off[key + 1] - a.list_off[key]);
+            const uint32_t words = (n + 63u) >> 6;
+            const unsigned long long* kw = keep + (a.block_off[key] >> 1);
+            unsigned long long* mw = a.mask + (a.seg_off[r] >> 6);
+            for (uint32_t i = (uint32_t)lane; i < words; i += 64u) {
+                const unsigned long long k = kw[i];
+                mw[i] = WRITE ? k : (__builtin_nontemporal_load(mw + i) & k);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 void launch_selector_list_kept(const uint32_t* count, const uint64_t* block_off, uint32_t nlist, uint32_t* kept, hipStream_t s) {
@@ -88,6 +126,16 @@ void launch_keep_rows(const KeepArgs& a, hipStream_t s) {
     const uint32_t grid = std::min<uint32_t>((want + 3u) / 4u, 8192u);
     if (a.write) LAUNCH(keep_rows_kernel<true>, dim3(grid), dim3(256), 0, s, a);
     else LAUNCH(keep_rows_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+}
+
+// (the grid from the same hints: a wave per expected row, which is what nq x P comes to when every query takes P rows)
+void launch_keep_rows_each(const KeepEachArgs& a, hipStream_t s) {
+    if (a.probes == 0 || a.nsel == 0) throw std::runtime_error("keep_rows_each: no probes or no selectors");
+    const unsigned long long want = a.nq_dev ? a.nseg_hint : (unsigned long long)a.nq * a.probes;
+    if (want == 0) return;
+    const uint32_t grid = (uint32_t)std::min<unsigned long long>((want + 3u) / 4u, 8192u);
+    if (a.write) LAUNCH(keep_rows_each_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    else LAUNCH(keep_rows_each_kernel<false>, dim3(grid), dim3(256), 0, s, a);
 }
 
 }  // namespace amdivf

@@ -3,7 +3,8 @@
 // sorted ids of an ID_BATCH.  Plain C++, nothing of the device in it: both callers share it, and it builds on its own
 // (tests/cpp/selector_args_main.cpp runs it under the address and undefined-behaviour sanitizers).  So are the operand checks of
 // amd_ivf_selector_combine and the one rule that says which bits of a keep word stand for entries (selector_valid_word: the combine
-// kernel and tests/cpp/selector_combine_main.cpp read the same definition).
+// kernel and tests/cpp/selector_combine_main.cpp read the same definition), and the checks of a search under a selector per query
+// (amd_ivf_search_*_selected_each: selector_each_*_error, tests/cpp/selector_each_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -79,6 +80,42 @@ inline std::string selector_combine_error(int op, const SelectorOperand* a, cons
     if (a->gen != index_gen || (b && b->gen != index_gen))
         return w + "an operand is stale: the index's lists were given or changed after it was made; make a new one";
     if (tickets) return w + "tickets are still out: wait for them before making a selector";
+    return std::string();
+}
+
+// ---- amd_ivf_search_*_selected_each: a table of selectors and one index into it per query
+// What the caller passed at all: read before anything behind a pointer is.  empty: go on to selector_each_error.
+inline std::string selector_each_null_error(const char* what, bool have_h, bool have_sels, bool have_sel_of, bool have_x, bool have_D, bool have_I,
+                                            size_t nsel, size_t n) {
+    const std::string w = std::string(what) + ": ";
+    if (!have_h || !have_sels || !have_sel_of || !have_D || !have_I) return w + "null argument";
+    if (!have_x && n > 0) return w + "null queries";
+    if (nsel == 0 && n > 0) return w + "no selectors (nsel == 0) for " + std::to_string(n) + " queries";
+    return std::string();
+}
+// The table and the indexes.  ops[j]: what the checks read of sels[j] (index == nullptr: the entry is null); index / index_gen: the
+// searching handle's index and its layout_gen as it is now.  Every entry of the table is checked, used by a query or not.
+inline std::string selector_each_error(const char* what, const SelectorOperand* ops, size_t nsel, const uint32_t* sel_of, size_t n, const void* index,
+                                       uint64_t index_gen) {
+    const std::string w = std::string(what) + ": ";
+    for (size_t j = 0; j < nsel; j++) {
+        const std::string at = "selector " + std::to_string(j) + " of the table ";
+        if (!ops[j].index) return w + at + "is null";
+        if (ops[j].index != index) return w + at + "was made on another index";
+        if (ops[j].gen != index_gen)
+            return w + at + "is stale: the index's lists were given or changed after it was made (amd_ivf_set_lists, amd_ivf_add, "
+                            "amd_ivf_update_lists, amd_ivf_remove_ids); make a new one";
+    }
+    for (size_t i = 0; i < n; i++)
+        if ((size_t)sel_of[i] >= nsel)
+            return w + "sel_of[" + std::to_string(i) + "] = " + std::to_string(sel_of[i]) + " is not below nsel = " + std::to_string(nsel);
+    return std::string();
+}
+// resident queries [start, start + n) of n_resident: a range that wraps is refused as such, not as whatever start + n comes to
+inline std::string selector_each_range_error(const char* what, size_t start, size_t n, size_t n_resident) {
+    const std::string w = std::string(what) + ": ";
+    if (start + n < start) return w + "the resident query range wraps";
+    if (start + n > n_resident) return w + "resident query range out of bounds";
     return std::string();
 }
 

@@ -154,15 +154,33 @@ int amd_ivf_selector_combine(int op, const amd_ivf_selector_t* a, const amd_ivf_
  * amd_ivf_stats, nheap_updates is the subset's (the admissions are the same sequence); ndis counts the entries of the probed lists
  * AS h HOLDS THEM, members or not: every one of them is scanned.
  * Fixed nprobe or a radius (below), every list (amd_ivf_search_exact_selected, further down), ids.  Not offered under a selector: the adaptive rule (its traces are trained on the whole
- * index), the scanner calls, store_pairs / max_codes, tickets of any search but amd_ivf_search_resident_selected, and one selector
- * per QUERY -- there is no entry point that takes a selector for any of them, so none can return an unfiltered answer.  -2 for a
- * null h / s, a selector of another index, a stale selector. */
+ * index), the scanner calls, store_pairs / max_codes, and tickets of any search but amd_ivf_search_resident_selected -- there is no
+ * entry point that takes a selector for any of them, so none can return an unfiltered answer.  One selector per QUERY: the _each
+ * calls below (fixed nprobe only).  -2 for a null h / s, a selector of another index, a stale selector. */
 int amd_ivf_search_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe, int coarse_mode,
                             float* D, int64_t* I);
 int amd_ivf_search_preassigned_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe,
                                         const int64_t* keys, const float* coarse_dis, float* D, int64_t* I);
 int amd_ivf_search_resident_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t k, size_t nprobe,
                                      int coarse_mode, float* D, int64_t* I);
+/* The three calls above with a selector per QUERY: sels is a table of nsel selectors of h's index, sel_of[i] < nsel names the one
+ * query i of the call is searched under (_resident: query start + i).  Row i of (D, I) is, bit for bit, row i of what the call above
+ * of the same kind returns for the same queries under sels[sel_of[i]]; nsel == 1 gives the bits of that call.  The same selector may
+ * stand in sels more than once, and a selector need not be used by any query; a query without a selector is one under a selector that
+ * keeps everything.  One coarse ranking, one plan and one scan per round serve the whole batch: a list is fetched once for all the
+ * queries that probe it, whichever selectors they carry (keep_rows_each_kernel).  In amd_ivf_stats nq, nlist and ndis
+ * are the single-selector call's over the whole batch (ndis over h's lists), nheap_updates the sum of every query's admissions under
+ * its own selector.  Synchronous; the selectors' ticket counts are not involved.
+ * -2 before anything reaches the device, D and I untouched: a null h, sels, sel_of, D or I; a null x with n > 0; nsel == 0 with
+ * n > 0; a null entry of sels, one of another index or a stale one (the message says which position); sel_of[i] >= nsel (the
+ * message says which i); a resident range that wraps or ends behind the resident queries.  n == 0 returns 0 without a launch. */
+int amd_ivf_search_selected_each(amd_ivf_t* h, const amd_ivf_selector_t* const* sels, size_t nsel, const uint32_t* sel_of, size_t n,
+                                 const float* x, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I);
+int amd_ivf_search_preassigned_selected_each(amd_ivf_t* h, const amd_ivf_selector_t* const* sels, size_t nsel, const uint32_t* sel_of,
+                                             size_t n, const float* x, size_t k, size_t nprobe, const int64_t* keys,
+                                             const float* coarse_dis, float* D, int64_t* I);
+int amd_ivf_search_resident_selected_each(amd_ivf_t* h, const amd_ivf_selector_t* const* sels, size_t nsel, const uint32_t* sel_of,
+                                          size_t start, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I);
 /* amd_ivf_range_search / _range_search_preassigned over the members only; the results are fetched with amd_ivf_range_results.  lims,
  * labels and distances are, bit for bit and in the same order, what the same call returns on amd_ivf_subset(h, the same selector).
  * ndis as above: the probed lists' entries as h holds them.  -2 as above, before anything is read. */
