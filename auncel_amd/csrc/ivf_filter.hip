@@ -25,6 +25,11 @@
 //   =>  |approx - r| <= (1.5 d + 20) u S.  The kernel uses C = (2 d + 32) u (a quarter more, and the rounding of the test
 //   itself) and keeps iff (1 - C)(xn + yn) - 2 p < thr.  Inner product: |p - r| <= 2 d u |x||y|; kept iff p + C |x||y| > thr.
 //
+//   Range: the derivation assumes fp32 arithmetic without overflow and with relative rounding errors.  The norms say whether that
+//   holds (filter_bound_u): squared norms in [2^-96, 2^126) under L2, norms in [2^-48, 2^63) under the inner product, or zero.  A
+//   query or a row outside it -- an overflowing norm, a NaN or infinite element, magnitudes whose products may leave the normal
+//   range -- is not filtered: the query keeps every candidate, the row is kept by every query, and the survivors are rescored.
+//
 // The fp16 form (HALF: round 4).  The filter only has to be *safe*, so its operands need not be the fp32 values: lists and
 // queries are also kept as fp16, scaled by powers of two s_y, s_x that bring their largest magnitudes into [2^14, 2^15) (no
 // overflow), 16 dimensions per piece in the operand order of v_mfma_f32_32x32x16_f16.  An element that lands below 2^-14 is
@@ -374,6 +379,25 @@ __device__ __forceinline__ void surv_retire(const FilterScanArgs& a, SurvChunk& 
     sc.left = 0;
 }
 
+// The right side u of a query's keep test (kept iff t > u).  L2: kept iff 2 p - (1 - C) yn > (1 - C) xn - thr; inner product: kept iff
+// p + C |x||y| > thr.  A NaN threshold: nothing passes (+inf).  The bound is derived for fp32 arithmetic that neither overflows nor
+// underflows (head comment), and the norms alone say whether it can: every partial sum of p is at most sum |x_i y_i| <=
+// (|x|^2 + |y|^2) / 2 <= |x||y|, so with both squared norms below 2^126 (L2), both norms below 2^63 (inner product), nothing on the
+// way to t overflows; a NaN or infinite element makes its row's norm a NaN or an infinity.  At the small end products may leave the
+// normal range (an absolute error of d 2^-126 at the worst, where the matrix cores flush, against a slack of about d 2^-25 S: S >=
+// 2^-96 covers it; under the inner product the slack is d 2^-24 |x||y|: both norms at or above 2^-48); a query of zeros has exact
+// products and stays filtered.  A query outside the range is marked by u = -inf and keeps every candidate; a row outside it is kept by
+// every query (filter_verdicts) -- slow, never wrong.
+constexpr float FILTER_TINY_L2 = 0x1p-96f, FILTER_TINY_IP = 0x1p-48f, FILTER_HUGE_L2 = 0x1p126f, FILTER_HUGE_IP = 0x1p63f;
+template <int METRIC> __device__ __forceinline__ bool filter_norm_outside(float n) {
+    return !(n < (METRIC == METRIC_L2 ? FILTER_HUGE_L2 : FILTER_HUGE_IP)) || (n > 0.f && n < (METRIC == METRIC_L2 ? FILTER_TINY_L2 : FILTER_TINY_IP));
+}
+template <int METRIC> __device__ __forceinline__ float filter_bound_u(float C, float xn, float thr) {
+    if (!(thr == thr)) return __builtin_inff();
+    if (filter_norm_outside<METRIC>(xn)) return -__builtin_inff();
+    return METRIC == METRIC_L2 ? (1.f - C) * xn - thr : thr;
+}
+
 // ---- verdicts of block i of an item against its query block qb, whose 32 x 32 dot products are in acc; per-query operands
 // of the item's queries in LDS tables (u, c, row position, query row: entry qb * 32 + query of the block); yn = this lane's
 // vector's |y|^2 (L2) / |y| (IP), loaded by the caller ahead of the block's MFMAs
@@ -401,14 +425,37 @@ __device__ __forceinline__ void filter_verdicts(const FilterScanArgs& a, const S
     int word = 0;  // lane q (< 32) collects the 32-candidate mask word of query q of the block
     unsigned long long kept[16];
     uint32_t total = 0;
+    // Outside the bound's range (filter_bound_u) a test value says nothing about the reference's, which may be finite: a row
+    // outside it is kept by every query, a query outside it (u = -inf) keeps every row, and the survivors are rescored.  Both are
+    // wave-uniform questions with the answer "no" on ordinary data, whose loop is the test alone.
+    const unsigned long long ybad = __ballot(filter_norm_outside<METRIC>(yn)) & vmask;
+    const uint32_t qbad = (uint32_t)__ballot(s_u[qb * 32 + m] == -__builtin_inff());
+    if (__builtin_expect(ybad == 0 && qbad == 0, 1)) {
 #pragma unroll
-    for (int reg = 0; reg < 16; reg++) {
-        const float p = HALF ? ps * acc[reg] : acc[reg];  // (a power of two: exact)
-        const float t = METRIC == METRIC_L2 ? fmaf(2.f, p, -c1yn) : fmaf(cr[reg], yn, p);
-        // (keep-all leaves out what nothing can pass: an absent query slot, a NaN threshold -- their u is +inf)
-        const bool keep = HALF ? ((C < 0.f) & (ur[reg] < __builtin_inff())) | (t > ur[reg]) : t > ur[reg];
-        kept[reg] = __ballot(keep) & vmask;
-        total += (uint32_t)__builtin_popcountll(kept[reg]);
+        for (int reg = 0; reg < 16; reg++) {
+            const float p = HALF ? ps * acc[reg] : acc[reg];  // (a power of two: exact)
+            const float t = METRIC == METRIC_L2 ? fmaf(2.f, p, -c1yn) : fmaf(cr[reg], yn, p);
+            // (keep-all leaves out what nothing can pass: an absent query slot, a NaN threshold -- their u is +inf)
+            const bool keep = HALF ? ((C < 0.f) & (ur[reg] < __builtin_inff())) | (t > ur[reg]) : t > ur[reg];
+            kept[reg] = __ballot(keep) & vmask;
+            total += (uint32_t)__builtin_popcountll(kept[reg]);
+        }
+    } else {
+        // (t may be anything here, a NaN included; the queries that may keep at all -- present, threshold not a NaN: u < +inf -- as
+        // a scalar mask, so that nothing reaches an absent slot's row)
+        const uint32_t qvalid = (uint32_t)__ballot(s_u[qb * 32 + m] < __builtin_inff());
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            const float p = HALF ? ps * acc[reg] : acc[reg];
+            const float t = METRIC == METRIC_L2 ? fmaf(2.f, p, -c1yn) : fmaf(cr[reg], yn, p);
+            const bool keep = (HALF & (C < 0.f)) | (t > ur[reg]);
+            const int q0 = (reg & 3) + 8 * (reg >> 2);  // query of lane half 0; half 1: q0 + 4
+            auto halves = [&](uint32_t bits) {
+                return (((bits >> q0) & 1u) ? 0xffffffffull : 0ull) | (((bits >> (q0 + 4)) & 1u) ? 0xffffffff00000000ull : 0ull);
+            };
+            kept[reg] = (__ballot(keep) | ybad | halves(qbad)) & vmask & halves(qvalid);
+            total += (uint32_t)__builtin_popcountll(kept[reg]);
+        }
     }
     static_for(std::make_integer_sequence<int, 16>{}, [&](auto R) {
         constexpr int reg = decltype(R)::value;
@@ -482,19 +529,13 @@ template <int METRIC, int NJ, bool HALF> __global__ __launch_bounds__(256) void 
         const bool qok = (uint32_t)m < it.npair;
         uint32_t qrow = 0;
         unsigned long long row = 0;
-        float u = __builtin_inff(), cq = 0.f;  // kept iff t > u: nothing passes for an absent query
+        float u = __builtin_inff(), cq = 0.f;  // +inf: nothing passes for an absent query (filter_verdicts: qvalid)
         if (qok) {
             qrow = a.pair_query[it.pair_begin + m];
             row = a.pair_out[it.pair_begin + m] + it.vec_off;
             const float thr = a.thr[qrow], xn = a.xn[qrow];
-            if (METRIC == METRIC_L2) {
-                u = (1.f - C) * xn - thr;  // kept iff 2 p - (1 - C) yn > (1 - C) xn - thr   (NaN thr: nothing passes)
-                if (!(thr == thr)) u = __builtin_inff();
-            } else {
-                u = thr;                   // kept iff p + C |x||y| > thr
-                if (!(thr == thr)) u = __builtin_inff();
-                cq = C * xn;
-            }
+            u = filter_bound_u<METRIC>(C, xn, thr);
+            if (METRIC != METRIC_L2) cq = C * xn;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the previous item's reads of this wave's LDS rows are done
         __builtin_amdgcn_wave_barrier();
@@ -665,19 +706,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const bool qok = (uint32_t)(wave * 32 + m) < it.npair;
         uint32_t qrow = 0;
         unsigned long long row = 0;
-        float u = __builtin_inff(), cq = 0.f;  // kept iff t > u: nothing passes for an absent query
+        float u = __builtin_inff(), cq = 0.f;  // +inf: nothing passes for an absent query (filter_verdicts: qvalid)
         if (qok) {
             qrow = a.pair_query[it.pair_begin + wave * 32 + m];
             row = a.pair_out[it.pair_begin + wave * 32 + m] + it.vec_off;
             const float thr = a.thr[qrow], xn = a.xn[qrow];
-            if (METRIC == METRIC_L2) {
-                u = (1.f - C) * xn - thr;
-                if (!(thr == thr)) u = __builtin_inff();
-            } else {
-                u = thr;
-                if (!(thr == thr)) u = __builtin_inff();
-                cq = C * xn;
-            }
+            u = filter_bound_u<METRIC>(C, xn, thr);
+            if (METRIC != METRIC_L2) cq = C * xn;
         }
         lds_barrier();  // the previous item's readers of the LDS tables and stages are done
         if (h == 0) {

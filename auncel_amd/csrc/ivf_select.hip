@@ -1592,7 +1592,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MASKED ? 4 
         // taken here and the block goes through the one-by-one admission like any other.
         bool bad = false;
 #pragma unroll
-        for (int c = 0; c < 4; c++) bad = bad || (64u * c + lane < m && okey<IsMax>(xs[c]) >= SKEY_SENT);
+        // (a NaN by its float: the key orders one of either sign as a number -- a positive NaN as the best inner product)
+        for (int c = 0; c < 4; c++) bad = bad || (64u * c + lane < m && (okey<IsMax>(xs[c]) >= SKEY_SENT || xs[c] != xs[c]));
         if (__ballot(bad) != 0) return 0u;
 #pragma unroll
         for (int c = 0; c < 4; c++) {

@@ -179,7 +179,54 @@ def io_sift():
     return c
 
 
-CASES = {f.__name__: f for f in [io_ragged, io_sift, fixed_sift_l2, fixed_gauss_l2_d96, fixed_deep_ip_d96, fixed_gist_l2_d960,
+def _worlds():
+    import os
+    import sys
+    tests = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    import extreme_range_cases
+    return extreme_range_cases
+
+
+def _extreme(metric, cen, xb, xq, radius):
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+    return dict(kind="fixed", d=24, nlist=4, nprobe=4, metric=metric, centroids=f(cen), xb=f(xb), xq=f(xq), ks=np.array([10, 1], dtype=np.int64),
+                nshard=0, max_codes=0, radius=np.array([radius], dtype=np.float32), dedup=0)
+
+
+def extreme_l2_d24():
+    # the ends of the fp32 range under L2 (tests/extreme_range_cases.py at d = 24): norms that overflow, a NaN / +inf / -inf element,
+    # all-zero and non-finite queries, subnormal distances (a reference build that flushed them would return zeros).  19 rows: the
+    # reference assigns fewer than 20 through its exact path.  The radius is a subnormal.
+    X = _worlds()
+    big, sub, odd = X.world("l2_norm_overflow", 24), X.world("subnormal", 24), X.world("nonfinite_l2", 24)
+    kinds = {k: r for r, k in sorted(odd["planted"].items(), reverse=True)}
+    rows = np.nonzero(big["assign"] < 3)[0][:9]
+    xb = np.concatenate([big["xb"][rows], odd["xb"][[kinds["nan"], kinds["+inf"], kinds["-inf"], kinds["overflow"]]],
+                         sub["xb"][np.nonzero(sub["assign"] == 0)[0][:6]]])
+    cen = np.concatenate([big["cen"][:3], sub["cen"][:1]])
+    xq = np.concatenate([big["xb"][rows[:2]] * np.float32(1.0001), big["xq"][:1], odd["xq"][[X.Q_NAN, X.Q_INF, X.Q_ZERO]], sub["xq"][:1], sub["xq"][20:21]])
+    return _extreme(METRIC_L2, cen, xb, xq, 2.0 ** -127)
+
+
+def extreme_ip_d24():
+    # ... under the inner product: products whose single-chain sum overflows while the reference's four chains stay finite, rows whose
+    # product is +inf (admitted as the best) and -inf (never), NaN / +-inf elements
+    X = _worlds()
+    big, odd = X.world("ip_norm_overflow", 24), X.world("nonfinite_ip", 24)
+    kinds = {k: r for r, k in sorted(odd["planted"].items(), reverse=True)}
+    pl = {k: r for r, k in sorted(big["planted"].items(), reverse=True)}
+    rows = np.nonzero(big["assign"] < 2)[0][:10]
+    xb = np.concatenate([big["xb"][rows], big["xb"][[pl["+inf"], pl["-inf"]]], odd["xb"][[kinds["nan"], kinds["+inf"], kinds["-inf"], kinds["overflow"]]],
+                         odd["xb"][np.nonzero(odd["assign"] == 0)[0][1:4]]])
+    cen = np.concatenate([big["cen"][:2], odd["cen"][:2]])
+    own = np.nonzero((big["xq"][:, 0] > 0) & (big["xq"][:, 1] > 0))[0][:4]  # (queries of groups 0 and 1: all coordinates but the last two positive)
+    xq = np.concatenate([big["xq"][own], odd["xq"][[X.Q_NAN, X.Q_INF, X.Q_ZERO]], odd["xq"][:1]])
+    return _extreme(METRIC_IP, cen, xb, xq, 0.0)
+
+
+CASES = {f.__name__: f for f in [extreme_l2_d24, extreme_ip_d24, io_ragged, io_sift, fixed_sift_l2, fixed_gauss_l2_d96, fixed_deep_ip_d96, fixed_gist_l2_d960,
                                   fixed_odd_d30, fixed_ragged, fixed_dups, auncel_sift_d32, auncel_gauss_d64, auncel_deep_ip_d64, auncel_sift_nl4096, kmeans_toy, kmeans_void, kmeans_toy_ip, kmeans_sub_int,
                                   kmeans_sub_int_d100, kmeans_ip_spherical_d96]}
 
