@@ -42,6 +42,8 @@ SYMBOLS = [
     "amd_ivf_search_exact", "amd_ivf_search_exact_resident", "amd_ivf_last_exact", "amd_ivf_last_exact_detail",
     "amd_ivf_search_exact_selected", "amd_ivf_search_exact_resident_selected",
     "amd_ivf_range_search_exact", "amd_ivf_range_search_exact_resident", "amd_ivf_range_search_exact_selected", "amd_ivf_last_range_exact",
+    "amd_ivf_make_direct_map", "amd_ivf_direct_map_info", "amd_ivf_reconstruct", "amd_ivf_reconstruct_n", "amd_ivf_reconstruct_from_offsets",
+    "amd_ivf_search_and_reconstruct", "amd_ivf_search_and_reconstruct_resident",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -559,6 +561,60 @@ class Handle:
         I = np.empty((n, k), np.int64)
         _chk(lib().amd_ivf_search(self._h, C.c_size_t(n), _f(x), C.c_size_t(k), C.c_size_t(nprobe), coarse_mode, _f(D), _i(I)))
         return D, I
+
+    # ---- stored vectors back (include/auncel_amd.h: amd_ivf_make_direct_map ...)
+    def make_direct_map(self, enable=True):
+        """the reference's direct_map on the device: one pass over the resident ids; EngineError -2 when an id lies outside [0, ntotal)"""
+        _chk(lib().amd_ivf_make_direct_map(self._h, int(bool(enable))))
+
+    def direct_map_info(self):
+        """[alive, ids mapped, ids of [0, ntotal) without an entry, passes made]"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_direct_map_info(self._h, out))
+        return [int(v) for v in out]
+
+    def reconstruct(self, ids, out=None):
+        """IndexIVF::reconstruct for a batch of ids (needs make_direct_map): the stored rows, len(ids) x d.  out: filled in place"""
+        ids = i64(ids).reshape(-1)
+        rec = np.empty((ids.shape[0], self.d), np.float32) if out is None else out
+        assert rec.dtype == np.float32 and rec.flags.c_contiguous and rec.size == ids.shape[0] * self.d
+        _chk(lib().amd_ivf_reconstruct(self._h, C.c_size_t(ids.shape[0]), _i(ids), _f(rec)))
+        return rec
+
+    def reconstruct_n(self, i0, ni, out=None, want_found=True):
+        """IndexIVF::reconstruct_n over the id window [i0, i0 + ni): (recons, found); slots whose id is not stored keep what `out`
+        held (zeros without `out`) and have found 0"""
+        rec = np.zeros((max(ni, 0), self.d), np.float32) if out is None else out
+        assert rec.dtype == np.float32 and rec.flags.c_contiguous and rec.size == max(ni, 0) * self.d
+        found = np.zeros(max(ni, 0), np.uint8) if want_found else None
+        fp = found.ctypes.data_as(C.POINTER(C.c_uint8)) if found is not None else None
+        _chk(lib().amd_ivf_reconstruct_n(self._h, C.c_int64(i0), C.c_int64(ni), _f(rec), fp))
+        return rec, found
+
+    def reconstruct_from_offsets(self, labels, want_ids=True, out=None, out_ids=None):
+        """rows (and stored ids) of position labels list << 32 | offset, as a store_pairs search returns them; -1: 0xFF bytes, id -1"""
+        labels = i64(labels).reshape(-1)
+        n = labels.shape[0]
+        rec = np.empty((n, self.d), np.float32) if out is None else out
+        ids = (np.empty(n, np.int64) if out_ids is None else out_ids) if want_ids else None
+        _chk(lib().amd_ivf_reconstruct_from_offsets(self._h, C.c_size_t(n), _i(labels), _f(rec), _i(ids)))
+        return rec, ids
+
+    def search_and_reconstruct(self, x, k, nprobe, coarse_mode=0, out=None):
+        """search() plus the stored row of every admitted entry: (D, I, recons n x k x d).  out = (D, I, recons) to fill (e.g.
+        page-locked arrays: recons is then written by the gather itself)"""
+        x = f32(x)
+        n = x.shape[0]
+        D, I, R = out if out is not None else (np.empty((n, k), np.float32), np.empty((n, k), np.int64), np.empty((n, k, self.d), np.float32))
+        _chk(lib().amd_ivf_search_and_reconstruct(self._h, C.c_size_t(n), _f(x), C.c_size_t(k), C.c_size_t(nprobe), coarse_mode, _f(D), _i(I),
+                                                  _f(R)))
+        return D, I, R
+
+    def search_and_reconstruct_resident(self, start, n, k, nprobe, coarse_mode=0, out=None):
+        D, I, R = out if out is not None else (np.empty((n, k), np.float32), np.empty((n, k), np.int64), np.empty((n, k, self.d), np.float32))
+        _chk(lib().amd_ivf_search_and_reconstruct_resident(self._h, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k), C.c_size_t(nprobe),
+                                                           coarse_mode, _f(D), _i(I), _f(R)))
+        return D, I, R
 
     def search_exact(self, x, k):
         """exact top-k over every list (include/auncel_amd.h: amd_ivf_search_exact): search_preassigned with identity keys, bit for bit"""

@@ -127,6 +127,17 @@ struct IndexIVFFlatSubset : Index {
     /// IndexIVFFlat::range_search_exact / range_exact_info over the subset's own lists
     void range_search_exact(idx_t n, const float* x, float radius, RangeSearchResult* result) const;
     void range_exact_info(uint64_t out[4]) const;
+    /// Stored vectors back, from the subset's own lists on the device -- it keeps no host rows (include/auncel_amd.h:
+    /// amd_ivf_make_direct_map ...).  make_direct_map / reconstruct as IndexIVF's: the ids must be 0 .. ntotal - 1 ("direct map
+    /// supported only for seuquential ids" otherwise), reconstruct without a map is "direct map is not initialized".  reconstruct_n
+    /// needs no map and keeps the reference's precondition ni == 0 || (i0 >= 0 && i0 + ni <= ntotal).  search_and_reconstruct runs
+    /// with the subset's nprobe / coarse_mode: search()'s (distances, labels) and the stored row of every admitted entry, rows of
+    /// 0xFF bytes behind the padding.  direct_map_info: amd_ivf_direct_map_info.
+    void make_direct_map(bool new_maintain_direct_map = true);
+    void reconstruct(idx_t key, float* recons) const override;
+    void reconstruct_n(idx_t i0, idx_t ni, float* recons) const override;
+    void search_and_reconstruct(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, float* recons) const override;
+    void direct_map_info(uint64_t out[4]) const;
     bool device_bound() const override { return true; }
     amd_ivf* engine() const { return gpu_; }
 

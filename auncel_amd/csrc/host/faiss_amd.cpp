@@ -1476,6 +1476,21 @@ void IndexIVFFlatSubset::range_search(idx_t nx, const float* x, float radius, Ra
     AMD(amd_ivf_range_results(gpu_, i64(result->labels), result->distances));
 }
 
+// ---- stored vectors back: the subset keeps no host rows, so these go to its engine (amd_ivf_make_direct_map ...)
+void IndexIVFFlatSubset::make_direct_map(bool new_maintain_direct_map) { AMD(amd_ivf_make_direct_map(gpu_, new_maintain_direct_map ? 1 : 0)); }
+void IndexIVFFlatSubset::direct_map_info(uint64_t out[4]) const { AMD(amd_ivf_direct_map_info(gpu_, out)); }
+void IndexIVFFlatSubset::reconstruct(idx_t key, float* recons) const {
+    const int64_t id = (int64_t)key;
+    AMD(amd_ivf_reconstruct(gpu_, 1, &id, recons));
+}
+void IndexIVFFlatSubset::reconstruct_n(idx_t i0, idx_t ni, float* recons) const {
+    FAISS_THROW_IF_NOT(ni == 0 || (i0 >= 0 && i0 <= ntotal && ni <= ntotal - i0));  // (i0 + ni <= ntotal, without the overflow)
+    AMD(amd_ivf_reconstruct_n(gpu_, (int64_t)i0, (int64_t)ni, recons, nullptr));
+}
+void IndexIVFFlatSubset::search_and_reconstruct(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, float* recons) const {
+    AMD(amd_ivf_search_and_reconstruct(gpu_, (size_t)n, x, (size_t)k, nprobe, coarse_mode, distances, i64(labels), recons));
+}
+
 IndexShardsByList::IndexShardsByList(const IndexIVFFlat& index, int nshard, bool threaded_, const int* devices)
     : IndexShards((idx_t)index.d, threaded_, false) {
     FAISS_THROW_IF_NOT(nshard > 0 && index.is_trained);

@@ -27,6 +27,7 @@
 #include "exact_args.h"
 #include "ivf_kernels.h"
 #include "kmeans_host.h"
+#include "reconstruct_args.h"
 
 using namespace amdivf;
 
@@ -541,6 +542,16 @@ struct amd_ivf {
     // and the contiguous result of the fill; the counts of the last call
     DevBuf w_rx_thr, w_rx_id, w_rx_valid, w_rx_off, w_rx_lab, w_rx_dis;
     uint64_t last_range_exact[4] = {0, 0, 0, 0};
+    // stored vectors back (ivf_reconstruct.hip).  On the index owner: the direct map -- table[id] = list << 32 | offset of the last
+    // entry with that id, ntotal slots, made for the lists of dmap_gen -- and {alive, ids mapped, ids without an entry, passes made}.
+    // Per context: the table of a reconstruct_n window, labels / keys sent in, rows, ids and found bytes on their way out, and the
+    // counters + flag of a call (outside, mapped, smallest bad position)
+    DevBuf d_dmap;
+    bool dmap_on = false;
+    uint64_t dmap_gen = ~(uint64_t)0, dmap_mapped = 0, dmap_missing = 0, dmap_passes = 0;
+    DevBuf w_rec_table, w_rec_lab, w_rec_rows, w_rec_ids, w_rec_found, w_rec_cnt;
+    std::vector<float> rec_rows_host;
+    std::vector<uint8_t> rec_found_host;
     DevBuf w_limit;  // time-bounded search: per-slot end of the probe loop (plan_counts_kernel -> replay_kernel)
     DevBuf w_tie_rows;  // rankings re-run through the reference's heap because of equal distances (launch_heap_tie_order)
 
@@ -1762,7 +1773,7 @@ void finish_results(amd_ivf* h, size_t n, size_t k, float* D, int64_t* I, uint32
         d2h_small(h, &back->err, h->w_error.p, 4, h->stream);
         d2h_small(h, back->rows, h->w_stats.p, sizeof back->rows, h->stream);
         if (stage_out) d2h_small(h, stage_out, h->w_stage.p, n * 4, h->stream);
-        if (!h->out_D) {  // (else the kernels wrote the caller's buffers themselves)
+        if (!h->out_D && D) {  // (else the kernels wrote the caller's buffers themselves, or the caller reads w_D / w_I on the device)
             d2h_small(h, D, h->w_D.p, n * k * sizeof(float), h->stream);
             d2h_small(h, I, h->w_I.p, n * k * sizeof(int64_t), h->stream);
         }
@@ -6607,6 +6618,274 @@ int amd_ivf_last_range_exact(amd_ivf_t* h, uint64_t out[4]) {
     if (!h || !out) throw EngineError("null argument");
     require_device();
     for (int i = 0; i < 4; i++) out[i] = h->last_range_exact[i];
+    API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------ stored vectors back
+// The rows are resident: a vector is handed back by a gather over d_codes (the rows amd_ivf_get_list reads), and found by id through
+// a table of positions that one pass over d_ids makes.  Only the counters, the labels / ids sent in and the rows of the answer cross
+// PCIe.
+namespace {
+
+constexpr unsigned long long REC_NO_BAD = ~0ull;
+
+// the counters of a call, on the device: {entries outside the window, slots that took a position, smallest bad position}
+void rec_counters_reset(amd_ivf* h) {
+    h->w_rec_cnt.ensure(24);
+    HIP_CHECK(hipMemsetAsync(h->w_rec_cnt.p, 0, 16, h->stream));
+    HIP_CHECK(hipMemsetAsync(h->w_rec_cnt.as<unsigned char>() + 16, 0xff, 8, h->stream));
+}
+
+// table[id - lo] = the largest position of id, for the stored ids in [lo, lo + n), -1 elsewhere; counts: {outside, slots mapped}.
+// One pass over the resident ids on h's stream; waits for it.
+void rec_positions(amd_ivf* h, DevBuf& table, int64_t lo, uint64_t n, unsigned long long counts[2]) {
+    const amd_ivf* I = ix(h);
+    table.ensure(std::max<uint64_t>(n, 1) * 8);
+    HIP_CHECK(hipMemsetAsync(table.p, 0xff, n * 8, h->stream));
+    rec_counters_reset(h);
+    launch_id_positions(I->d_ids.as<int64_t>(), I->d_list_off.as<uint64_t>(), (uint32_t)I->nlist, I->h_list_off[I->nlist], lo, n,
+                        table.as<int64_t>(), h->w_rec_cnt.as<unsigned long long>(), h->stream);
+    HIP_CHECK(hipMemcpyAsync(counts, h->w_rec_cnt.p, 16, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(stream_sync(h->stream));
+}
+
+// The direct map of the owner h for the lists as they are now: kept while layout_gen repeats, else made again (one more pass).
+// Lists that break the precondition leave no map and switch it off.
+void rec_direct_map(amd_ivf* h) {
+    upload_lists(h);
+    const uint64_t gen = h->layout_gen.load();
+    if (h->dmap_on && h->dmap_gen == gen) return;
+    if (tickets_out(h)) throw EngineError("tickets are still out: wait for them before building the direct map");
+    h->dmap_on = false;
+    h->dmap_mapped = h->dmap_missing = 0;
+    unsigned long long c[2] = {0, 0};
+    rec_positions(h, h->d_dmap, 0, h->ntotal, c);
+    h->dmap_passes++;
+    if (c[0]) {
+        h->d_dmap.release();
+        throw EngineError("direct map supported only for seuquential ids");  // (the reference's message, IndexIVF.cpp:320)
+    }
+    h->dmap_on = true;
+    h->dmap_gen = gen;
+    h->dmap_mapped = c[1];
+    h->dmap_missing = h->ntotal - c[1];
+}
+
+// m rows on h's stream: labels (device), or keys (device) through the owner's direct map.  Nothing is waited for.
+void rec_gather(amd_ivf* h, uint64_t m, const int64_t* d_labels, const int64_t* d_keys, int none_mode, float* rows, int64_t* ids_out,
+                uint8_t* found) {
+    const amd_ivf* I = ix(h);
+    GatherRowsArgs a{};
+    a.m = m;
+    a.labels = d_labels;
+    a.keys = d_keys;
+    a.table = d_keys ? I->d_dmap.as<int64_t>() : nullptr;
+    a.table_n = d_keys ? I->ntotal : 0;
+    a.codes = I->d_codes.as<float>();
+    a.ids = I->d_ids.as<int64_t>();
+    a.list_off = I->d_list_off.as<uint64_t>();
+    a.nlist = I->nlist;
+    a.d = h->d;
+    a.dpad = h->dpad;
+    a.none_mode = none_mode;
+    a.wide_out = h->d == h->dpad && (reinterpret_cast<uintptr_t>(rows) & 15) == 0;
+    a.rows = rows;
+    a.ids_out = ids_out;
+    a.found = found;
+    a.bad = h->w_rec_cnt.as<unsigned long long>() + 2;
+    launch_gather_rows(a, h->stream);
+}
+
+// the flag of the gathers since rec_counters_reset: the smallest position whose label named nothing, or REC_NO_BAD.  Waits.
+unsigned long long rec_bad(amd_ivf* h) {
+    unsigned long long bad = REC_NO_BAD;
+    HIP_CHECK(hipMemcpyAsync(&bad, h->w_rec_cnt.as<unsigned long long>() + 2, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(stream_sync(h->stream));
+    return bad;
+}
+
+// A fixed-nprobe search with pair labels whose result stays on the device (w_D, w_I), then one gather: the labels become the stored
+// ids and the rows of the admitted entries.  The selection keeps positions until its last step whatever the label kind, so (D, ids)
+// are the plain search's bits.  recons: written by the gather itself when it is page-locked (the "direct_out" rule of (D, I)), else
+// gathered in HBM and sent by one copy.
+void search_recon_core(amd_ivf* h, const float* d_x, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I, float* recons,
+                       const IntRange& qr) {
+    h->w_cdis.ensure(n * nprobe * 4);
+    h->w_ckeys.ensure(n * nprobe * 8);
+    coarse_dev(h, d_x, n, nprobe, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(),
+               h->allow_fused && ix(h)->centroid_range.fusable_with(qr, h->metric));
+    search_fixed_device(h, d_x, n, k, nprobe, h->w_ckeys.as<int64_t>(), nullptr, nullptr, 1, 0, qr);
+    const uint64_t m = (uint64_t)n * k;
+    const size_t row_bytes = (size_t)h->d * sizeof(float);
+    float* direct = opt(h, OPT_DIRECT_OUT, 1) != 0 ? static_cast<float*>(device_view(recons)) : nullptr;
+    if (!direct) h->w_rec_rows.ensure(m * row_bytes);
+    h->w_rec_ids.ensure(m * 8);
+    rec_counters_reset(h);
+    rec_gather(h, m, h->w_I.as<int64_t>(), nullptr, RECON_NONE_FILL, direct ? direct : h->w_rec_rows.as<float>(), h->w_rec_ids.as<int64_t>(),
+               nullptr);
+    HIP_CHECK(hipMemcpyAsync(D, h->w_D.p, m * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(I, h->w_rec_ids.p, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (!direct) HIP_CHECK(hipMemcpyAsync(recons, h->w_rec_rows.p, m * row_bytes, hipMemcpyDeviceToHost, h->stream));
+    const unsigned long long bad = rec_bad(h);
+    if (bad != REC_NO_BAD) throw std::runtime_error("search_and_reconstruct: result " + std::to_string(bad) + " names no stored entry");
+}
+
+}  // namespace
+
+extern "C" {
+
+int amd_ivf_make_direct_map(amd_ivf_t* h, int enable) {
+    API_BEGIN
+    if (!h) throw EngineError("make_direct_map: null handle");
+    OWNER_ONLY(h);
+    if (tickets_out(h)) throw EngineError("tickets are still out: wait for them before changing the direct map");
+    require_device();
+    use_device(h);
+    if (!enable) {
+        h->d_dmap.release();
+        h->dmap_on = false;
+        h->dmap_mapped = h->dmap_missing = 0;
+        return 0;
+    }
+    rec_direct_map(h);
+    API_END
+}
+
+int amd_ivf_direct_map_info(amd_ivf_t* h, uint64_t out[4]) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("direct_map_info: null argument");
+    OWNER_ONLY(h);
+    out[0] = h->dmap_on ? 1 : 0;
+    out[1] = h->dmap_mapped;
+    out[2] = h->dmap_missing;
+    out[3] = h->dmap_passes;
+    API_END
+}
+
+int amd_ivf_reconstruct(amd_ivf_t* h, size_t n, const int64_t* ids, float* recons) {
+    API_BEGIN
+    const std::string bad_args = recon_keys_args_error("reconstruct", h != nullptr, n, ids, recons);
+    if (!bad_args.empty()) throw EngineError(bad_args);
+    OWNER_ONLY(h);
+    if (!h->dmap_on) throw EngineError("direct map is not initialized");
+    const size_t b = recon_first_bad_id(ids, n, h->ntotal);
+    if (b < n) throw EngineError("invalid key " + std::to_string(ids[b]) + " at position " + std::to_string(b));
+    require_device();
+    use_device(h);
+    rec_direct_map(h);
+    if (n == 0) return 0;
+    const size_t row_bytes = (size_t)h->d * sizeof(float);
+    h->w_rec_lab.ensure(n * 8);
+    h->w_rec_rows.ensure(n * row_bytes);
+    HIP_CHECK(hipMemcpyAsync(h->w_rec_lab.p, ids, n * 8, hipMemcpyHostToDevice, h->stream));
+    rec_counters_reset(h);
+    rec_gather(h, n, nullptr, h->w_rec_lab.as<int64_t>(), RECON_NONE_ERROR, h->w_rec_rows.as<float>(), nullptr, nullptr);
+    const unsigned long long bad = rec_bad(h);
+    if (bad != REC_NO_BAD)
+        throw EngineError("invalid key " + std::to_string(ids[bad]) + " at position " + std::to_string(bad) + ": no entry in the direct map");
+    HIP_CHECK(hipMemcpyAsync(recons, h->w_rec_rows.p, n * row_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(stream_sync(h->stream));
+    API_END
+}
+
+int amd_ivf_reconstruct_n(amd_ivf_t* h, int64_t i0, int64_t ni, float* recons, uint8_t* found) {
+    API_BEGIN
+    const std::string bad_args = recon_n_args_error(h != nullptr, i0, ni, recons);
+    if (!bad_args.empty()) throw EngineError(bad_args);
+    if (ni == 0) return 0;
+    require_device();
+    use_device(h);
+    upload_lists(h);
+    const uint64_t n = (uint64_t)ni;
+    const size_t row_bytes = (size_t)h->d * sizeof(float);
+    unsigned long long c[2] = {0, 0};
+    rec_positions(h, h->w_rec_table, i0, n, c);
+    if (c[1] == 0) {
+        if (found) memset(found, 0, n);
+        return 0;
+    }
+    h->w_rec_rows.ensure(n * row_bytes);
+    h->w_rec_found.ensure(n);
+    rec_counters_reset(h);
+    rec_gather(h, n, h->w_rec_table.as<int64_t>(), nullptr, RECON_NONE_SKIP, h->w_rec_rows.as<float>(), nullptr, h->w_rec_found.as<uint8_t>());
+    const unsigned long long bad = rec_bad(h);
+    if (bad != REC_NO_BAD) throw std::runtime_error("reconstruct_n: slot " + std::to_string(bad) + " names no stored entry");
+    if (c[1] == n) {  // every slot is stored: one copy, straight to the caller
+        HIP_CHECK(hipMemcpyAsync(recons, h->w_rec_rows.p, n * row_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(stream_sync(h->stream));
+        if (found) memset(found, 1, n);
+        return 0;
+    }
+    // some slots are not: the rows come back by one copy all the same, and only the stored ones are handed on
+    h->rec_rows_host.resize(n * (size_t)h->d);
+    h->rec_found_host.resize(n);
+    HIP_CHECK(hipMemcpyAsync(h->rec_rows_host.data(), h->w_rec_rows.p, n * row_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h->rec_found_host.data(), h->w_rec_found.p, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(stream_sync(h->stream));
+    for (uint64_t i = 0; i < n; i++)
+        if (h->rec_found_host[i]) memcpy(recons + i * (size_t)h->d, h->rec_rows_host.data() + i * (size_t)h->d, row_bytes);
+    if (found) memcpy(found, h->rec_found_host.data(), n);
+    API_END
+}
+
+int amd_ivf_reconstruct_from_offsets(amd_ivf_t* h, size_t n, const int64_t* labels, float* recons, int64_t* ids) {
+    API_BEGIN
+    const std::string bad_args = recon_keys_args_error("reconstruct_from_offsets", h != nullptr, n, labels, recons);
+    if (!bad_args.empty()) throw EngineError(bad_args);
+    if (n == 0) return 0;
+    require_device();
+    use_device(h);
+    upload_lists(h);
+    const amd_ivf* I = ix(h);
+    const size_t b = recon_first_bad_label(labels, n, I->h_list_off.data(), I->nlist);
+    if (b < n) throw EngineError("reconstruct_from_offsets: label at position " + std::to_string(b) + " names no stored entry");
+    const size_t row_bytes = (size_t)h->d * sizeof(float);
+    h->w_rec_lab.ensure(n * 8);
+    h->w_rec_rows.ensure(n * row_bytes);
+    if (ids) h->w_rec_ids.ensure(n * 8);
+    HIP_CHECK(hipMemcpyAsync(h->w_rec_lab.p, labels, n * 8, hipMemcpyHostToDevice, h->stream));
+    rec_counters_reset(h);
+    rec_gather(h, n, h->w_rec_lab.as<int64_t>(), nullptr, RECON_NONE_FILL, h->w_rec_rows.as<float>(), ids ? h->w_rec_ids.as<int64_t>() : nullptr,
+               nullptr);
+    const unsigned long long bad = rec_bad(h);
+    if (bad != REC_NO_BAD) throw EngineError("reconstruct_from_offsets: label at position " + std::to_string(bad) + " names no stored entry");
+    HIP_CHECK(hipMemcpyAsync(recons, h->w_rec_rows.p, n * row_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (ids) HIP_CHECK(hipMemcpyAsync(ids, h->w_rec_ids.p, n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(stream_sync(h->stream));
+    API_END
+}
+
+int amd_ivf_search_and_reconstruct(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I,
+                                   float* recons) {
+    API_BEGIN
+    const std::string bad_args = recon_search_args_error(h != nullptr, x != nullptr, 0, n, k, D, I, recons);
+    if (!bad_args.empty()) throw EngineError(bad_args);
+    require_device();
+    use_device(h);
+    if (n == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    const QueryRows q = host_rows(h, x, n);
+    search_recon_core(h, q.d_x, n, k, nprobe, coarse_mode, D, I, recons, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_and_reconstruct_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D,
+                                            int64_t* I, float* recons) {
+    API_BEGIN
+    const std::string bad_args = recon_search_args_error(h != nullptr, true, start, n, k, D, I, recons);
+    if (!bad_args.empty()) throw EngineError(bad_args);
+    require_device();
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    if (n == 0) return 0;
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    search_recon_core(h, q.d_x, n, k, nprobe, coarse_mode, D, I, recons, q.range);
+    finish_timing(h, wc.stop());
     API_END
 }
 

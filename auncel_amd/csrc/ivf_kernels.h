@@ -727,6 +727,34 @@ void launch_subset_offsets(const uint32_t* count, const uint64_t* block_off, uin
 void launch_subset_compact(const float* old_codes, const int64_t* old_ids, const uint64_t* old_off, const uint64_t* old_block_off, uint32_t nlist,
                            uint64_t nwords, const uint64_t* mask, const uint32_t* rank_base, const uint64_t* new_off, int dpad, float* codes,
                            int64_t* ids, uint32_t* range, hipStream_t s);
+// ---------------------------------------------------------------------------- stored vectors back (ivf_reconstruct.hip)
+// table[id - lo] = max(table[id - lo], list << 32 | offset) for every stored entry whose id lies in [lo, lo + n) (nt entries, list_off:
+// nlist + 1); the caller starts the table at -1 in every slot and counts at {0, 0}: counts[0] += entries outside the window,
+// counts[1] += slots that took a position.  lo + n must be an int64 (reconstruct_args.h: recon_window_error).
+void launch_id_positions(const int64_t* ids, const uint64_t* list_off, uint32_t nlist, uint64_t nt, int64_t lo, uint64_t n, int64_t* table,
+                         unsigned long long* counts, hipStream_t s);
+// m position labels (list << 32 | offset, or -1) into m compact rows of d floats, read from the rows as stored (stride dpad)
+constexpr int RECON_NONE_FILL = 0, RECON_NONE_SKIP = 1, RECON_NONE_ERROR = 2;  // what a label of -1 does
+struct GatherRowsArgs {
+    uint64_t m;
+    const int64_t* labels;   // row i's label, unless ...
+    const int64_t* keys;     // ... table != null: table[keys[i]], keys[i] in [0, table_n)
+    const int64_t* table;
+    uint64_t table_n;
+    const float* codes;      // the resident rows, ids and offsets
+    const int64_t* ids;
+    const uint64_t* list_off;
+    uint64_t nlist;
+    int d, dpad;
+    int none_mode;           // RECON_NONE_FILL: 0xFF bytes and id -1; _SKIP: nothing written, found 0; _ERROR: the flag
+    int wide_out;            // rows is 16-byte aligned and d % 4 == 0: 16-byte stores
+    float* rows;             // m x d out
+    int64_t* ids_out;        // m stored ids out, or null
+    uint8_t* found;          // m bytes out (1: a row was written), or null
+    unsigned long long* bad; // started at ~0 by the caller: the smallest i whose label or key names nothing (nothing is read for it)
+};
+void launch_gather_rows(const GatherRowsArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------------------- search under an id selector (ivf_selector.hip)
 // kept[l] = the set bits of list l's words (a wave per list)
 void launch_selector_list_kept(const uint32_t* count, const uint64_t* block_off, uint32_t nlist, uint32_t* kept, hipStream_t s);

@@ -317,6 +317,57 @@ int amd_ivf_range_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, fl
 int amd_ivf_range_search_exact_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, float radius, size_t* lims);
 int amd_ivf_last_range_exact(amd_ivf_t* h, uint64_t out[4]);
 
+/* ---- stored vectors back ---------------------------------------------------------------------
+ * IndexIVF::make_direct_map / reconstruct / reconstruct_n / search_and_reconstruct and IndexIVFFlat::reconstruct_from_offset
+ * [IndexIVF.cpp:305-328, 869-945, IndexIVFFlat.cpp:226-230, c_api/IndexIVF_c.h:103-150] over the lists that are resident in HBM: a
+ * vector is handed back by a gather over the rows amd_ivf_get_list reads -- the stored bits, whatever arithmetic the scans use, byte-
+ * coded indexes included -- and found by id through a table of positions that one pass over the resident ids makes.
+ * What crosses PCIe: the ids / labels sent in, a few counters, and the rows (and ids) of the answer, by one copy at the end.  Every
+ * call applies a pending journal first and works on an index made by amd_ivf_subset, which keeps no host rows.
+ * A position label is list << 32 | offset, what a store_pairs = 1 search returns; -1 is "no entry".  Ids may repeat: wherever a
+ * vector is found by id, it is the entry at the LARGEST position (the last one the reference's list-by-list, offset-by-offset
+ * loops write), whatever order the device works in.
+ *
+ * amd_ivf_make_direct_map(h, 1): the reference's direct_map, on the device -- table[id] = position, ntotal slots, one pass over the
+ * ids, nothing but the counters comes back.  -2 with the reference's message ("direct map supported only for seuquential ids",
+ * spelled as there), and no map, if any stored id lies outside [0, ntotal).  enable = 0 frees the table.  The map is a function of
+ * the lists: after amd_ivf_set_lists, _add, _update_lists or _remove_ids the next call that needs it makes it again, and if the new
+ * lists break the precondition that call returns -2 and the map is off.  Owner only; refused with tickets out.
+ * amd_ivf_direct_map_info: {1 if a map is alive, ids mapped, ids of [0, ntotal) without an entry, passes over the ids made so far} of
+ * the map as it was last made.
+ * amd_ivf_reconstruct: IndexIVF::reconstruct for n ids at once, recons n x d.  -2 "direct map is not initialized" without a map; -2
+ * "invalid key", with the id and its position in ids, for an id outside [0, ntotal) and for one without an entry in the map (the
+ * reference reads direct_map's -1 as a position there).  Whatever is refused, recons is untouched.  Owner only.
+ * amd_ivf_reconstruct_n: IndexIVF::reconstruct_n over the id window [i0, i0 + ni): slot id - i0 of recons (ni x d) gets the row of the
+ * last stored entry with that id; a slot whose id is not stored is left as it was, as the reference leaves it, and found[slot] (may
+ * be NULL) says which is which.  Needs no map and assumes nothing about the ids: the window may lie anywhere (the reference's
+ * i0 >= 0 && i0 + ni <= ntotal is the class mirror's to enforce); its table costs 8 ni bytes of HBM.  ni = 0 returns 0 without a
+ * launch; -2 before the device is touched for ni < 0 and for i0 + ni beyond the int64 range.  Works on amd_ivf_clone contexts.
+ * amd_ivf_reconstruct_from_offsets: reconstruct_from_offset for n labels at once; ids (may be NULL) gets the stored ids.  A label of
+ * -1 gives a row of 0xFF bytes -- the reference's memset(reconstructed, -1, ...) -- and id -1.  -2, naming the position, for a label
+ * whose list is >= nlist or whose offset is at or past its list's size (every negative label but -1 is one); the outputs are then
+ * untouched.  Works on amd_ivf_clone contexts.
+ * amd_ivf_search_and_reconstruct / _resident: (D, I) are, bit for bit, what amd_ivf_search / amd_ivf_search_resident return for the
+ * same arguments; recons (n x k x d) row (i, j) is the stored row of the ENTRY that was admitted -- its position, not "some entry
+ * with id I[i, j]" -- and a row of 0xFF bytes where I is the padding's -1.  The search runs with pair labels that never leave the
+ * device; one gather turns them into ids and rows.  amd_ivf_stats, amd_ivf_last_timing and the tie diagnostics move as for the plain
+ * search (the wall time includes the gather).  (D, I) come back by a copy at the end; recons is written by the gather itself when
+ * it is page-locked and option "direct_out" is not 0, else it is gathered in HBM and comes back by one copy.  Works on
+ * amd_ivf_clone contexts and on subsets.
+ * Returns -2 before the device is touched for: a null h; null ids / labels / x or a null output with n > 0; k = 0; a resident range
+ * that wraps round.
+ * Not offered, because no entry point takes them, so none can return a wrong row: a selector form (cut a subset and reconstruct from
+ * it), the exact calls (they have no store_pairs), the adaptive rule, tickets. */
+int amd_ivf_make_direct_map(amd_ivf_t* h, int enable);
+int amd_ivf_direct_map_info(amd_ivf_t* h, uint64_t out[4]);
+int amd_ivf_reconstruct(amd_ivf_t* h, size_t n, const int64_t* ids, float* recons);
+int amd_ivf_reconstruct_n(amd_ivf_t* h, int64_t i0, int64_t ni, float* recons, uint8_t* found);
+int amd_ivf_reconstruct_from_offsets(amd_ivf_t* h, size_t n, const int64_t* labels, float* recons, int64_t* ids);
+int amd_ivf_search_and_reconstruct(amd_ivf_t* h, size_t n, const float* x, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I,
+                                   float* recons);
+int amd_ivf_search_and_reconstruct_resident(amd_ivf_t* h, size_t start, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D,
+                                            int64_t* I, float* recons);
+
 /* InvertedListScanner: set_query + set_list + scan_codes on a caller-owned raw binary heap
  * (simi/idxi, k entries, heapified by the caller as in tests/test_lowlevel_ivf.cpp:150-175);
  * returns the number of heap updates in *nup  [IndexIVFFlat.cpp:101-137] */

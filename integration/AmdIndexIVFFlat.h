@@ -172,6 +172,20 @@ struct AmdIndexIVFFlat : IndexIVFFlat {
     };
     InvertedListScanner* get_InvertedListScanner(bool store_pairs = false) const override { return new Scanner(this, store_pairs); }
 
+    // Stored vectors back from the device rows, for a maintainer who does not keep the host lists around: the
+    // reference's reconstruct / reconstruct_n / search_and_reconstruct read `invlists` and stay as they are; these two ask the
+    // engine instead (include/auncel_amd.h: amd_ivf_search_and_reconstruct, amd_ivf_reconstruct_n).  The search runs with the
+    // index's nprobe on the exact coarse path; rows behind a padding label are 0xFF bytes, as the reference's memset leaves them.
+    void device_search_and_reconstruct(idx_t n, const float* x, idx_t k, float* D, idx_t* I, float* recons) const {
+        Lease lease(this, false, false);
+        check(amd_ivf_search_and_reconstruct(lease.ctx, (size_t)n, x, (size_t)k, nprobe, 0, D, reinterpret_cast<int64_t*>(I), recons));
+    }
+    void device_reconstruct_n(idx_t i0, idx_t ni, float* recons) const {
+        FAISS_THROW_IF_NOT(ni == 0 || (i0 >= 0 && i0 <= ntotal && ni <= ntotal - i0));
+        Lease lease(this, false, false);
+        check(amd_ivf_reconstruct_n(lease.ctx, (int64_t)i0, (int64_t)ni, recons, nullptr));
+    }
+
    private:
     // Device state.  search_preassigned is const and re-entrant like the reference's.  Everything below is guarded by `mu`.
     // A call checks a search context out of a bounded pool (clones of h: own stream and work buffers, same lists) and gives it
