@@ -39,6 +39,8 @@ SYMBOLS = [
     "amd_ivf_selector_combine", "amd_ivf_range_search_selected", "amd_ivf_range_search_preassigned_selected",
     "amd_ivf_submit_search_resident_selected",
     "amd_ivf_search_selected_each", "amd_ivf_search_preassigned_selected_each", "amd_ivf_search_resident_selected_each",
+    "amd_ivf_search_adaptive_selected", "amd_ivf_search_adaptive_x_selected", "amd_ivf_search_adaptive_selected_each",
+    "amd_ivf_train_samples_selected",
     "amd_ivf_search_exact", "amd_ivf_search_exact_resident", "amd_ivf_last_exact", "amd_ivf_last_exact_detail",
     "amd_ivf_search_exact_selected", "amd_ivf_search_exact_resident_selected",
     "amd_ivf_range_search_exact", "amd_ivf_range_search_exact_resident", "amd_ivf_range_search_exact_selected", "amd_ivf_last_range_exact",
@@ -498,6 +500,53 @@ class Handle:
         I = np.empty((n, k), np.int64)
         _chk(lib().amd_ivf_search_resident_selected_each(self._h, table, nsel, so, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k),
                                                          C.c_size_t(nprobe), coarse_mode, _f(D), _i(I)))
+        return D, I
+
+    # ---- the adaptive rule and its training branch under a selector (include/auncel_amd.h: amd_ivf_search_adaptive_selected & co)
+    def _adaptive_args(self, n, require_acc, my_nprobe, t_recalls, gt_D):
+        assert my_nprobe.dtype == np.uint64 and t_recalls.dtype == np.float32
+        K = self.max_topk
+        return f32(require_acc), (f32(gt_D) if gt_D is not None else None), np.empty((n, K), np.float32), np.empty((n, K), np.int64)
+
+    def search_adaptive_selected(self, selector, start, n, query_topk, multipler, std_m, require_acc, my_nprobe, t_recalls, gt_D=None,
+                                 profile=0, coarse_mode=0):
+        """search_adaptive over the selector's members: the bits of the same call on subset(the same selector)"""
+        req, gt, D, I = self._adaptive_args(n, require_acc, my_nprobe, t_recalls, gt_D)
+        _chk(lib().amd_ivf_search_adaptive_selected(self._h, selector._s, C.c_size_t(start), C.c_size_t(n), C.c_size_t(query_topk),
+                                                    C.c_float(multipler), C.c_float(std_m), _f(req), _f(gt), int(profile), coarse_mode,
+                                                    my_nprobe.ctypes.data_as(_u64p), _f(t_recalls), _f(D), _i(I)))
+        return D, I
+
+    def search_adaptive_x_selected(self, selector, x, id_offset, query_topk, multipler, std_m, require_acc, my_nprobe, t_recalls,
+                                   gt_D=None, profile=0, coarse_mode=0):
+        """... over the caller's query rows: row qi is query id_offset + qi of every per-query array"""
+        x = f32(x)
+        n = x.shape[0]
+        req, gt, D, I = self._adaptive_args(n, require_acc, my_nprobe, t_recalls, gt_D)
+        _chk(lib().amd_ivf_search_adaptive_x_selected(self._h, selector._s, C.c_size_t(n), _f(x), C.c_size_t(id_offset),
+                                                      C.c_size_t(query_topk), C.c_float(multipler), C.c_float(std_m), _f(req), _f(gt),
+                                                      int(profile), coarse_mode, my_nprobe.ctypes.data_as(_u64p), _f(t_recalls), _f(D),
+                                                      _i(I)))
+        return D, I
+
+    def search_adaptive_selected_each(self, sels, sel_of, start, n, query_topk, multipler, std_m, require_acc, my_nprobe, t_recalls,
+                                      gt_D=None, profile=0, coarse_mode=0):
+        """... with a selector per query: resident query start + i is searched under sels[sel_of[i]]"""
+        table, nsel, sel_of, so = self._each(sels, sel_of, n)
+        req, gt, D, I = self._adaptive_args(n, require_acc, my_nprobe, t_recalls, gt_D)
+        _chk(lib().amd_ivf_search_adaptive_selected_each(self._h, table, nsel, so, C.c_size_t(start), C.c_size_t(n), C.c_size_t(query_topk),
+                                                         C.c_float(multipler), C.c_float(std_m), _f(req), _f(gt), int(profile),
+                                                         coarse_mode, my_nprobe.ctypes.data_as(_u64p), _f(t_recalls), _f(D), _i(I)))
+        return D, I
+
+    def train_samples_selected(self, selector, start, n, max_topk, gt_D, train_num, raw, coarse_mode=0):
+        """train_samples over the selector's members (gt_D: the filtered ground truth)"""
+        gt = f32(gt_D)
+        D = np.empty((n, max_topk), np.float32)
+        I = np.empty((n, max_topk), np.int64)
+        ptrs = (_f32p * len(raw))(*[_f(r) for r in raw])
+        _chk(lib().amd_ivf_train_samples_selected(self._h, selector._s, C.c_size_t(start), C.c_size_t(n), C.c_size_t(max_topk), _f(gt),
+                                                  C.c_size_t(train_num), coarse_mode, ptrs, _f(D), _i(I)))
         return D, I
 
     def range_search_selected(self, selector, x, radius, nprobe, keys=None, coarse_mode=0):

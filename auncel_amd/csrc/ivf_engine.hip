@@ -90,6 +90,8 @@ enum OptId {
     OPT_EXACT_FLOAT,        // amd_ivf_search_exact over float lists: 1 the fp16 matrix-core list pass + rescoring, 0 (the default) the general way
     OPT_EXACT_WIDE,         // ... beyond 128 dimensions (up to 1024), with exact_float: 1 the workgroup-tiled fp16 list pass, 0 (the default) the general way
     OPT_EXACT_WIDE_BYTES,   // amd_ivf_search_exact over byte-coded lists beyond 128 dimensions (up to 1024): 1 the workgroup-tiled byte list pass, 0 (the default) the general way
+    OPT_SELECTED_SKIP_EMPTY,  // amd_ivf_search_adaptive_selected & co: 1 (the default) a list that keeps nothing under a query's selector is planned as
+                              // an absent probe -- no row, no scan; the probe still counts -- 0 it is scanned and masked out like any other
     N_OPT
 };
 struct OptSpec {
@@ -121,6 +123,7 @@ const OptSpec OPT_TABLE[N_OPT] = {
     {"exact_float", "AUNCEL_AMD_EXACT_FLOAT", nullptr},
     {"exact_wide", "AUNCEL_AMD_EXACT_WIDE", nullptr},
     {"exact_wide_bytes", "AUNCEL_AMD_EXACT_WIDE_BYTES", nullptr},
+    {"selected_skip_empty", "AUNCEL_AMD_SELECTED_SKIP_EMPTY", nullptr},
 };
 struct Options {
     // (atomic: amd_ivf_set_option on the owner may run while search contexts cloned from it are searching; a search reads the
@@ -533,6 +536,18 @@ struct amd_ivf {
     const int64_t* given_keys = nullptr;
     const float* given_dis = nullptr;
     size_t given_nprobe = 0;
+    // tune / train search under an id selector (amd_ivf_search_adaptive_selected & co, SelectedCall): what adaptive_core_once and
+    // train_core hand to the rounds.  One selector: its keep words and its per-list kept counts (device).  A selector per query: the
+    // device addresses of both for every selector of the table, and the selector number of every query of the PASS AT HAND (host:
+    // the second pass of the "redo" tie regime searches a few of the call's queries again and re-indexes it)
+    struct SelectedState {
+        const unsigned long long* keep = nullptr;
+        const uint32_t* kept = nullptr;
+        std::vector<uint64_t> keep_bases, kept_bases;
+        const uint32_t* sel_of = nullptr;
+        bool skip_empty = false;  // plan a (query, list) pair whose list keeps nothing as an absent probe (option selected_skip_empty)
+        bool on() const { return keep != nullptr || !keep_bases.empty(); }
+    } selected;
     // amd_ivf_search_exact: per-block table of the fragment copy, the queries' candidate counters and buffers, the selection's flags
     // and totals, its results, the rows and numbers of the queries that go the general way; the counts of the last call
     DevBuf w_ex_blk, w_ex_cnt, w_ex_cand, w_ex_flag, w_ex_tot, w_ex_D, w_ex_I, w_ex_x, w_ex_idx;
@@ -1301,6 +1316,7 @@ struct KeepEach {
     const unsigned long long* const* keeps = nullptr;
     const uint32_t* sel_of = nullptr;
     uint32_t nsel = 0;
+    const uint32_t* const* kepts = nullptr;  // ... and of its per-list kept counts (stage_selected_each: the calls that skip empty lists)
 };
 // What a search hands to run_rounds_device: the queries and their coarse ranking on the device, and what the rounds do with them.
 struct RoundSpec {
@@ -1348,6 +1364,11 @@ struct RoundSpec {
     // ... under a selector per QUERY (amd_ivf_search_*_selected_each; keep stays null): the device table of the call's keep-word
     // bases and the selector number of every query slot (keep_rows_each_kernel); everything behind the mask is the same
     KeepEach each{};
+    // ... and plans a (query, list) pair whose list keeps nothing under the query's selector as an absent probe (the adaptive and
+    // training calls under a selector, option selected_skip_empty): the per-list kept counts of `keep`'s selector; under a selector
+    // per query each.kepts
+    const uint32_t* kept = nullptr;
+    bool skip_empty = false;
 };
 
 static bool dbg_timing() {
@@ -2393,6 +2414,11 @@ void run_rounds_device(amd_ivf* h, const RoundSpec& base, size_t n, size_t first
     pa.error = h->w_error.as<uint32_t>();
     uint32_t* const d_unfinished = h->w_pl_counters.as<uint32_t>() + 24;  // [PLAN_MAX_ROUNDS][8 XCDs]
     pa.round_unfinished = d_unfinished;
+    if (base.skip_empty) {
+        pa.kept = base.kept;
+        pa.kepts = base.each.kepts;
+        pa.kept_sel_of = base.each.sel_of;
+    }
     if (base.d_budget_ms) {
         h->w_limit.ensure(n * 4);
         pa.budget_ms = base.d_budget_ms;
@@ -3963,6 +3989,32 @@ static size_t coarse_read_bound(size_t nlist, float multipler, const uint64_t* m
     return bound + 16;
 }
 
+// A tune / train pass of n queries under the selector(s) its entry point has set on the handle (amd_ivf::SelectedState): the rounds'
+// keep words, and the kept counts when the planner is to skip the lists that keep nothing.  A selector per query: the call's table on
+// the device -- nsel keep-word bases, nsel kept-count bases, then the selector number of every query of this pass -- packed on the
+// host and queued with the pass's other small inputs (h2d_small; the caller flushes).
+static void selected_into_rounds(amd_ivf* h, size_t n, RoundSpec& base) {
+    const amd_ivf::SelectedState& sc = h->selected;
+    if (!sc.on()) return;
+    base.skip_empty = sc.skip_empty;
+    if (sc.keep) {
+        base.keep = sc.keep;
+        base.kept = sc.kept;
+        return;
+    }
+    const size_t nsel = sc.keep_bases.size(), words = 2 * nsel + (n + 1) / 2;
+    h->keep_each_host.assign(words, 0);
+    std::copy(sc.keep_bases.begin(), sc.keep_bases.end(), h->keep_each_host.begin());
+    std::copy(sc.kept_bases.begin(), sc.kept_bases.end(), h->keep_each_host.begin() + nsel);
+    memcpy(h->keep_each_host.data() + 2 * nsel, sc.sel_of, n * 4);
+    h->w_keep_each.ensure(words * 8);
+    h2d_small(h, h->w_keep_each.p, h->keep_each_host.data(), words * 8, h->stream);
+    base.each.keeps = h->w_keep_each.as<const unsigned long long*>();
+    base.each.kepts = reinterpret_cast<const uint32_t* const*>(h->w_keep_each.as<uint64_t>() + nsel);
+    base.each.sel_of = reinterpret_cast<const uint32_t*>(h->w_keep_each.as<uint64_t>() + 2 * nsel);
+    base.each.nsel = (uint32_t)nsel;
+}
+
 // One adaptive (tune) search of queries [start, start + n) on h, under the tie-order regime its caller has set (TieRegime)
 static void adaptive_core_once(amd_ivf_t* h, const float* d_x, size_t start, size_t n, size_t query_topk, float multipler, float std_m,
                             const float* require_acc, const float* gt_D, int profile, int coarse_mode,
@@ -4005,6 +4057,9 @@ static void adaptive_core_once(amd_ivf_t* h, const float* d_x, size_t start, siz
     h2d_small(h, dtr + start, t_recalls + start, n * 4, h->stream);
     if (gt_D) HIP_CHECK(hipMemcpyAsync(dgt + start * K, gt_D + start * K, n * K * 4, hipMemcpyHostToDevice, h->stream));
     h2d_small(h, d_np.as<unsigned long long>() + start, my_nprobe + start, n * 8, h->stream);
+    RoundSpec base;
+    selected_into_rounds(h, n, base);  // (under a selector: the keep words; a selector per query: the call's table rides along)
+    const bool selected = h->selected.on();
     flush_h2d(h, h->stream);
     host_stamp("inputs");
 
@@ -4089,7 +4144,9 @@ static void adaptive_core_once(amd_ivf_t* h, const float* d_x, size_t start, siz
             // heap sort (nlist a power of two) the heap takes ~1.5 ms a row, about what coarse ranking -> planning -> scan of
             // round 0 take among other searches; the literal heap (12 ms a row) stays under the pass and feeds a second one.
             static const bool no_patch = getenv("AUNCEL_AMD_NO_TIE_PATCH") != nullptr;
-            h->spec_inline = !no_patch && (nlist & (nlist - 1)) == 0 && nlist >= 64;
+            // (under a selector the pass is not patched: a round's mask words are addressed by its rows' places, launch_tie_patch moves
+            // rows and knows nothing of masks -- such calls run under the non-patching regime, the second pass of adaptive_redo_ties)
+            h->spec_inline = !no_patch && !selected && (nlist & (nlist - 1)) == 0 && nlist >= 64;
         }
     }
     const bool tie_inline = h->want_first_tie && h->spec_valid && h->spec_inline;
@@ -4111,7 +4168,6 @@ static void adaptive_core_once(amd_ivf_t* h, const float* d_x, size_t start, siz
                           only, only_count);
     };
     if (!fuse_small && !tie_inline) set_online();
-    RoundSpec base;
     if (tie_inline) {
         // room for the rows the patch moves: a round's rows of every slot if that is not beyond reason (a query that finds no room is
         // searched again)
@@ -4326,10 +4382,20 @@ static void adaptive_redo_ties(amd_ivf_t* h, const float* d_x, size_t start, siz
     }
     h->ties_override = 1;
     h->spec_use = spec;
+    // (under a selector per query the queries searched again keep theirs: sel_of of this pass is by their place in it; the entry
+    // point's scope puts the handle's state back whatever happens here)
+    std::vector<uint32_t> sel_again;
+    const uint32_t* const sel_of_call = h->selected.sel_of;
+    if (sel_of_call) {
+        sel_again.resize(m);
+        for (size_t j = 0; j < m; j++) sel_again[j] = sel_of_call[again[j]];
+        h->selected.sel_of = sel_again.data();
+    }
     with_select_fallback(h, [&] {
         adaptive_core_once(h, h->w_redo_x.as<float>(), 0, m, query_topk, multipler, std_m, req.data(), gt_D ? gt.data() : nullptr, profile,
                            coarse_mode, np.data(), tr.data(), Dc.data(), Ic.data(), qr);
     });
+    h->selected.sel_of = sel_of_call;
     for (size_t j = 0; j < m; j++) {
         const size_t i = again[j];
         my_nprobe[start + i] = np[j];
@@ -4489,6 +4555,10 @@ static void train_core(amd_ivf_t* h, const float* d_x, size_t start, size_t n, s
     launch_set_online(h->metric, (uint32_t)nlist, (uint32_t)n, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(), (uint32_t)np_row,
                       h->d_interdis.as<float>(), h->d_arcos.as<float>(), h->w_dtb.as<float>(), h->w_error.as<uint32_t>(), h->stream);
     RoundSpec base;
+    if (h->selected.on()) {  // (amd_ivf_train_samples_selected: the heaps the stages read hold the selector's members only)
+        selected_into_rounds(h, n, base);
+        flush_h2d(h, h->stream);
+    }
     base.fused = h->allow_fused && h->db_range.fusable_with(qr, h->metric);
     base.bytes = byte_queries(h, ix(h), d_x, n, qr);
     ix(h)->last_arith = base.bytes ? 2 : base.fused ? 1 : 0;
@@ -5887,6 +5957,115 @@ int amd_ivf_search_resident_selected_each(amd_ivf_t* h, const amd_ivf_selector_t
     const KeepEach each = stage_selector_each(h, sels, nsel, sel_of, n);
     search_full(h, q.d_x, n, k, nprobe, coarse_mode, D, I, q.range, nullptr, &each);
     finish_timing(h, wc.stop());
+    API_END
+}
+
+}  // extern "C"
+
+namespace {
+// Scope of an adaptive or training call under a selector (one, or a table with sel_of: the selector number of every query of the
+// call): amd_ivf::SelectedState of the handle, which adaptive_core_once and train_core read, cleared on the way out.  The selectors
+// were checked by the caller (selector_words, check_selector_each).  An index without entries has no keep words and no counts:
+// the call then runs as the unselected one, which finds nothing either.
+struct SelectedCall {
+    amd_ivf* h;
+    SelectedCall(amd_ivf* hh, const amd_ivf_selector* one, const amd_ivf_selector* const* sels, size_t nsel, const uint32_t* sel_of) : h(hh) {
+        amd_ivf::SelectedState& sc = h->selected;
+        sc = amd_ivf::SelectedState{};
+        if (ix(h)->ntotal == 0) return;
+        sc.skip_empty = opt(h, OPT_SELECTED_SKIP_EMPTY, 1) != 0;
+        if (one) {
+            sc.keep = one->keep.as<unsigned long long>();
+            sc.kept = one->list_kept.as<uint32_t>();
+            return;
+        }
+        for (size_t j = 0; j < nsel; j++) {
+            sc.keep_bases.push_back((uint64_t) reinterpret_cast<uintptr_t>(sels[j]->keep.as<unsigned long long>()));
+            sc.kept_bases.push_back((uint64_t) reinterpret_cast<uintptr_t>(sels[j]->list_kept.as<uint32_t>()));
+        }
+        sc.sel_of = sel_of;
+    }
+    SelectedCall(const SelectedCall&) = delete;
+    ~SelectedCall() { h->selected = amd_ivf::SelectedState{}; }
+};
+// what every adaptive call under a selector refuses beside its selector(s): read before anything behind a pointer is
+void check_adaptive_selected(const char* what, bool have_all, int profile) {
+    if (!have_all) throw EngineError(std::string(what) + ": null argument");
+    if (profile & 2) throw EngineError(std::string(what) + ": profile bit 1 (overhead_profile) is not offered under a selector");
+}
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------ the adaptive rule under an id selector
+// amd_ivf_search_adaptive / _x over the selector's members only: every round carries the selector's mask (RoundSpec::keep), the stop
+// rule is evaluated after every probe on the heap of the members, and the traces are whatever the handle holds.  Bit for bit what
+// the unselected call returns on amd_ivf_subset of the same selector.
+int amd_ivf_search_adaptive_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t query_topk, float multipler,
+                                     float std_m, const float* require_acc, const float* gt_D, int profile, int coarse_mode,
+                                     uint64_t* my_nprobe, float* t_recalls, float* D, int64_t* I) {
+    API_BEGIN
+    check_adaptive_selected("search_adaptive_selected", h && s && require_acc && my_nprobe && t_recalls && D && I, profile);
+    selector_words(h, s);
+    OWNER_ONLY(h);
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    if (n == 0) return 0;
+    SelectedCall call(h, s, nullptr, 0, nullptr);
+    adaptive_core(h, q.d_x, start, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, D, I,
+                  q.range);
+    API_END
+}
+
+int amd_ivf_search_adaptive_x_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t id_offset, size_t query_topk,
+                                       float multipler, float std_m, const float* require_acc, const float* gt_D, int profile,
+                                       int coarse_mode, uint64_t* my_nprobe, float* t_recalls, float* D, int64_t* I) {
+    API_BEGIN
+    check_adaptive_selected("search_adaptive_x_selected", h && s && (x || n == 0) && require_acc && my_nprobe && t_recalls && D && I, profile);
+    selector_words(h, s);
+    OWNER_ONLY(h);
+    use_device(h);
+    if (n == 0) return 0;
+    const QueryRows q = host_rows(h, x, n);
+    SelectedCall call(h, s, nullptr, 0, nullptr);
+    adaptive_core(h, q.d_x, id_offset, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, D, I,
+                  q.range);
+    API_END
+}
+
+// ... with a selector per query: resident queries, sel_of[i] belongs to query start + i (every other array is by absolute id)
+int amd_ivf_search_adaptive_selected_each(amd_ivf_t* h, const amd_ivf_selector_t* const* sels, size_t nsel, const uint32_t* sel_of, size_t start,
+                                          size_t n, size_t query_topk, float multipler, float std_m, const float* require_acc,
+                                          const float* gt_D, int profile, int coarse_mode, uint64_t* my_nprobe, float* t_recalls, float* D,
+                                          int64_t* I) {
+    API_BEGIN
+    check_adaptive_selected("search_adaptive_selected_each", require_acc && my_nprobe && t_recalls, profile);
+    check_selector_each("search_adaptive_selected_each", h, sels, nsel, sel_of, n, nullptr, false, D, I);
+    const std::string bad = selector_each_range_error("search_adaptive_selected_each", start, n, resident_owner(h)->n_resident);
+    if (!bad.empty()) throw EngineError(bad);
+    OWNER_ONLY(h);
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    if (n == 0) return 0;
+    SelectedCall call(h, nullptr, sels, nsel, sel_of);
+    adaptive_core(h, q.d_x, start, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, D, I,
+                  q.range);
+    API_END
+}
+
+// amd_ivf_train_samples over the selector's members only: the heaps the stages 1, 2, 4 ... nlist/8 read hold members only, so the
+// raw traces are a tenant's own when gt_D is its filtered ground truth (amd_ivf_search_exact_selected)
+int amd_ivf_train_samples_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t max_topk, const float* gt_D,
+                                   size_t train_num, int coarse_mode, float* const* raw, float* D, int64_t* I) {
+    API_BEGIN
+    if (!h || !s || !gt_D || !raw || !D || !I) throw EngineError("train_samples_selected: null argument");
+    selector_words(h, s);
+    OWNER_ONLY(h);
+    use_device(h);
+    if (start + n < start || start + n > h->n_resident) throw EngineError("resident query range out of bounds");
+    SelectedCall call(h, s, nullptr, 0, nullptr);
+    train_core(h, h->d_resident.as<float>() + start * h->dpad, start, n, max_topk, gt_D, train_num, coarse_mode, raw, D, I,
+               h->resident_range);
     API_END
 }
 

@@ -509,6 +509,13 @@ struct PlanArgs {
     // null or the sorted coarse distances [nq][key_stride]: a round never ends inside a run of exactly equal distances (the order
     // inside a run may still change -- launch_tie_patch -- and a round's rows can be reordered, not exchanged with the next round's)
     const float* run_dis;
+    // a search under an id selector that skips the lists it keeps nothing in: the per-list kept counts of the call's selector (kept),
+    // or of every selector of the call's table with the selector number of every query slot (kepts / kept_sel_of); all null: every
+    // probe is planned.  A (query, list) pair whose count is 0 is planned as an absent probe: seg_list -1, no row, no pair, no item --
+    // the selection counts the probe and evaluates the stop rule after it, as it does for an empty list.
+    const uint32_t* kept;
+    const uint32_t* const* kepts;
+    const uint32_t* kept_sel_of;
 };
 
 // self-check of the per-XCD counters (ivf_plan.hip: xcd_check_kernel): counters [8][nkeys] zeroed by the caller

@@ -26,6 +26,10 @@ __device__ __forceinline__ void plan_begin(const PlanArgs& a, uint32_t tid, uint
     if (a.first_plan && a.round_unfinished)
         for (uint32_t r = tid; r < PLAN_MAX_ROUNDS * 8; r += nthreads) a.round_unfinished[r] = 0;
 }
+// the per-list kept counts query slot i is planned under (PlanArgs::kept / kepts; wave-uniform), or null: every probe is planned
+__device__ __forceinline__ const uint32_t* plan_kept_of(const PlanArgs& a, uint32_t i) {
+    return a.kept ? a.kept : a.kepts ? a.kepts[a.kept_sel_of[i]] : nullptr;
+}
 // one wave: query i
 __device__ __forceinline__ void plan_counts_query(const PlanArgs& a, uint32_t i, uint32_t lane) {
     const bool have = i < a.nq;
@@ -77,9 +81,10 @@ __device__ __forceinline__ void plan_counts_query(const PlanArgs& a, uint32_t i,
         const bool ends = target >= a.total_nprobe || last || (a.tune && np != 0);
         more = ends ? 0u : 1u;
         const int64_t* kq = a.keys + (size_t)i * a.key_stride + stage;
+        const uint32_t* kept = plan_kept_of(a, i);
         for (uint32_t p = lane; p < cnt; p += 64) {
             const int64_t key = kq[p];
-            if (key >= 0 && (unsigned long long)key < a.nlist) {
+            if (key >= 0 && (unsigned long long)key < a.nlist && !(kept && kept[key] == 0)) {
                 const unsigned long long sz = a.list_off[key + 1] - a.list_off[key], psz = (sz + ra) & ~ra;
                 need += psz;
                 pad += (uint32_t)(psz - sz);
@@ -262,12 +267,14 @@ __device__ __forceinline__ void plan_segments_query(const PlanArgs& a, uint32_t 
     unsigned long long cur = a.dist_base[i];  // wave-uniform running offset
     const unsigned long long ra = a.row_align - 1;
     const uint32_t sb = a.seg_begin[i];
+    const uint32_t* kept = plan_kept_of(a, i);
     for (uint32_t p0 = 0; p0 < c; p0 += 64) {
         const uint32_t p = p0 + lane;
         int64_t key = -1;
         unsigned long long psz = 0;
         if (p < c) {
             key = kq[p];
+            if (kept && key >= 0 && (unsigned long long)key < a.nlist && kept[key] == 0) key = -1;  // (nothing kept: an absent probe)
             if (key >= 0 && (unsigned long long)key < a.nlist) {
                 const unsigned long long sz = a.list_off[key + 1] - a.list_off[key];
                 if (sz) {
@@ -639,12 +646,14 @@ __global__ __launch_bounds__(64) void plan_one_kernel(PlanArgs a) {
     uint32_t np = 0, ni = 0;                            // pairs (= query groups) and items so far
     double list_bytes = 0;
     const uint32_t tv1 = scan_tile_vecs(1);
+    const uint32_t* kept = plan_kept_of(a, 0);
     for (uint32_t p0 = 0; p0 < c; p0 += 64) {
         const uint32_t p = p0 + lane;
         int64_t key = -1;
         uint32_t sz = 0;
         if (p < c) {
             key = kq[p];
+            if (kept && key >= 0 && (unsigned long long)key < a.nlist && kept[key] == 0) key = -1;  // (nothing kept: an absent probe)
             if (key >= 0 && (unsigned long long)key < a.nlist) sz = (uint32_t)(a.list_off[key + 1] - a.list_off[key]);
         }
         const bool valid = sz != 0;

@@ -153,10 +153,11 @@ int amd_ivf_selector_combine(int op, const amd_ivf_selector_t* a, const amd_ivf_
  * in order; a query that finds fewer than k members ends with the reference's padding.  The coarse ranking is h's own.  In
  * amd_ivf_stats, nheap_updates is the subset's (the admissions are the same sequence); ndis counts the entries of the probed lists
  * AS h HOLDS THEM, members or not: every one of them is scanned.
- * Fixed nprobe or a radius (below), every list (amd_ivf_search_exact_selected, further down), ids.  Not offered under a selector: the adaptive rule (its traces are trained on the whole
- * index), the scanner calls, store_pairs / max_codes, and tickets of any search but amd_ivf_search_resident_selected -- there is no
- * entry point that takes a selector for any of them, so none can return an unfiltered answer.  One selector per QUERY: the _each
- * calls below (fixed nprobe only).  -2 for a null h / s, a selector of another index, a stale selector. */
+ * Fixed nprobe or a radius (below), every list (amd_ivf_search_exact_selected, further down), the adaptive rule and its training
+ * branch (amd_ivf_search_adaptive_selected & co, below), ids.  Not offered under a selector: the scanner calls, store_pairs /
+ * max_codes, and tickets of any search but amd_ivf_search_resident_selected -- there is no entry point that takes a selector for any
+ * of them, so none can return an unfiltered answer.  One selector per QUERY: the _each calls below.  -2 for a null h / s, a selector
+ * of another index, a stale selector. */
 int amd_ivf_search_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe, int coarse_mode,
                             float* D, int64_t* I);
 int amd_ivf_search_preassigned_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t k, size_t nprobe,
@@ -181,6 +182,42 @@ int amd_ivf_search_preassigned_selected_each(amd_ivf_t* h, const amd_ivf_selecto
                                              const float* coarse_dis, float* D, int64_t* I);
 int amd_ivf_search_resident_selected_each(amd_ivf_t* h, const amd_ivf_selector_t* const* sels, size_t nsel, const uint32_t* sel_of,
                                           size_t start, size_t n, size_t k, size_t nprobe, int coarse_mode, float* D, int64_t* I);
+/* The adaptive (error-bounded) search and its training branch over the members only: amd_ivf_search_adaptive, _search_adaptive_x and
+ * amd_ivf_train_samples (declared further down; every argument behind the selector is theirs) under one selector, and the resident
+ * adaptive search under a selector per QUERY (sels / nsel / sel_of as in the _each calls above; sel_of[i] belongs to query
+ * start + i).  D, I, my_nprobe and t_recalls -- for the training call D, I and raw -- are, bit for bit, what the unselected call of
+ * the same name returns on amd_ivf_subset(h, the same selector), when h's centroid table and tuner were set before the cut; row i of
+ * the _each call is what the single-selector call returns for query start + i under sels[sel_of[i]].  All arrays are indexed as the
+ * unselected calls index them: by absolute query id, my_nprobe zero on entry.  The stop rule is evaluated after every probe on the
+ * heap of the members; a probed list that holds no member counts as a probe, as an empty list of the subset does.  gt_D, when
+ * given, is the caller's FILTERED ground truth (amd_ivf_search_exact_selected returns it): profile bit 0 measures t_recalls against
+ * it, and the training call makes a tenant's raw traces from it.  The traces the rule reads are whatever the handle holds (set_tuner):
+ * training them per tenant is the caller's business.
+ * Option "selected_skip_empty" (default 1; read by these four calls only): a (query, list) pair whose list keeps nothing under the
+ * query's selector is planned as an absent probe -- no distance row, no scan -- from the per-list kept counts the selector holds on
+ * the device; 0 scans and masks such a list like any other.  The outputs are the same either way; amd_ivf_last_timing's scan bytes
+ * are not.
+ * Coarse tie order: these calls never patch a pass in flight (the patch moves distance rows, the masks are addressed by the rows'
+ * places); under option "coarse_ties" = 2 the queries concerned are searched again, under their own selectors.
+ * Not offered under a selector: the _pre forms, tickets (amd_ivf_submit_adaptive), the timed search, profile bit 1
+ * (overhead_profile: -2), search contexts made by amd_ivf_clone (-2, as for every call not on their list), and the class mirror
+ * under csrc/host.
+ * -2 before anything reaches the device, outputs untouched: a null h, selector or table, sel_of, require_acc, my_nprobe, t_recalls, D
+ * or I (the training call: gt_D, raw, D, I); a null x with n > 0; a stale selector or one of another index; nsel == 0 with n > 0, a
+ * null / foreign / stale entry of sels, sel_of[i] >= nsel; profile bit 1; a resident range that wraps or ends behind the resident
+ * queries. */
+int amd_ivf_search_adaptive_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t query_topk, float multipler,
+                                     float std_m, const float* require_acc, const float* gt_D, int profile, int coarse_mode,
+                                     uint64_t* my_nprobe, float* t_recalls, float* D, int64_t* I);
+int amd_ivf_search_adaptive_x_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t n, const float* x, size_t id_offset, size_t query_topk,
+                                       float multipler, float std_m, const float* require_acc, const float* gt_D, int profile,
+                                       int coarse_mode, uint64_t* my_nprobe, float* t_recalls, float* D, int64_t* I);
+int amd_ivf_search_adaptive_selected_each(amd_ivf_t* h, const amd_ivf_selector_t* const* sels, size_t nsel, const uint32_t* sel_of, size_t start,
+                                          size_t n, size_t query_topk, float multipler, float std_m, const float* require_acc,
+                                          const float* gt_D, int profile, int coarse_mode, uint64_t* my_nprobe, float* t_recalls, float* D,
+                                          int64_t* I);
+int amd_ivf_train_samples_selected(amd_ivf_t* h, const amd_ivf_selector_t* s, size_t start, size_t n, size_t max_topk, const float* gt_D,
+                                   size_t train_num, int coarse_mode, float* const* raw, float* D, int64_t* I);
 /* amd_ivf_range_search / _range_search_preassigned over the members only; the results are fetched with amd_ivf_range_results.  lims,
  * labels and distances are, bit for bit and in the same order, what the same call returns on amd_ivf_subset(h, the same selector).
  * ndis as above: the probed lists' entries as h holds them.  -2 as above, before anything is read. */
@@ -711,6 +748,9 @@ int amd_ivf_set_byte_codes(amd_ivf_t* h, int enable);
  *                     byte list pass (exact integers, no rescoring), 0 the general way for the whole call; independent of
  *                     "exact_float" / "exact_wide" (AUNCEL_AMD_EXACT_WIDE_BYTES is the environment's form).  Cannot change a
  *                     result
+ *   "selected_skip_empty"  the adaptive and training calls under a selector (amd_ivf_search_adaptive_selected & co): 1 a list    1
+ *                     that keeps nothing under a query's selector is planned as an absent probe, 0 it is scanned and masked
+ *                     (AUNCEL_AMD_SELECTED_SKIP_EMPTY is the environment's form).  Cannot change a result
  * amd_ivf_set_option(h, key, NAN) returns the key to "unset".  May be called while search contexts of the index are searching: a
  * search reads what shapes its launches once, when it starts, so the change takes effect with the searches that start after it. */
 int amd_ivf_set_option(amd_ivf_t* h, const char* key, double value);
