@@ -33,7 +33,7 @@ SYMBOLS = [
     "amd_ivf_range_search_preassigned", "amd_ivf_range_search", "amd_ivf_range_results",
     "amd_ivf_scan_arith",
     "amd_ivf_update_lists", "amd_ivf_remove_ids", "amd_ivf_last_update", "amd_ivf_layout_digest",
-    "amd_ivf_subset", "amd_ivf_last_subset",
+    "amd_ivf_subset", "amd_ivf_last_subset", "amd_ivf_concat", "amd_ivf_last_concat",
     "amd_ivf_selector_create", "amd_ivf_selector_destroy", "amd_ivf_selector_info",
     "amd_ivf_search_selected", "amd_ivf_search_preassigned_selected", "amd_ivf_search_resident_selected",
     "amd_ivf_selector_combine", "amd_ivf_range_search_selected", "amd_ivf_range_search_preassigned_selected",
@@ -48,6 +48,11 @@ SYMBOLS = [
     "amd_ivf_search_and_reconstruct", "amd_ivf_search_and_reconstruct_resident",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
+
+
+class Part(C.Structure):
+    """amd_ivf_part_t (include/auncel_amd.h: amd_ivf_concat)"""
+    _fields_ = [("h", C.c_void_p), ("begin", _u64p), ("end", _u64p), ("id_add", C.c_int64)]
 
 
 class EngineError(RuntimeError):
@@ -427,6 +432,41 @@ class Handle:
         """(entries looked at, entries kept, host-to-device bytes, device-to-host bytes) of the call that made this subset"""
         out = (C.c_uint64 * 4)()
         _chk(lib().amd_ivf_last_subset(self._h, out))
+        return tuple(int(v) for v in out)
+
+    # ---- resident indexes joined on the device (include/auncel_amd.h: amd_ivf_concat)
+    @staticmethod
+    def concat(parts):
+        """a read-only Handle whose list l is, over `parts` in order, a run of each part's list l.  A part is a Handle (taken whole,
+        ids unchanged) or a tuple (handle, begin, end, id_add): begin / end are nlist entry numbers each or None (0 / the list's
+        size), id_add (optional) is added to every id taken.  The centroids, the Auncel state and the options are parts[0]'s."""
+        parts = [p if isinstance(p, (tuple, list)) else (p,) for p in parts]
+        arr = (Part * max(len(parts), 1))()
+        keep = []  # (the run tables, as long as the call reads them)
+        for a, p in zip(arr, parts):
+            h, begin, end, id_add = (tuple(p) + (None, None, 0))[:4]
+            a.h = h._h.value if h is not None else None
+            for name, run in (("begin", begin), ("end", end)):
+                if run is not None:
+                    run = np.ascontiguousarray(run, dtype=np.uint64)
+                    if h is not None and run.shape != (h.nlist,):
+                        raise ValueError("a run table has one entry per list")
+                    keep.append(run)
+                    setattr(a, name, run.ctypes.data_as(_u64p))
+            a.id_add = int(id_add or 0)
+        first = parts[0][0] if parts else None
+        c = Handle.__new__(Handle)
+        c._h = C.c_void_p()
+        _chk(lib().amd_ivf_concat(arr if parts else None, C.c_size_t(len(parts)), C.byref(c._h)))
+        c.d, c.nlist, c.metric, c.device = first.d, first.nlist, first.metric, first.device
+        if hasattr(first, "max_topk"):
+            c.max_topk = first.max_topk
+        return c
+
+    def last_concat(self):
+        """(entries taken, parts, host-to-device bytes, device-to-host bytes) of the call that made this joined index"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_last_concat(self._h, out))
         return tuple(int(v) for v in out)
 
     # ---- search under an id selector (include/auncel_amd.h: amd_ivf_selector_create)

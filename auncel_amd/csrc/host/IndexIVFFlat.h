@@ -111,6 +111,21 @@ struct IndexIVFFlatSubset : Index {
 
     IndexIVFFlatSubset(const IndexIVFFlat& src, int subset_type, idx_t a1, idx_t a2);
     IndexIVFFlatSubset(const IndexIVFFlat& src, const IDSelector& sel);
+    /// The inverse: an index JOINED on the device from lists that are resident there (include/auncel_amd.h: amd_ivf_concat).  List l
+    /// holds, over the parts in order, entries [begin[l], end[l]) of each part's list l with add_id added to their ids -- every part
+    /// whole is IndexIVF::merge_from without the host, two parts with runs are a step of ivflib::SlidingIndexWindowDevice (IVFlib.h).
+    /// A part is an IndexIVFFlat or an IndexIVFFlatSubset; no part is changed and each may be destroyed afterwards.  The quantizer,
+    /// interdis_cem, the tuner's traces, nprobe and coarse_mode are part 0's; the engine refuses parts of other shapes or centroids.
+    struct Part {
+        const IndexIVFFlat* flat = nullptr;  // one of the two
+        const IndexIVFFlatSubset* subset = nullptr;
+        std::vector<uint64_t> begin, end;  // nlist entries each, or empty: 0 / the list's size
+        idx_t add_id = 0;
+        Part(const IndexIVFFlat* ix, idx_t add_id_ = 0) : flat(ix), add_id(add_id_) {}
+        Part(const IndexIVFFlatSubset* ix, idx_t add_id_ = 0) : subset(ix), add_id(add_id_) {}
+    };
+    explicit IndexIVFFlatSubset(const std::vector<Part>& parts);
+    size_t list_size(size_t list_no) const;
     IndexIVFFlatSubset(const IndexIVFFlatSubset&) = delete;
     IndexIVFFlatSubset& operator=(const IndexIVFFlatSubset&) = delete;
     ~IndexIVFFlatSubset() override;

@@ -26,6 +26,7 @@
 #include "FaissAssert.h"
 #include "Heap.h"
 #include "IVF_pro.h"
+#include "IVFlib.h"
 #include "IndexFlat.h"
 #include "IndexIVF.h"
 #include "IndexIVFFlat.h"
@@ -1457,9 +1458,134 @@ IndexIVFFlatSubset::IndexIVFFlatSubset(const IndexIVFFlat& src, const IDSelector
     }
 }
 
+IndexIVFFlatSubset::IndexIVFFlatSubset(const std::vector<Part>& parts) : Index() {
+    FAISS_THROW_IF_NOT_MSG(!parts.empty(), "a joined index needs at least one part");
+    std::vector<amd_ivf_part_t> ps(parts.size());
+    for (size_t j = 0; j < parts.size(); j++) {
+        const Part& p = parts[j];
+        FAISS_THROW_IF_NOT_MSG((p.flat != nullptr) != (p.subset != nullptr), "a part is one IndexIVFFlat or one IndexIVFFlatSubset");
+        const size_t nl = p.flat ? p.flat->nlist : p.subset->nlist;
+        FAISS_THROW_IF_NOT_MSG((p.begin.empty() || p.begin.size() == nl) && (p.end.empty() || p.end.size() == nl),
+                               "a part's runs have one entry per list");
+        if (p.flat) {
+            FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(p.flat) == nullptr, "a join with an IndexIVFFlatDedup is not implemented");
+            FAISS_THROW_IF_NOT_MSG(p.flat->is_trained, "a part is not trained");
+        }
+        ps[j].h = p.flat ? p.flat->engine() : p.subset->engine();  // (engine() syncs a flat part: centroids, lists or their journal)
+        ps[j].begin = p.begin.empty() ? nullptr : p.begin.data();
+        ps[j].end = p.end.empty() ? nullptr : p.end.data();
+        ps[j].id_add = (int64_t)p.add_id;
+    }
+    const Part& p0 = parts[0];
+    d = p0.flat ? p0.flat->d : p0.subset->d;
+    metric_type = p0.flat ? p0.flat->metric_type : p0.subset->metric_type;
+    is_trained = true;
+    amd_device = p0.flat ? p0.flat->amd_device : p0.subset->amd_device;
+    nlist = p0.flat ? p0.flat->nlist : p0.subset->nlist;
+    nprobe = p0.flat ? p0.flat->nprobe : p0.subset->nprobe;
+    coarse_mode = p0.flat ? p0.flat->coarse_mode : p0.subset->coarse_mode;
+    AMD(amd_ivf_concat(ps.data(), ps.size(), &gpu_));
+    size_t nt = 0;
+    AMD(amd_ivf_ntotal(gpu_, &nt));
+    ntotal = (idx_t)nt;
+}
+
+size_t IndexIVFFlatSubset::list_size(size_t list_no) const {
+    size_t n = 0;
+    AMD(amd_ivf_list_size(gpu_, list_no, &n));
+    return n;
+}
+
 IndexIVFFlatSubset::~IndexIVFFlatSubset() {
     if (gpu_) amd_ivf_destroy(gpu_);
 }
+
+// ------------------------------------------------------------------------------------- ivflib (IVFlib.h)
+namespace ivflib {
+
+namespace {
+// what the checks compare: an IndexIVFFlatSubset is read as the IndexIVFFlat it was made from
+struct IvfShape {
+    bool ivf = false, flat_lists = false;
+    size_t nlist = 0, code_size = 0;
+};
+IvfShape shape_of(const Index* index) {
+    IvfShape s;
+    if (const IndexIVFFlatSubset* sub = dynamic_cast<const IndexIVFFlatSubset*>(index)) {
+        s.ivf = s.flat_lists = true;
+        s.nlist = sub->nlist;
+        s.code_size = sizeof(float) * (size_t)sub->d;
+    } else if (const IndexIVF* ivf = dynamic_cast<const IndexIVF*>(index)) {
+        s.ivf = true;
+        s.flat_lists = typeid(*ivf) == typeid(IndexIVFFlat);
+        s.nlist = ivf->nlist;
+        s.code_size = ivf->code_size;
+    }
+    return s;
+}
+}  // namespace
+
+void check_compatible_for_merge(const Index* index0, const Index* index1) {
+    FAISS_THROW_IF_NOT(index0 && index1);
+    FAISS_THROW_IF_NOT(index0->d == index1->d && index0->metric_type == index1->metric_type);
+    const IvfShape s0 = shape_of(index0), s1 = shape_of(index1);
+    FAISS_THROW_IF_NOT(s0.ivf && s1.ivf);
+    FAISS_THROW_IF_NOT(s1.nlist == s0.nlist);
+    FAISS_THROW_IF_NOT(s1.code_size == s0.code_size);
+    FAISS_THROW_IF_NOT_MSG(s0.flat_lists && s1.flat_lists, "can only merge indexes of the same type");
+}
+
+SlidingIndexWindowDevice::SlidingIndexWindowDevice(const IndexIVFFlat* index) : nlist(index->nlist), first_(index) {
+    FAISS_THROW_IF_NOT_MSG(typeid(*index) == typeid(IndexIVFFlat), "only supports an IndexIVFFlat");
+    sizes.resize(nlist);
+    cur_.reset(new IndexIVFFlatSubset(std::vector<IndexIVFFlatSubset::Part>{IndexIVFFlatSubset::Part(index)}));
+}
+
+void SlidingIndexWindowDevice::step(const Index* sub_index, bool remove_oldest) {
+    FAISS_THROW_IF_NOT_MSG(!remove_oldest || n_slice > 0, "cannot remove slice: there is none");
+    typedef IndexIVFFlatSubset::Part Part;
+    std::vector<Part> parts;
+    if (remove_oldest) {  // the window without the prefix its oldest slice gave every list
+        Part keep(cur_.get());
+        keep.begin.resize(nlist);
+        for (size_t i = 0; i < nlist; i++) keep.begin[i] = sizes[i][0];
+        parts.push_back(keep);
+    } else {
+        parts.push_back(Part(cur_.get()));
+    }
+    if (sub_index) {
+        check_compatible_for_merge(first_, sub_index);
+        if (const IndexIVFFlatSubset* sub = dynamic_cast<const IndexIVFFlatSubset*>(sub_index)) parts.push_back(Part(sub));
+        else parts.push_back(Part(dynamic_cast<const IndexIVFFlat*>(sub_index)));
+    } else if (!remove_oldest) {
+        FAISS_THROW_MSG("nothing to do???");
+    }
+    std::unique_ptr<IndexIVFFlatSubset> next(new IndexIVFFlatSubset(parts));
+    next->nprobe = cur_->nprobe;  // (what the caller set on the window stays)
+    next->coarse_mode = cur_->coarse_mode;
+    // the reference's three branches, on the table alone
+    if (remove_oldest && sub_index) {
+        for (size_t i = 0; i < nlist; i++) {
+            std::vector<size_t>& sizesi = sizes[i];
+            const size_t amount_to_remove = sizesi[0];
+            for (int j = 0; j + 1 < n_slice; j++) sizesi[j] = sizesi[j + 1] - amount_to_remove;
+            sizesi[n_slice - 1] = next->list_size(i);
+        }
+    } else if (sub_index) {
+        for (size_t i = 0; i < nlist; i++) sizes[i].push_back(next->list_size(i));
+        n_slice++;
+    } else {
+        for (size_t i = 0; i < nlist; i++) {
+            const size_t amount_to_remove = sizes[i][0];
+            for (int j = 0; j + 1 < n_slice; j++) sizes[i][j] = sizes[i][j + 1] - amount_to_remove;
+            sizes[i].pop_back();
+        }
+        n_slice--;
+    }
+    cur_.swap(next);  // (the old window goes when `next` does: after the new one exists)
+}
+
+}  // namespace ivflib
 
 void IndexIVFFlatSubset::train(idx_t, const float*) { FAISS_THROW_MSG("a subset index is read-only: train its source"); }
 void IndexIVFFlatSubset::add(idx_t, const float*) { FAISS_THROW_MSG("a subset index is read-only: add to its source and cut again"); }

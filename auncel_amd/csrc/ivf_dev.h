@@ -180,6 +180,49 @@ __device__ __forceinline__ uint32_t list_of_block(const uint64_t* block_off, uin
     return lo;
 }
 
+// largest l < nlist with off[l] >> shift <= x (the list of entry / block x; empty lists share their successor's offset)
+__device__ __forceinline__ uint32_t list_of(const uint64_t* __restrict__ off, uint32_t nlist, uint64_t x, int shift) {
+    uint32_t lo = 0, hi = nlist;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((off[mid] >> shift) <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The IntRange of the rows a kernel copies, riding on its loads (subset_compact_kernel, concat_rows_kernel): every lane looks at
+// the values it moves; commit, called by whole waves, reduces them and moves range = {some value is not an integer of magnitude
+// <= 4095, order key of the smallest value, of the largest, -} (launch_subset_compact) by three integer atomics
+struct RangeWatch {
+    bool bad = false;
+    float lo = 0.f, hi = 0.f;
+    __device__ __forceinline__ void look(float v) {
+        bad |= !(v >= -4095.f && v <= 4095.f && v == truncf(v));
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+    }
+    __device__ __forceinline__ void look(const float4& v) {
+        look(v.x);
+        look(v.y);
+        look(v.z);
+        look(v.w);
+    }
+    __device__ __forceinline__ void commit(uint32_t* range, int lane) const {
+        // smaller key <=> smaller value; -0 counts as 0, as in a comparison of floats
+        uint32_t klo = ~fkey(lo + 0.f), khi = fkey(hi + 0.f);
+        klo = ~wave_max_u32(klo);
+        khi = wave_max_u32(khi);
+        const bool any_bad = __ballot(bad) != 0;
+        if (lane == 0) {
+            // every wave moves the three results one way only: a wave that cannot move them leaves them alone
+            if (any_bad && __hip_atomic_load(&range[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(&range[0], 1u);
+            if (klo < __hip_atomic_load(&range[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&range[1], klo);
+            if (khi > __hip_atomic_load(&range[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&range[2], khi);
+        }
+    }
+};
+
 template <int... I, class F> __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
     (f(std::integral_constant<int, I>{}), ...);
 }

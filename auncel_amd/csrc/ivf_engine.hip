@@ -364,8 +364,10 @@ struct amd_ivf {
     uint64_t last_update[4] = {0, 0, 0, 0};  // amd_ivf_last_update
     // made by amd_ivf_subset (ivf_subset.hip): an index of its own whose lists were cut from another's on the device.  Read-only: it
     // keeps no host copy of the rows (h_codes / h_ids stay empty; sizes come from h_list_off, amd_ivf_get_list reads the device)
+    // An index joined from others' lists (amd_ivf_concat, ivf_concat.hip) is in the same state: made on the device, no host rows.
     bool is_subset = false;
     uint64_t last_subset[4] = {0, 0, 0, 0};  // amd_ivf_last_subset
+    uint64_t last_concat[4] = {0, 0, 0, 0};  // amd_ivf_last_concat
     PinnedBuf p_upd;
     DevBuf d_upd;
     DevBuf d_codes, d_ids, d_list_off, d_centroids, d_centroid_norms;
@@ -5542,34 +5544,16 @@ uint64_t membership_pass(amd_ivf* h, int type, int64_t a1, int64_t a2, const voi
                          st);
     return h2d;
 }
-}  // namespace
 
-extern "C" {
-
-// ------------------------------------------------------------------------------------ subset of a resident index
-// A new index on h's device whose list l holds the members of h's list l in h's order, cut in HBM (ivf_subset.hip): the device then
-// holds what amd_ivf_set_lists of the filtered lists would have made.  What crosses PCIe: the selector in, the SLICE runs in, the
-// offsets and the block table out, 16 bytes of value range each way.
-int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const void* sel, size_t nsel, amd_ivf_t** out) {
-    API_BEGIN
-    if (!h || !out) throw EngineError("null argument");
-    *out = nullptr;
-    OWNER_ONLY(h);
-    const std::string bad = selector_args_error("subset", subset_type, a1, a2, sel, nsel, (uint64_t)h->ntotal);
-    if (!bad.empty()) throw EngineError(bad);
-    if (tickets_out(h)) throw EngineError("tickets are still out: wait for them before cutting a subset");
-    use_device(h);
-    upload_lists(h);  // (a pending journal or dirty lists: the subset sees every amd_ivf_add made before the call)
-    std::lock_guard<std::mutex> lock(h->upload_mu);
+// An index made on the device from h's lists (amd_ivf_subset) or from h's and others' (amd_ivf_concat), before it has lists of its
+// own: h's shape and options, a stream of its own, and copies of the quantizer and the Auncel state -- device to device, enqueued on
+// the new stream, the small host mirrors host to host.  Read-only, no host rows (amd_ivf::is_subset).
+std::unique_ptr<amd_ivf> derived_index(const amd_ivf* h) {
     const size_t nlist = h->nlist;
-    const int d = h->d, dpad = h->dpad;
-    const uint64_t nt = h->h_list_off[nlist];
-    for (size_t l = 0; l < nlist; l++)
-        if ((h->h_list_off[l + 1] - h->h_list_off[l]) >> 32) throw EngineError("subset: list too long");
     std::unique_ptr<amd_ivf> s(new amd_ivf);
     s->is_subset = true;
-    s->d = d;
-    s->dpad = dpad;
+    s->d = h->d;
+    s->dpad = h->dpad;
     s->nlist = nlist;
     s->metric = h->metric;
     s->device = h->device;
@@ -5585,15 +5569,13 @@ int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const 
     s->list_range.resize(nlist);
     s->h_list_off.assign(nlist + 1, 0);
     hipStream_t st = s->stream;
-    uint64_t h2d = 0, d2h = 0;
     auto d2d = [&](DevBuf& dst, const DevBuf& src, size_t bytes) {
         if (!src.p || !bytes) return;
         dst.ensure(bytes);
         HIP_CHECK(hipMemcpyAsync(dst.p, src.p, bytes, hipMemcpyDeviceToDevice, st));
     };
-    // the quantizer and the Auncel state: device to device, the small host mirrors host to host
     if (h->have_centroids) {
-        d2d(s->d_centroids, h->d_centroids, nlist * dpad * sizeof(float));
+        d2d(s->d_centroids, h->d_centroids, nlist * h->dpad * sizeof(float));
         d2d(s->d_centroid_norms, h->d_centroid_norms, nlist * sizeof(float));
         d2d(s->d_cinfo, h->d_cinfo, 16);
         s->h_centroids = h->h_centroids;
@@ -5617,6 +5599,76 @@ int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const 
         s->tuner_trace_total = h->tuner_trace_total;
         s->have_tuner = true;
     }
+    return s;
+}
+
+// ... and once its rows, ids, offsets and block table are in place (h_list_off / h_block_off are their host copies) and db_range is
+// the range of the `kept` rows: what upload_lists derives from the lists, and the byte fragments where the rows qualify -- byte
+// eligibility is decided over the values the index holds, whatever its sources were.  The other copies are left to the first search
+// that wants them.  Returns the bytes that crossed to the device.
+uint64_t finish_derived_index(amd_ivf* s, uint64_t kept) {
+    const size_t nlist = s->nlist;
+    hipStream_t st = s->stream;
+    uint64_t h2d = 0;
+    if (kept == 0) {  // an index with empty lists, as amd_ivf_set_lists of none
+        s->h_list_off.assign(nlist + 1, 0);
+        s->d_block_off.release();
+        s->db_range = IntRange();
+        s->ntotal = 0;
+        s->lists_dirty = true;
+        upload_lists(s);
+        h2d += (nlist + 1) * 8;
+    } else {
+        s->ntotal = kept;
+        s->have_codes8 = s->allow_bytes && s->db_range.bytes() && (double)s->d * 255.0 * 255.0 < 2147483648.0;
+        s->frag32_possible = s->allow_filter && kept < 0xffffffffull;
+        double s1 = 0, s2 = 0;
+        for (size_t l = 0; l < nlist; l++) {
+            const double len = (double)(s->h_list_off[l + 1] - s->h_list_off[l]);
+            s1 += len;
+            s2 += len * len;
+        }
+        s->probed_len = s1 > 0 ? s2 / s1 : 0.0;
+        if (s->have_codes8) {
+            const uint64_t nblk = s->h_block_off[nlist];
+            s->d_frag.ensure(nblk * mfma_ksteps(s->d) * 1024);
+            s->d_cy.ensure(nblk * 32 * sizeof(int32_t));
+            launch_frag_from_f32(s->d_codes.as<float>(), s->d_list_off.as<uint64_t>(), s->d_block_off.as<uint64_t>(), (uint32_t)nlist, nblk, s->d,
+                                 s->dpad, s->metric, s->d_frag.as<uint8_t>(), s->d_cy.as<int32_t>(), st);
+        }
+        HIP_CHECK(stream_sync(st));
+        s->lists_dirty = false;
+    }
+    HIP_CHECK(stream_sync(st));
+    return h2d;
+}
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------ subset of a resident index
+// A new index on h's device whose list l holds the members of h's list l in h's order, cut in HBM (ivf_subset.hip): the device then
+// holds what amd_ivf_set_lists of the filtered lists would have made.  What crosses PCIe: the selector in, the SLICE runs in, the
+// offsets and the block table out, 16 bytes of value range each way.
+int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const void* sel, size_t nsel, amd_ivf_t** out) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("null argument");
+    *out = nullptr;
+    OWNER_ONLY(h);
+    const std::string bad = selector_args_error("subset", subset_type, a1, a2, sel, nsel, (uint64_t)h->ntotal);
+    if (!bad.empty()) throw EngineError(bad);
+    if (tickets_out(h)) throw EngineError("tickets are still out: wait for them before cutting a subset");
+    use_device(h);
+    upload_lists(h);  // (a pending journal or dirty lists: the subset sees every amd_ivf_add made before the call)
+    std::lock_guard<std::mutex> lock(h->upload_mu);
+    const size_t nlist = h->nlist;
+    const int dpad = h->dpad;
+    const uint64_t nt = h->h_list_off[nlist];
+    for (size_t l = 0; l < nlist; l++)
+        if ((h->h_list_off[l + 1] - h->h_list_off[l]) >> 32) throw EngineError("subset: list too long");
+    std::unique_ptr<amd_ivf> s = derived_index(h);  // (the quantizer and the Auncel state come along)
+    hipStream_t st = s->stream;
+    uint64_t h2d = 0, d2h = 0;
     uint64_t kept = 0;
     if (nt > 0) {
         const uint64_t nwords = h->h_block_off[nlist] / 2;
@@ -5659,36 +5711,7 @@ int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const 
             s->db_range.hi = subset_range_value(rg[2]);
         }
     }
-    if (kept == 0) {  // an index with empty lists, as amd_ivf_set_lists of none
-        s->h_list_off.assign(nlist + 1, 0);
-        s->d_block_off.release();
-        s->db_range = IntRange();
-        s->ntotal = 0;
-        s->lists_dirty = true;
-        upload_lists(s.get());
-        h2d += (nlist + 1) * 8;
-    } else {  // (what upload_lists derives from the lists)
-        s->ntotal = kept;
-        s->have_codes8 = s->allow_bytes && s->db_range.bytes() && (double)d * 255.0 * 255.0 < 2147483648.0;
-        s->frag32_possible = s->allow_filter && kept < 0xffffffffull;
-        double s1 = 0, s2 = 0;
-        for (size_t l = 0; l < nlist; l++) {
-            const double len = (double)(s->h_list_off[l + 1] - s->h_list_off[l]);
-            s1 += len;
-            s2 += len * len;
-        }
-        s->probed_len = s1 > 0 ? s2 / s1 : 0.0;
-        if (s->have_codes8) {
-            const uint64_t nblk = s->h_block_off[nlist];
-            s->d_frag.ensure(nblk * mfma_ksteps(d) * 1024);
-            s->d_cy.ensure(nblk * 32 * sizeof(int32_t));
-            launch_frag_from_f32(s->d_codes.as<float>(), s->d_list_off.as<uint64_t>(), s->d_block_off.as<uint64_t>(), (uint32_t)nlist, nblk, d, dpad,
-                                 s->metric, s->d_frag.as<uint8_t>(), s->d_cy.as<int32_t>(), st);
-        }
-        HIP_CHECK(stream_sync(st));
-        s->lists_dirty = false;
-    }
-    HIP_CHECK(stream_sync(st));
+    h2d += finish_derived_index(s.get(), kept);
     s->last_subset[0] = nt;
     s->last_subset[1] = kept;
     s->last_subset[2] = h2d;
@@ -5701,6 +5724,130 @@ int amd_ivf_last_subset(amd_ivf_t* sub, uint64_t out[4]) {
     API_BEGIN
     if (!sub || !out) throw EngineError("null argument");
     for (int i = 0; i < 4; i++) out[i] = ix(sub)->last_subset[i];
+    API_END
+}
+
+// ------------------------------------------------------------------------------------ resident indexes joined
+// A new index on the parts' device whose list l is, over the parts in order, entries [begin[l], end[l]) of each part's list l, copied
+// in HBM (ivf_concat.hip): the device then holds what amd_ivf_set_lists of those lists would have made.  Every size is on the host, so
+// the result's tables are made here and go in by one upload; what crosses PCIe is O(nparts * nlist) numbers and no row.
+int amd_ivf_concat(const amd_ivf_part_t* parts, size_t nparts, amd_ivf_t** out) {
+    API_BEGIN
+    if (!parts || !out) throw EngineError("null argument");
+    *out = nullptr;
+    if (nparts == 0 || nparts > 64) throw EngineError("concat: the number of parts must be 1 .. 64");
+    for (size_t j = 0; j < nparts; j++) {
+        if (!parts[j].h) throw EngineError("concat: part " + std::to_string(j) + " is null");
+        OWNER_ONLY(parts[j].h);
+    }
+    amd_ivf* p0 = parts[0].h;
+    const size_t nlist = p0->nlist;
+    const int dpad = p0->dpad;
+    // a part's list sizes as the host knows them: a pending amd_ivf_add is in them already
+    auto size_of = [](const amd_ivf* h, size_t l) -> uint64_t { return h->is_subset ? h->h_list_off[l + 1] - h->h_list_off[l] : h->h_ids[l].size(); };
+    for (size_t j = 0; j < nparts; j++) {
+        amd_ivf* h = parts[j].h;
+        const std::string who = "concat: part " + std::to_string(j);
+        if (h->device != p0->device || h->d != p0->d || h->nlist != nlist || h->metric != p0->metric)
+            throw EngineError(who + " differs from part 0 in device, d, nlist or metric");
+        if (tickets_out(h)) throw EngineError(who + ": tickets are still out: wait for them before joining");
+        if (p0->have_centroids && !h->have_centroids) throw EngineError(who + " has no centroids and part 0 has");
+        if (p0->have_centroids && (h->h_centroids.size() != p0->h_centroids.size() ||
+                                   memcmp(h->h_centroids.data(), p0->h_centroids.data(), p0->h_centroids.size() * sizeof(float)) != 0))
+            throw EngineError(who + ": the centroids are not those of part 0");
+        for (size_t l = 0; l < nlist; l++) {
+            const uint64_t size = size_of(h, l), b = parts[j].begin ? parts[j].begin[l] : 0, e = parts[j].end ? parts[j].end[l] : size;
+            if (b > e || e > size)
+                throw EngineError(who + ", list " + std::to_string(l) + ": the run [" + std::to_string(b) + ", " + std::to_string(e) +
+                                  ") is not inside the list's " + std::to_string(size) + " entries");
+        }
+    }
+    // the joined lists' offsets and block table by upload_lists' rule; per part where its run of every list starts inside its own lists
+    // (filled below, from the offsets its upload leaves) and how far into the joined list the parts up to it reach
+    std::vector<uint64_t> tab((2 + 2 * nparts) * (nlist + 1) + 3 * nparts, 0);
+    uint64_t* t_off = tab.data();
+    uint64_t* t_boff = t_off + (nlist + 1);
+    uint64_t* t_src = t_boff + (nlist + 1);
+    uint64_t* t_cum = t_src + nparts * nlist;
+    uint64_t* t_parts = t_cum + nparts * nlist;
+    for (size_t l = 0; l < nlist; l++) {
+        uint64_t len = 0;
+        for (size_t j = 0; j < nparts; j++) {
+            const uint64_t b = parts[j].begin ? parts[j].begin[l] : 0, e = parts[j].end ? parts[j].end[l] : size_of(parts[j].h, l);
+            len += e - b;
+            if (len >> 32) throw EngineError("concat: the joined list " + std::to_string(l) + " would hold 2^32 entries or more");
+            t_cum[j * nlist + l] = len;
+        }
+        t_off[l + 1] = t_off[l] + len;
+        t_boff[l + 1] = t_boff[l] + mfma_list_blocks(len);
+    }
+    const uint64_t nt = t_off[nlist];
+    if (nt >= (1ull << SCAN_VB_BITS)) throw EngineError("too many vectors for one index");
+    // ---- the device from here on
+    use_device(p0);
+    std::vector<amd_ivf*> distinct;
+    for (size_t j = 0; j < nparts; j++)
+        if (std::find(distinct.begin(), distinct.end(), parts[j].h) == distinct.end()) distinct.push_back(parts[j].h);
+    std::sort(distinct.begin(), distinct.end(), std::less<amd_ivf*>());  // (one locking order for every caller)
+    for (amd_ivf* h : distinct) upload_lists(h);  // (a pending journal or dirty lists: the join sees every amd_ivf_add made before the call)
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (amd_ivf* h : distinct) locks.emplace_back(h->upload_mu);
+    for (size_t j = 0; j < nparts; j++) {
+        const amd_ivf* h = parts[j].h;
+        for (size_t l = 0; l < nlist; l++) {
+            if (h->h_list_off[l + 1] - h->h_list_off[l] != size_of(h, l)) throw std::runtime_error("concat: a part's device lists are not its host lists");
+            t_src[j * nlist + l] = h->h_list_off[l] + (parts[j].begin ? parts[j].begin[l] : 0);
+        }
+        t_parts[3 * j] = (uint64_t)(uintptr_t)h->d_codes.p;
+        t_parts[3 * j + 1] = (uint64_t)(uintptr_t)h->d_ids.p;
+        t_parts[3 * j + 2] = (uint64_t)parts[j].id_add;
+    }
+    static_assert(sizeof(ConcatPart) == 24, "ConcatPart travels as three 64-bit words");
+    std::unique_ptr<amd_ivf> s = derived_index(p0);  // (the quantizer, the Auncel state and the options are part 0's)
+    hipStream_t st = s->stream;
+    uint64_t h2d = 0, d2h = 0;
+    if (nt > 0) {
+        DevBuf b_tab, b_range;
+        b_tab.ensure(tab.size() * 8);
+        HIP_CHECK(hipMemcpyAsync(b_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+        h2d += tab.size() * 8;
+        const uint64_t* d_tab = b_tab.as<uint64_t>();
+        s->d_list_off.ensure((nlist + 1) * 8);
+        s->d_block_off.ensure((nlist + 1) * 8);
+        HIP_CHECK(hipMemcpyAsync(s->d_list_off.p, d_tab, (nlist + 1) * 8, hipMemcpyDeviceToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(s->d_block_off.p, d_tab + (nlist + 1), (nlist + 1) * 8, hipMemcpyDeviceToDevice, st));
+        s->h_list_off.assign(t_off, t_off + nlist + 1);
+        s->h_block_off.assign(t_boff, t_boff + nlist + 1);
+        s->d_codes.ensure(nt * dpad * sizeof(float));
+        s->d_ids.ensure(nt * sizeof(int64_t));
+        uint32_t rg[4] = {0, subset_range_key(0.f), subset_range_key(0.f), 0};
+        b_range.ensure(16);
+        HIP_CHECK(hipMemcpyAsync(b_range.p, rg, 16, hipMemcpyHostToDevice, st));
+        launch_concat_rows(reinterpret_cast<const ConcatPart*>(d_tab + (t_parts - t_off)), (uint32_t)nparts, d_tab + (t_src - t_off),
+                           d_tab + (t_cum - t_off), s->d_list_off.as<uint64_t>(), (uint32_t)nlist, nt, dpad, s->d_codes.as<float>(),
+                           s->d_ids.as<int64_t>(), b_range.as<uint32_t>(), st);
+        HIP_CHECK(hipMemcpyAsync(rg, b_range.p, 16, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(stream_sync(st));
+        h2d += 16;
+        d2h += 16;
+        // byte eligibility over the values TAKEN: a window that drops its only non-byte row comes back byte-coded
+        s->db_range.ok = rg[0] == 0;
+        s->db_range.lo = subset_range_value(rg[1]);
+        s->db_range.hi = subset_range_value(rg[2]);
+    }
+    h2d += finish_derived_index(s.get(), nt);
+    s->last_concat[0] = nt;
+    s->last_concat[1] = nparts;
+    s->last_concat[2] = h2d;
+    s->last_concat[3] = d2h;
+    *out = s.release();
+    API_END
+}
+
+int amd_ivf_last_concat(amd_ivf_t* joined, uint64_t out[4]) {
+    API_BEGIN
+    if (!joined || !out) throw EngineError("null argument");
+    for (int i = 0; i < 4; i++) out[i] = ix(joined)->last_concat[i];
     API_END
 }
 

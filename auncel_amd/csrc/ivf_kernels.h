@@ -734,6 +734,19 @@ void launch_subset_offsets(const uint32_t* count, const uint64_t* block_off, uin
 void launch_subset_compact(const float* old_codes, const int64_t* old_ids, const uint64_t* old_off, const uint64_t* old_block_off, uint32_t nlist,
                            uint64_t nwords, const uint64_t* mask, const uint32_t* rank_base, const uint64_t* new_off, int dpad, float* codes,
                            int64_t* ids, uint32_t* range, hipStream_t s);
+// ---------------------------------------------------------------------------- resident indexes joined (ivf_concat.hip)
+// One part of a join (include/auncel_amd.h: amd_ivf_concat): the rows (stride dpad) and ids of an index that is resident on the same
+// device, and what is added to every id taken from it
+struct ConcatPart {
+    const float* codes;
+    const int64_t* ids;
+    int64_t id_add;
+};
+// Rows and ids of the joined layout: entry p of list l comes from the first part j with cum[j * nlist + l] > p -- cum: the entries
+// parts 0 .. j give list l together -- and is that part's row src_start[j * nlist + l] + (p - cum[(j - 1) * nlist + l]), its id plus
+// the part's id_add.  Every array is device memory; range as launch_subset_compact's, over the rows taken.
+void launch_concat_rows(const ConcatPart* parts, uint32_t nparts, const uint64_t* src_start, const uint64_t* cum, const uint64_t* new_off,
+                        uint32_t nlist, uint64_t nt, int dpad, float* codes, int64_t* ids, uint32_t* range, hipStream_t s);
 // ---------------------------------------------------------------------------- stored vectors back (ivf_reconstruct.hip)
 // table[id - lo] = max(table[id - lo], list << 32 | offset) for every stored entry whose id lies in [lo, lo + n) (nt entries, list_off:
 // nlist + 1); the caller starts the table at -1 in every slot and counts at {0, 0}: counts[0] += entries outside the window,

@@ -141,13 +141,7 @@ __global__ __launch_bounds__(256) void subset_compact_kernel(const float* __rest
     const uint32_t nsteps = (uint32_t)dpad >> 2, total = nrows * nsteps;
     const float4* src4 = reinterpret_cast<const float4*>(old_codes);
     float4* dst4 = reinterpret_cast<float4*>(codes) + dst0 * nsteps;
-    bool bad = false;
-    float lo = 0.f, hi = 0.f;
-    auto look = [&](float v) {
-        bad |= !(v >= -4095.f && v <= 4095.f && v == truncf(v));
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-    };
+    RangeWatch watch;
     for (uint32_t i0 = lane; i0 < total; i0 += 4 * 64) {
         float4 v[4];
 #pragma unroll
@@ -163,23 +157,10 @@ __global__ __launch_bounds__(256) void subset_compact_kernel(const float* __rest
         for (int u = 0; u < 4; u++) {
             const uint32_t i = i0 + u * 64;
             if (i < total) dst4[i] = v[u];
-            look(v[u].x);
-            look(v[u].y);
-            look(v[u].z);
-            look(v[u].w);
+            watch.look(v[u]);
         }
     }
-    // smaller key <=> smaller value; -0 counts as 0, as in a comparison of floats
-    uint32_t klo = ~fkey(lo + 0.f), khi = fkey(hi + 0.f);
-    klo = ~wave_max_u32(klo);
-    khi = wave_max_u32(khi);
-    const bool any_bad = __ballot(bad) != 0;
-    if (lane == 0) {
-        // every word moves the three results one way only: a wave that cannot move them leaves them alone
-        if (any_bad && __hip_atomic_load(&range[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(&range[0], 1u);
-        if (klo < __hip_atomic_load(&range[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&range[1], klo);
-        if (khi > __hip_atomic_load(&range[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&range[2], khi);
-    }
+    watch.commit(range, lane);
 }
 
 }  // namespace

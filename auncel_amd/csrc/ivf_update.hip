@@ -7,24 +7,13 @@
 
 #include <algorithm>
 
-#include "ivf_kernels.h"
+#include "ivf_dev.h"
 
 namespace amdivf {
 
 namespace {
 
-constexpr int ROWS_PER_WG = 64;
-
-// largest l < nlist with off[l] >> shift <= x (the list of entry / block x; empty lists share their successor's offset)
-__device__ __forceinline__ uint32_t list_of(const uint64_t* __restrict__ off, uint32_t nlist, uint64_t x, int shift) {
-    uint32_t lo = 0, hi = nlist;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if ((off[mid] >> shift) <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+constexpr int ROWS_PER_WG = 64;  // (list_of: ivf_dev.h)
 
 // a workgroup per 64 rows of the new layout: one thread a row finds where the row comes from, then the workgroup copies the rows,
 // four 16-byte pieces in flight per thread

@@ -119,6 +119,36 @@ int amd_ivf_subset(amd_ivf_t* h, int subset_type, int64_t a1, int64_t a2, const 
 /* {entries looked at, entries kept, host-to-device bytes, device-to-host bytes} of the call that made `sub` */
 int amd_ivf_last_subset(amd_ivf_t* sub, uint64_t out[4]);
 
+/* ---- resident indexes joined on the device ---------------------------------------------
+ * The inverse of amd_ivf_subset, and what ivflib::merge_into and SlidingIndexWindow::step  [IVFlib.cpp:77-88, 190-243] do to host
+ * lists, applied to indexes that are resident in HBM: *out is an index of its own on the parts' device -- same d, nlist, metric --
+ * whose list l holds, for j = 0 .. nparts - 1 in order, entries [begin_j[l], end_j[l]) of part j's list l in that part's order, their
+ * ids plus id_add_j.  A merge is every part taken whole; a step of a sliding window is two parts: the window without the prefix
+ * its oldest slice gave every list, then the new slice.  No list row crosses PCIe: every size is on the host, so the host makes the
+ * joined offsets and per part a table of source starts and of cumulative lengths -- O(nparts * nlist) numbers, one upload -- and one
+ * pass copies rows and ids device to device.  The device then holds exactly what amd_ivf_set_lists of the joined lists
+ * would have made: amd_ivf_layout_digest is equal in all eight words once the same derived copies were built, byte eligibility
+ * included -- it is decided over the values actually taken, so a window that drops its only non-byte row comes back byte-coded.
+ * A pending amd_ivf_add of a part is applied first; no part is changed; the same handle may appear in several parts.  Centroids (with
+ * norms and the fp16 range), the centroid table of amd_ivf_set_interdis, the tuner and the options are copied from part 0, as
+ * amd_ivf_subset copies them from its parent; the result borrows nothing, so every part may be destroyed afterwards.
+ * The result is in a subset's state: no host rows, read-only.  Everything a subset allows works on it -- every search form, clones,
+ * tickets, selectors, the exact calls, range search, the scanner calls, amd_ivf_get_list, the reconstruct calls, amd_ivf_subset and
+ * amd_ivf_concat of it -- and the mutating entry points return -2.
+ * Returns -2 before the device is touched for: a null parts / out; nparts 0 or above 64; a part whose h is null or a clone or has
+ * tickets out; parts that differ in device, d, nlist or metric; centroids that part 0 has and another part lacks or holds with other
+ * bits; begin[l] > end[l] or end[l] beyond the list's size; a joined list of 2^32 entries or more.  An empty result is a valid index
+ * of ntotal 0. */
+typedef struct {
+    amd_ivf_t* h;          /* an owner handle, or an index made by amd_ivf_subset / amd_ivf_concat; not a clone */
+    const uint64_t* begin; /* nlist entries, or NULL: 0 for every list */
+    const uint64_t* end;   /* nlist entries, or NULL: the list's size */
+    int64_t id_add;        /* added to every id taken from this part (IndexIVF::merge_from's add_id) */
+} amd_ivf_part_t;
+int amd_ivf_concat(const amd_ivf_part_t* parts, size_t nparts, amd_ivf_t** out);
+/* {entries taken, parts, host-to-device bytes, device-to-host bytes} of the call that made `joined` */
+int amd_ivf_last_concat(amd_ivf_t* joined, uint64_t out[4]);
+
 /* ---- search under an id selector, without a subset index -------------------------------
  * The same selectors as amd_ivf_subset (kind, a1, a2, sel, nsel: the five AMD_IVF_SUBSET_* kinds, the same membership rules, made
  * by the same pass over the resident ids), kept as ONE BIT PER STORED ENTRY instead of a second index: a selector moves no row and
