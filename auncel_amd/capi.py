@@ -46,6 +46,8 @@ SYMBOLS = [
     "amd_ivf_range_search_exact", "amd_ivf_range_search_exact_resident", "amd_ivf_range_search_exact_selected", "amd_ivf_last_range_exact",
     "amd_ivf_make_direct_map", "amd_ivf_direct_map_info", "amd_ivf_reconstruct", "amd_ivf_reconstruct_n", "amd_ivf_reconstruct_from_offsets",
     "amd_ivf_search_and_reconstruct", "amd_ivf_search_and_reconstruct_resident",
+    "amd_ivf_set_queries_dev", "amd_ivf_search_dev", "amd_ivf_search_preassigned_dev", "amd_ivf_search_resident_dev",
+    "amd_ivf_search_exact_dev", "amd_ivf_search_adaptive_dev", "amd_ivf_last_dev_io",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -854,6 +856,105 @@ class Handle:
         _chk(lib().amd_ivf_search_resident(self._h, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k), C.c_size_t(nprobe),
                                            coarse_mode, _f(D), _i(I)))
         return D, I
+
+    # ---- from and into device memory: torch tensors on the handle's device (include/auncel_amd.h: the `_dev` calls)
+    def _dev_rows(self, x):
+        """(pointer, dtype, ldx) of a [n, d] fp32 / fp16 tensor whose columns are contiguous; rows may be strided (a column slice)"""
+        import torch
+        if not (x.is_cuda and x.device.index == self.device):
+            raise ValueError("x must be a tensor on the handle's device")
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise ValueError(f"x must be [n, {self.d}]")
+        if x.dtype not in (torch.float32, torch.float16):
+            raise ValueError("x must be float32 or float16")
+        if x.shape[1] > 1 and x.stride(1) != 1:
+            raise ValueError("the columns of x must be contiguous (x.stride(1) == 1)")
+        ldx = x.stride(0) if x.shape[0] > 1 else max(x.stride(0), self.d)  # (the stride of a single row means nothing)
+        return C.c_void_p(x.data_ptr()), 0 if x.dtype == torch.float32 else 1, C.c_size_t(ldx)
+
+    def _dev_out(self, n, k, out):
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            return torch.empty((n, k), dtype=torch.float32, device=dev), torch.empty((n, k), dtype=torch.int64, device=dev)
+        D, I = out
+        if not (D.shape == (n, k) and D.dtype == torch.float32 and D.is_contiguous() and D.device == dev):
+            raise ValueError(f"out[0] must be a contiguous float32 [{n}, {k}] tensor on the handle's device")
+        if not (I.shape == (n, k) and I.dtype == torch.int64 and I.is_contiguous() and I.device == dev):
+            raise ValueError(f"out[1] must be a contiguous int64 [{n}, {k}] tensor on the handle's device")
+        return D, I
+
+    def _dev_stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def set_queries_dev(self, x):
+        p, dtype, ldx = self._dev_rows(x)
+        _chk(lib().amd_ivf_set_queries_dev(self._h, C.c_size_t(x.shape[0]), p, dtype, ldx, self._dev_stream()))
+
+    def search_dev(self, x, k, nprobe, coarse_mode=0, out=None):
+        """search() for a query tensor on the GPU; (D, I) are GPU tensors (out: the tensors to fill).  Ordered behind the current
+        torch stream; the results may be read from any stream on return."""
+        p, dtype, ldx = self._dev_rows(x)
+        n = x.shape[0]
+        D, I = self._dev_out(n, k, out)
+        _chk(lib().amd_ivf_search_dev(self._h, C.c_size_t(n), p, dtype, ldx, C.c_size_t(k), C.c_size_t(nprobe), coarse_mode,
+                                      C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()), self._dev_stream()))
+        return D, I
+
+    def search_preassigned_dev(self, x, k, keys, out=None):
+        """keys: an int64 [n, nprobe] tensor on the handle's device"""
+        import torch
+        p, dtype, ldx = self._dev_rows(x)
+        n = x.shape[0]
+        if not (keys.dtype == torch.int64 and keys.dim() == 2 and keys.shape[0] == n and keys.is_contiguous() and keys.is_cuda
+                and keys.device.index == self.device):
+            raise ValueError("keys must be a contiguous int64 [n, nprobe] tensor on the handle's device")
+        D, I = self._dev_out(n, k, out)
+        _chk(lib().amd_ivf_search_preassigned_dev(self._h, C.c_size_t(n), p, dtype, ldx, C.c_size_t(k), C.c_size_t(keys.shape[1]),
+                                                  C.c_void_p(keys.data_ptr()), C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()),
+                                                  self._dev_stream()))
+        return D, I
+
+    def search_resident_dev(self, start, n, k, nprobe, coarse_mode=0, out=None):
+        import torch
+        D, I = self._dev_out(n, k, out)
+        if out is not None:
+            torch.cuda.current_stream(self.device).synchronize()  # (the call takes no stream: whatever still uses `out` ends first)
+        _chk(lib().amd_ivf_search_resident_dev(self._h, C.c_size_t(start), C.c_size_t(n), C.c_size_t(k), C.c_size_t(nprobe), coarse_mode,
+                                               C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr())))
+        return D, I
+
+    def search_exact_dev(self, x, k, out=None):
+        p, dtype, ldx = self._dev_rows(x)
+        n = x.shape[0]
+        D, I = self._dev_out(n, k, out)
+        _chk(lib().amd_ivf_search_exact_dev(self._h, C.c_size_t(n), p, dtype, ldx, C.c_size_t(k), C.c_void_p(D.data_ptr()),
+                                            C.c_void_p(I.data_ptr()), self._dev_stream()))
+        return D, I
+
+    def search_adaptive_dev(self, start, n, query_topk, multipler, std_m, require_acc, my_nprobe, t_recalls, gt_D=None, profile=False,
+                            coarse_mode=0, out=None):
+        """search_adaptive() with (D, I) as GPU tensors; require_acc, my_nprobe, t_recalls and gt_D stay numpy arrays"""
+        import torch
+        req = f32(require_acc)
+        gt = f32(gt_D) if gt_D is not None else None
+        assert my_nprobe.dtype == np.uint64 and t_recalls.dtype == np.float32
+        D, I = self._dev_out(n, self.max_topk, out)
+        if out is not None:
+            torch.cuda.current_stream(self.device).synchronize()
+        _chk(lib().amd_ivf_search_adaptive_dev(self._h, C.c_size_t(start), C.c_size_t(n), C.c_size_t(query_topk), C.c_float(multipler),
+                                               C.c_float(std_m), _f(req), _f(gt), int(profile), coarse_mode,
+                                               my_nprobe.ctypes.data_as(_u64p), _f(t_recalls), C.c_void_p(D.data_ptr()),
+                                               C.c_void_p(I.data_ptr())))
+        return D, I
+
+    def last_dev_io(self):
+        """[query-row bytes host -> device, (D, I) bytes across the bus, ingest launches, 1 kernels stored the results / 2 a device
+        copy did] of the handle's last `_dev` call"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_last_dev_io(self._h, out))
+        return [int(v) for v in out]
 
     # ---- Auncel
     def set_interdis(self, table=None):

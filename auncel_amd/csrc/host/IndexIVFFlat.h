@@ -57,6 +57,11 @@ struct IndexIVFFlat : IndexIVF {
     void range_search_exact(idx_t n, const float* x, float radius, RangeSearchResult* result) const;
     void range_search_exact_selected(idx_t n, const float* x, float radius, RangeSearchResult* result, const IDSelector& sel) const;
     void range_exact_info(uint64_t out[4]) const;
+    /// search() from and into DEVICE memory of the engine's GPU (include/auncel_amd.h: amd_ivf_search_dev): d_x holds n contiguous
+    /// fp32 rows, d_D / d_I take n x k results, all three device pointers; bit for bit what search() returns for the same rows.
+    /// Ordered behind `stream` (a hipStream_t; null: the default stream) and finished on return.  The plain search only; not for
+    /// an IndexIVFFlatDedup (its results are expanded on the host).
+    void search_dev(idx_t n, const float* d_x, idx_t k, float* d_D, idx_t* d_I, void* stream = nullptr) const;
     IndexIVFFlat(const IndexIVFFlat&) = delete;
     IndexIVFFlat& operator=(const IndexIVFFlat&) = delete;
     ~IndexIVFFlat() override;
@@ -135,6 +140,8 @@ struct IndexIVFFlatSubset : Index {
     void reset() override;
     void search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const override;
     void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result) const override;
+    /// IndexIVFFlat::search_dev over the subset's own lists
+    void search_dev(idx_t n, const float* d_x, idx_t k, float* d_D, idx_t* d_I, void* stream = nullptr) const;
     /// IndexIVFFlat::search_exact / exact_info / exact_detail over the subset's own lists
     void search_exact(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels) const;
     void exact_info(uint64_t out[4]) const;

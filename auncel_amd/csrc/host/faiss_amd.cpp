@@ -1378,6 +1378,19 @@ void IndexIVFFlat::search_exact_selected(idx_t n, const float* x, idx_t k, float
     AMD(amd_ivf_search_exact_selected(g, device_selector(g, sel), (size_t)n, x, (size_t)k, distances, i64(labels)));
 }
 
+// ------------------------------------------------------------------------------------- search_dev
+void IndexIVFFlat::search_dev(idx_t n, const float* d_x, idx_t k, float* d_D, idx_t* d_I, void* stream) const {
+    FAISS_THROW_IF_NOT_MSG(dynamic_cast<const IndexIVFFlatDedup*>(this) == nullptr, "search_dev of an IndexIVFFlatDedup is not implemented");
+    FAISS_THROW_IF_NOT_MSG(!tune && !training && !(t && t->time_tune), "search_dev is the plain search only");
+    FAISS_THROW_IF_NOT_MSG(max_codes == 0, "search_dev with max_codes is not implemented");
+    amd_ivf* g = engine();  // (syncs the engine: centroids, lists or their journal)
+    AMD(amd_ivf_search_dev(g, (size_t)n, d_x, 0, (size_t)d, (size_t)k, nprobe, coarse_mode, d_D, i64(d_I), stream));
+}
+
+void IndexIVFFlatSubset::search_dev(idx_t n, const float* d_x, idx_t k, float* d_D, idx_t* d_I, void* stream) const {
+    AMD(amd_ivf_search_dev(gpu_, (size_t)n, d_x, 0, (size_t)d, (size_t)k, nprobe, coarse_mode, d_D, i64(d_I), stream));
+}
+
 void IndexIVFFlat::exact_info(uint64_t out[4]) const { AMD(amd_ivf_last_exact(engine(), out)); }
 void IndexIVFFlat::exact_detail(uint64_t out[4]) const { AMD(amd_ivf_last_exact_detail(engine(), out)); }
 

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/auncel_amd.h"
+#include "dev_io_args.h"
 #include "exact_args.h"
 #include "ivf_kernels.h"
 #include "kmeans_host.h"
@@ -597,6 +598,13 @@ struct amd_ivf {
     // side streams for the sparse tile shapes of a round (fork / join around the dense launch)
     hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
+    // the `_dev` entry points (DevCall): (D, I) of the call under way are the caller's DEVICE buffers -- the kernels store into them
+    // (out_D / out_I) or one device-to-device copy from w_D / w_I does (finish_results); nothing of them is touched by the host.
+    // (Kept behind every other member: the layout of what the host-pointer searches read and write is what it was.)
+    bool dev_out = false;
+    uint64_t dev_io[4] = {0, 0, 0, 0};  // amd_ivf_last_dev_io
+    DevBuf w_ingest;                    // ingest_rows_kernel's partial ranges and the call's (INGEST_MAX_PARTS + 1 of them)
+    hipEvent_t ev_dev_in = nullptr;     // recorded on the caller's stream, waited for by h->stream before it reads the caller's memory
 
     ~amd_ivf() {
         async_shutdown(this);
@@ -609,6 +617,7 @@ struct amd_ivf {
         if (ev_spec_go) (void)hipEventDestroy(ev_spec_go);
         if (ev_spec_done) (void)hipEventDestroy(ev_spec_done);
         if (ev_sel) (void)hipEventDestroy(ev_sel);
+        if (ev_dev_in) (void)hipEventDestroy(ev_dev_in);
         for (int i = 0; i < 2; i++)
             if (ev_fix[i]) (void)hipEventDestroy(ev_fix[i]);
         if (stream) (void)hipStreamDestroy(stream);
@@ -1755,6 +1764,12 @@ static void* device_view(const void* host) {
 struct DirectOut {
     amd_ivf* h;
     DirectOut(amd_ivf* h_, float* D, int64_t* I) : h(h_) {
+        if (h->dev_out) {  // (a `_dev` call: the caller's buffers are device memory, checked at the entry point)
+            h->out_D = D, h->out_I = I;
+            h->last_direct_out = 1;
+            h->dev_io[3] = std::max<uint64_t>(h->dev_io[3], 1);
+            return;
+        }
         void* d = opt(h, OPT_DIRECT_OUT, 1) != 0 ? device_view(D) : nullptr;
         void* i = d ? device_view(I) : nullptr;
         h->out_D = i ? static_cast<float*>(d) : nullptr;
@@ -1796,7 +1811,11 @@ void finish_results(amd_ivf* h, size_t n, size_t k, float* D, int64_t* I, uint32
         d2h_small(h, &back->err, h->w_error.p, 4, h->stream);
         d2h_small(h, back->rows, h->w_stats.p, sizeof back->rows, h->stream);
         if (stage_out) d2h_small(h, stage_out, h->w_stage.p, n * 4, h->stream);
-        if (!h->out_D && D) {  // (else the kernels wrote the caller's buffers themselves, or the caller reads w_D / w_I on the device)
+        if (!h->out_D && D && h->dev_out) {  // (a `_dev` call whose core stores into w_D / w_I: one copy on the device)
+            HIP_CHECK(hipMemcpyAsync(D, h->w_D.p, n * k * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(I, h->w_I.p, n * k * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
+            h->dev_io[3] = 2;
+        } else if (!h->out_D && D) {  // (else the kernels wrote the caller's buffers themselves, or the caller reads w_D / w_I on the device)
             d2h_small(h, D, h->w_D.p, n * k * sizeof(float), h->stream);
             d2h_small(h, I, h->w_I.p, n * k * sizeof(int64_t), h->stream);
         }
@@ -1810,6 +1829,64 @@ void finish_results(amd_ivf* h, size_t n, size_t k, float* D, int64_t* I, uint32
     queue();
     sync_and_flush(h, h->stream);
     epilogue();
+}
+
+// ---- the `_dev` entry points: query rows and results in the caller's device memory
+// what the runtime says of a pointer, in dev_io_args.h's terms
+static DevPtrKind dev_ptr_kind(const amd_ivf* h, const void* p) {
+    if (!p) return DEV_PTR_UNKNOWN;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();  // (pageable memory: not an error of ours)
+        return DEV_PTR_UNKNOWN;
+    }
+    if (at.type != hipMemoryTypeDevice) return DEV_PTR_HOST;
+    return at.device == h->device ? DEV_PTR_DEVICE : DEV_PTR_OTHER_DEVICE;
+}
+// scope of a `_dev` call on a handle: its counters start at zero; out: (D, I) are the caller's device buffers
+struct DevCall {
+    amd_ivf* h;
+    DevCall(amd_ivf* hh, bool out) : h(hh) {
+        for (auto& c : h->dev_io) c = 0;
+        h->dev_out = out;
+    }
+    DevCall(const DevCall&) = delete;
+    DevCall& operator=(const DevCall&) = delete;
+    ~DevCall() { h->dev_out = false; }
+};
+// the engine's stream goes on only after everything the caller's stream holds now: what produces the rows (and keys) this call
+// reads, and whatever still uses the buffers it writes
+static void wait_for_caller(amd_ivf* h, void* stream) {
+    if (!h->ev_dev_in) HIP_CHECK(hipEventCreateWithFlags(&h->ev_dev_in, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(h->ev_dev_in, static_cast<hipStream_t>(stream)));
+    HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_dev_in, 0));
+}
+// n x d rows of fp32 / fp16 at a device pointer, into dst (w_x, d_resident) in the engine's layout; their range comes back from the
+// device -- 12 bytes behind one synchronisation, because the choice of the arithmetic (byte_queries, fusable_with,
+// exact_pick_pass) is host code that shapes every launch after this one
+QueryRows device_rows(amd_ivf* h, float* dst, const void* d_x, int dtype, size_t ldx, size_t n) {
+    h->w_ingest.ensure((INGEST_MAX_PARTS + 1) * sizeof(QueryRange));
+    QueryRange* parts = h->w_ingest.as<QueryRange>();
+    launch_ingest_rows(d_x, dtype, n, h->d, h->dpad, ldx, dst, parts, h->stream);
+    h->dev_io[2] += 2;
+    QueryRange got = query_range_empty();
+    {
+        SmallCopies guard(h);
+        d2h_small(h, &got, parts + INGEST_MAX_PARTS, sizeof got, h->stream);
+        sync_and_flush(h, h->stream);
+    }
+    QueryRows r{dst, IntRange()};
+    r.range.ok = got.ok != 0;
+    r.range.lo = got.lo;
+    r.range.hi = got.hi;
+    return r;
+}
+// rows i0 .. i0 + c of a [.][k] result from a device buffer to the caller's (host, or device in a `_dev` call)
+static void copy_result_rows(amd_ivf* h, float* D, int64_t* I, const float* src_D, const int64_t* src_I, size_t rows, size_t k) {
+    const hipMemcpyKind kind = h->dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIP_CHECK(hipMemcpyAsync(D, src_D, rows * k * sizeof(float), kind, h->stream));
+    HIP_CHECK(hipMemcpyAsync(I, src_I, rows * k * sizeof(int64_t), kind, h->stream));
+    if (h->dev_out) h->dev_io[3] = 2;
 }
 
 static void fill_timing(amd_ivf* h, const double* ms, const double* ln) {
@@ -4393,18 +4470,35 @@ static void adaptive_redo_ties(amd_ivf_t* h, const float* d_x, size_t start, siz
         for (size_t j = 0; j < m; j++) sel_again[j] = sel_of_call[again[j]];
         h->selected.sel_of = sel_again.data();
     }
-    with_select_fallback(h, [&] {
-        adaptive_core_once(h, h->w_redo_x.as<float>(), 0, m, query_topk, multipler, std_m, req.data(), gt_D ? gt.data() : nullptr, profile,
-                           coarse_mode, np.data(), tr.data(), Dc.data(), Ic.data(), qr);
-    });
+    // (a `_dev` call: the few rows of this pass come back to the host like any host call's and are sent to their places in the
+    // caller's device buffers below -- the one case in which result bytes cross, counted in amd_ivf_last_dev_io's out[1])
+    const bool dev_out = h->dev_out;
+    h->dev_out = false;
+    try {
+        with_select_fallback(h, [&] {
+            adaptive_core_once(h, h->w_redo_x.as<float>(), 0, m, query_topk, multipler, std_m, req.data(), gt_D ? gt.data() : nullptr, profile,
+                               coarse_mode, np.data(), tr.data(), Dc.data(), Ic.data(), qr);
+        });
+    } catch (...) {
+        h->dev_out = dev_out;
+        throw;
+    }
+    h->dev_out = dev_out;
     h->selected.sel_of = sel_of_call;
     for (size_t j = 0; j < m; j++) {
         const size_t i = again[j];
         my_nprobe[start + i] = np[j];
         t_recalls[start + i] = tr[j];
+        if (dev_out) {
+            HIP_CHECK(hipMemcpyAsync(D + i * K, Dc.data() + j * K, K * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(I + i * K, Ic.data() + j * K, K * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+            h->dev_io[1] += K * (sizeof(float) + sizeof(int64_t));
+            continue;
+        }
         std::copy(Dc.begin() + j * K, Dc.begin() + (j + 1) * K, D + i * K);
         std::copy(Ic.begin() + j * K, Ic.begin() + (j + 1) * K, I + i * K);
     }
+    if (dev_out) HIP_CHECK(stream_sync(h->stream));
 }
 
 // Fewer than 20 queries per call is the regime in which the reference ranks exact coarse distances (utils.cpp:624-655), so
@@ -6328,6 +6422,20 @@ size_t exact_general(amd_ivf* h, const float* d_x, const uint32_t* idx, size_t m
         const size_t before = h->stats_host[3];
         if (!idx) {
             search_fixed_device(h, rows, c, k, nlist, h->w_ckeys.as<int64_t>(), D + o * k, I + o * k, 0, 0, qr, keep);
+        } else if (h->dev_out) {
+            // a `_dev` call: the slice's rows into w_ex_D / w_ex_I (the list pass's result has left them: exact_slice), then every run
+            // of consecutive queries to its place in the caller's device buffers by one copy
+            h->w_ex_D.ensure(c * k * sizeof(float));
+            h->w_ex_I.ensure(c * k * sizeof(int64_t));
+            search_fixed_device(h, rows, c, k, nlist, h->w_ckeys.as<int64_t>(), h->w_ex_D.as<float>(), h->w_ex_I.as<int64_t>(), 0, 0, qr, keep);
+            for (size_t j = 0; j < c;) {
+                size_t e = j + 1;
+                while (e < c && idx[o + e] == idx[o + e - 1] + 1) e++;
+                copy_result_rows(h, D + (size_t)idx[o + j] * k, I + (size_t)idx[o + j] * k, h->w_ex_D.as<float>() + j * k,
+                                 h->w_ex_I.as<int64_t>() + j * k, e - j, k);
+                j = e;
+            }
+            HIP_CHECK(stream_sync(h->stream));
         } else {
             tD.resize(c * k);
             tI.resize(c * k);
@@ -6497,8 +6605,9 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
         return exact_general(h, d_x, nullptr, n, k, D, I, qr, keep);
     }
     search_full(h, d_x, n, k, seed, -1, D, I, qr, keep);
-    const float* seed_D = h->last_direct_out ? static_cast<const float*>(device_view(D)) : h->w_D.as<float>();
-    const int64_t* seed_I = h->last_direct_out ? static_cast<const int64_t*>(device_view(I)) : h->w_I.as<int64_t>();
+    // (a `_dev` call: the seed went straight into the caller's device buffers)
+    const float* seed_D = !h->last_direct_out ? h->w_D.as<float>() : h->dev_out ? D : static_cast<const float*>(device_view(D));
+    const int64_t* seed_I = !h->last_direct_out ? h->w_I.as<int64_t>() : h->dev_out ? I : static_cast<const int64_t*>(device_view(I));
     if (!seed_D || !seed_I) throw std::runtime_error("exact search: the seed's result is not on the device");
     // ---- 2. list pass
     h->w_ex_D.ensure(n * k * sizeof(float));
@@ -6531,8 +6640,7 @@ size_t exact_slice(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, i
     HIP_CHECK(hipMemcpyAsync(flag.data(), h->w_ex_flag.p, n * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(tot, h->w_ex_tot.p, sizeof tot, hipMemcpyDeviceToHost, s));
     // (the rows of flagged queries are not written by the selection: the general way fills them below)
-    HIP_CHECK(hipMemcpyAsync(D, h->w_ex_D.p, n * k * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(I, h->w_ex_I.p, n * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    copy_result_rows(h, D, I, h->w_ex_D.as<float>(), h->w_ex_I.as<int64_t>(), n, k);
     HIP_CHECK(stream_sync(s));
     if (timed) {
         float a = 0, b = 0;
@@ -6564,8 +6672,18 @@ void exact_core(amd_ivf* h, const float* d_x, size_t n, size_t k, float* D, int6
     uint64_t out[4] = {0, 0, 0, 0};
     size_t heap = 0;
     if (ntotal == 0 || (sel && sel->info[1] == 0)) {  // an empty index, a selector without members: the reference's padding for every query
-        std::fill(D, D + n * k, h->metric == METRIC_L2 ? FLT_MAX : -FLT_MAX);
-        std::fill(I, I + n * k, (int64_t)-1);
+        if (h->dev_out) {  // (the same padding, set on the device)
+            const float pad = h->metric == METRIC_L2 ? FLT_MAX : -FLT_MAX;
+            int bits;
+            memcpy(&bits, &pad, 4);
+            HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(D), bits, n * k, h->stream));
+            HIP_CHECK(hipMemsetAsync(I, 0xff, n * k * sizeof(int64_t), h->stream));
+            HIP_CHECK(stream_sync(h->stream));
+            h->dev_io[3] = 2;
+        } else {
+            std::fill(D, D + n * k, h->metric == METRIC_L2 ? FLT_MAX : -FLT_MAX);
+            std::fill(I, I + n * k, (int64_t)-1);
+        }
         out[2] = n;
     } else {
         const size_t slice = 8192;  // (bounds the candidate buffers: slice x cap x 8 bytes)
@@ -6823,6 +6941,137 @@ int amd_ivf_search_exact_resident(amd_ivf_t* h, size_t start, size_t n, size_t k
     reset_scan_counters(h);
     exact_core(h, q.d_x, n, k, D, I, q.range);
     finish_timing(h, wc.stop());
+    API_END
+}
+
+// ---- search from and into device memory.  Every call is the body of its host-pointer namesake with two changes:
+// the query rows come from ingest_rows_kernel instead of host_rows, and the cores store into the caller's device buffers (DevCall:
+// amd_ivf::dev_out).  dev_call_check refuses what dev_io_args.h refuses, before anything is launched.
+static void dev_call_check(const char* what, const amd_ivf* h, bool have_rows, const void* x, int dtype, size_t ldx, bool have_out,
+                           const void* D, const void* I) {
+    const std::string bad = dev_call_error(what, true, have_rows, x, have_rows ? dev_ptr_kind(h, x) : DEV_PTR_DEVICE, dtype, ldx, (size_t)h->d,
+                                           have_out, D, have_out ? dev_ptr_kind(h, D) : DEV_PTR_DEVICE, I,
+                                           have_out ? dev_ptr_kind(h, I) : DEV_PTR_DEVICE);
+    if (!bad.empty()) throw EngineError(bad);
+}
+static QueryRows ingest_queries(amd_ivf* h, size_t n, const void* d_x, int dtype, size_t ldx) {
+    h->w_x.ensure(n * h->dpad * sizeof(float));
+    return device_rows(h, h->w_x.as<float>(), d_x, dtype, ldx, n);
+}
+
+int amd_ivf_set_queries_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, void* stream) {
+    API_BEGIN
+    if (!h) throw EngineError("set_queries_dev: null handle");
+    if (n == 0) return 0;
+    require_device();
+    use_device(h);
+    dev_call_check("set_queries_dev", h, true, d_x, dtype, ldx, false, nullptr, nullptr);
+    DevCall call(h, false);
+    wait_for_caller(h, stream);
+    h->d_resident.ensure(n * h->dpad * sizeof(float));
+    const QueryRows q = device_rows(h, h->d_resident.as<float>(), d_x, dtype, ldx, n);  // (synchronises h->stream)
+    h->n_resident = n;
+    h->resident_gen++;
+    h->resident_range = q.range;
+    API_END
+}
+
+int amd_ivf_search_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, size_t k, size_t nprobe, int coarse_mode, float* d_D,
+                       int64_t* d_I, void* stream) {
+    API_BEGIN
+    if (!h) throw EngineError("search_dev: null handle");
+    if (n == 0 || k == 0) return 0;
+    require_device();
+    use_device(h);
+    dev_call_check("search_dev", h, true, d_x, dtype, ldx, true, d_D, d_I);
+    DevCall call(h, true);
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    wait_for_caller(h, stream);
+    const QueryRows q = ingest_queries(h, n, d_x, dtype, ldx);
+    search_full(h, q.d_x, n, k, nprobe, coarse_mode, d_D, d_I, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_preassigned_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, size_t k, size_t nprobe,
+                                   const int64_t* d_keys, float* d_D, int64_t* d_I, void* stream) {
+    API_BEGIN
+    if (!h) throw EngineError("search_preassigned_dev: null handle");
+    if (n == 0 || k == 0) return 0;
+    require_device();
+    use_device(h);
+    dev_call_check("search_preassigned_dev", h, true, d_x, dtype, ldx, true, d_D, d_I);
+    {
+        const std::string bad = dev_ptr_error("d_keys", d_keys, dev_ptr_kind(h, d_keys), sizeof(int64_t));
+        if (!bad.empty()) throw EngineError("search_preassigned_dev: " + bad);
+    }
+    DevCall call(h, true);
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    wait_for_caller(h, stream);
+    const QueryRows q = ingest_queries(h, n, d_x, dtype, ldx);
+    // (the keys are read where they are: the rounds are planned on the device from keys that are already there)
+    search_fixed_device(h, q.d_x, n, k, nprobe, d_keys, d_D, d_I, 0, 0, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_resident_dev(amd_ivf_t* h, size_t start, size_t n, size_t k, size_t nprobe, int coarse_mode, float* d_D, int64_t* d_I) {
+    API_BEGIN
+    if (!h) throw EngineError("search_resident_dev: null handle");
+    require_device();
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    if (n == 0 || k == 0) return 0;
+    dev_call_check("search_resident_dev", h, false, nullptr, 0, 0, true, d_D, d_I);
+    DevCall call(h, true);
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    search_full(h, q.d_x, n, k, nprobe, coarse_mode, d_D, d_I, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_exact_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, size_t k, float* d_D, int64_t* d_I, void* stream) {
+    API_BEGIN
+    if (!h) throw EngineError("search_exact_dev: null handle");
+    if (k == 0) throw EngineError("search_exact: k must be positive");
+    if (n == 0) return 0;
+    require_device();
+    use_device(h);
+    dev_call_check("search_exact_dev", h, true, d_x, dtype, ldx, true, d_D, d_I);
+    for (int i = 0; i < 4; i++) h->last_exact[i] = h->last_exact_detail[i] = 0;
+    DevCall call(h, true);
+    WallClock wc(h->stream);
+    reset_scan_counters(h);
+    wait_for_caller(h, stream);
+    const QueryRows q = ingest_queries(h, n, d_x, dtype, ldx);
+    exact_core(h, q.d_x, n, k, d_D, d_I, q.range);
+    finish_timing(h, wc.stop());
+    API_END
+}
+
+int amd_ivf_search_adaptive_dev(amd_ivf_t* h, size_t start, size_t n, size_t query_topk, float multipler, float std_m, const float* require_acc,
+                                const float* gt_D, int profile, int coarse_mode, uint64_t* my_nprobe, float* t_recalls, float* d_D,
+                                int64_t* d_I) {
+    API_BEGIN
+    if (!h) throw EngineError("search_adaptive_dev: null handle");
+    require_device();
+    use_device(h);
+    const QueryRows q = resident_rows(h, start, n);
+    if (n == 0) return 0;
+    dev_call_check("search_adaptive_dev", h, false, nullptr, 0, 0, true, d_D, d_I);
+    DevCall call(h, true);
+    adaptive_core(h, q.d_x, start, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, d_D, d_I,
+                  q.range);
+    API_END
+}
+
+int amd_ivf_last_dev_io(amd_ivf_t* h, uint64_t out[4]) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("last_dev_io: null argument");
+    for (int i = 0; i < 4; i++) out[i] = h->dev_io[i];
     API_END
 }
 

@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "query_range.h"
 #include "selector_args.h"
 
 namespace amdivf {
@@ -774,6 +775,13 @@ struct GatherRowsArgs {
     unsigned long long* bad; // started at ~0 by the caller: the smallest i whose label or key names nothing (nothing is read for it)
 };
 void launch_gather_rows(const GatherRowsArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------------------- query rows from device memory (ivf_ingest.hip)
+// n rows of d elements (dtype 0: fp32, 1: fp16; row stride ldx >= d elements, columns contiguous) at the device pointer x -> the
+// engine's query layout in `out` (fp32, row stride dpad, zero padded), and in the same pass the range of the n x d elements
+// (query_range.h) into parts[INGEST_MAX_PARTS]; parts[0 .. INGEST_MAX_PARTS) are the workgroups' partial ranges.  Two launches.
+constexpr uint32_t INGEST_MAX_PARTS = 512;
+void launch_ingest_rows(const void* x, int dtype, size_t n, int d, int dpad, size_t ldx, float* out, QueryRange* parts, hipStream_t s);
 
 // ---------------------------------------------------------------------------- search under an id selector (ivf_selector.hip)
 // kept[l] = the set bits of list l's words (a wave per list)

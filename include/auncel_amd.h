@@ -787,6 +787,41 @@ int amd_ivf_set_option(amd_ivf_t* h, const char* key, double value);
 int amd_ivf_get_option(amd_ivf_t* h, const char* key, double* value);
 
 /* ------------------------------------------------------------------------------------------------
+ * Search from and into device memory.  The `_dev` forms of amd_ivf_set_queries, amd_ivf_search,
+ * amd_ivf_search_preassigned, amd_ivf_search_resident, amd_ivf_search_exact and amd_ivf_search_adaptive: the query rows, the keys and
+ * the results (d_x, d_keys, d_D, d_I) are DEVICE pointers on the handle's GPU; everything else is as in the host-pointer call, and
+ * the results are the host-pointer call's bit for bit.  No query row and no result byte crosses the bus.
+ *   d_x      n rows of d elements, columns contiguous, row stride ldx >= d ELEMENTS; nothing between the rows is read
+ *   dtype    0: fp32, 1: fp16 (widened exactly: the result is that of the fp32 call on the widened values)
+ *   d_D, d_I n x k floats and int64 (n x max_topk for the adaptive call), rows contiguous; padded with -1 and +-FLT_MAX as the
+ *            host-pointer calls pad
+ *   stream   the caller's hipStream_t (NULL: the default stream).  The engine's stream waits for what that stream holds when the
+ *            call is made -- the work that produces d_x / d_keys, the last use of d_D / d_I -- before it touches any of them; no host
+ *            synchronisation is needed in front of the call.  The calls without a stream argument expect d_D / d_I to be idle.
+ *            Every call returns after the engine's stream has finished: the results may then be read from any stream.
+ * One small synchronisation per call is kept: the range of the query values (12 bytes, computed by the kernel that reads the rows)
+ * is read back before the search's arithmetic -- exact, fused or byte codes -- is chosen, because that choice is host code.
+ * require_acc, gt_D, my_nprobe and t_recalls of the adaptive call stay HOST arrays, as in amd_ivf_search_adaptive.
+ * Refused with -2 before anything is launched: a null pointer, a pointer that is not device memory of the handle's device, ldx < d,
+ * a dtype other than 0 or 1, a pointer misaligned for its element type -- and what the host-pointer call refuses.  n == 0 returns 0
+ * and touches nothing.
+ * amd_ivf_last_dev_io: the handle's last `_dev` call.  out[0] bytes of query rows that crossed host -> device (0), out[1] bytes of
+ * (D, I) that crossed between device and host (0; the rows of queries searched again under option "coarse_ties" = 2 are the one
+ * exception, and are counted), out[2] launches of the ingest kernels, out[3] how the caller's buffers were written: 1 the search's
+ * kernels stored into them, 2 a device-to-device copy did (the exact call, whose passes select into a workspace), 0 no results. */
+int amd_ivf_set_queries_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, void* stream);
+int amd_ivf_search_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, size_t k, size_t nprobe, int coarse_mode, float* d_D,
+                       int64_t* d_I, void* stream);
+int amd_ivf_search_preassigned_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, size_t k, size_t nprobe,
+                                   const int64_t* d_keys, float* d_D, int64_t* d_I, void* stream);
+int amd_ivf_search_resident_dev(amd_ivf_t* h, size_t start, size_t n, size_t k, size_t nprobe, int coarse_mode, float* d_D, int64_t* d_I);
+int amd_ivf_search_exact_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, size_t k, float* d_D, int64_t* d_I, void* stream);
+int amd_ivf_search_adaptive_dev(amd_ivf_t* h, size_t start, size_t n, size_t query_topk, float multipler, float std_m, const float* require_acc,
+                                const float* gt_D, int profile, int coarse_mode, uint64_t* my_nprobe, float* t_recalls, float* d_D,
+                                int64_t* d_I);
+int amd_ivf_last_dev_io(amd_ivf_t* h, uint64_t out[4]);
+
+/* ------------------------------------------------------------------------------------------------
  * Dataset files of the reference's harness (Auncel/eval/bound.cpp:29-113; host only).  Buffers are malloc'ed
  * here and released with amd_ivf_free.  Where the harness aborts (missing file, size that is not a whole number of rows,
  * short read) these return -2 and amd_ivf_last_error() says why.
