@@ -998,6 +998,8 @@ void IndexIVFFlat::add_core(idx_t n, const float* x, const long* xids, const lon
         quantizer->assign(n, x, own.data());
         idx = own.data();
     }
+    // (all or nothing: the lists and the direct map stay as they are when a list number cannot be)
+    for (idx_t i = 0; i < n; i++) FAISS_THROW_IF_NOT_MSG(idx[i] < (long)nlist, "Invalid list number in add");
     long n_add = 0;
     for (idx_t i = 0; i < n; i++) {
         long id = xids ? xids[i] : ntotal + i;

@@ -3442,6 +3442,9 @@ int amd_ivf_add(amd_ivf_t* h, size_t n, const float* x, const int64_t* xids, con
     // (the device layout moves at the next search: not under searches that are still running)
     const bool journal = !h->lists_dirty && opt(h, OPT_INCREMENTAL, 1) != 0;
     if (journal && n && tickets_out(h)) throw EngineError("tickets are still out: wait for them before changing the index");
+    // (all or nothing: a list number that cannot be is found before anything of the index -- lists, journal, selectors -- has moved)
+    for (size_t i = 0; precomputed_idx && i < n; i++)
+        if (precomputed_idx[i] >= 0 && (size_t)precomputed_idx[i] >= h->nlist) throw EngineError("Invalid list number in add");
     std::vector<int64_t> assign;
     const int64_t* idx = precomputed_idx;
     if (!idx) {
@@ -3475,8 +3478,8 @@ int amd_ivf_add(amd_ivf_t* h, size_t n, const float* x, const int64_t* xids, con
         memcpy(&c[o], x + i * h->d, h->d * sizeof(float));
         h->h_ids[l].push_back(id);
         h->list_range[l].add(x + i * h->d, h->d);
+        h->db_range.add(x + i * h->d, h->d);  // (stored vectors only: one that is skipped leaves no trace in the lists' range)
     }
-    h->db_range.add(x, n * (size_t)h->d);
     h->ntotal += n;
     if (journal && n) {
         h->journal_pending = true;

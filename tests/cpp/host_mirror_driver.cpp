@@ -54,6 +54,27 @@ static int run_fixed(const tb::Bundle& in) {
     bool sizes_ok = true;
     for (size_t l = 0; l < nlist; l++) sizes_ok &= ix->invlists->list_size(l) == (size_t)ls[l];
     expect(sizes_ok, "list sizes after add");
+    if (sizes_ok && in.has("list_ids")) {  // every list's content: ids and codes, list after list
+        const int64_t* gi = in.get("list_ids").as<int64_t>();
+        const float* gc = in.get("list_codes").as<float>();
+        bool same = true;
+        size_t o = 0;
+        for (size_t l = 0; l < nlist; o += (size_t)ls[l], l++) {
+            if (!ls[l]) continue;
+            same &= same_i(ix->invlists->get_ids(l), gi + o, (size_t)ls[l]) &&
+                    memcmp(ix->invlists->get_codes(l), gc + o * d, (size_t)ls[l] * d * sizeof(float)) == 0;
+        }
+        expect(same, "list contents after add");
+    }
+    {   // add_core with a list number that cannot be: refused whole, whatever stood before the bad number
+        IndexIVFFlat* flat = dynamic_cast<IndexIVFFlat*>(ix);
+        const long bad[4] = {0, 1, (long)nlist, 2};
+        bool threw = false;
+        try { flat->add_core(4, xb.as<float>(), nullptr, bad); } catch (const FaissException&) { threw = true; }
+        bool whole = threw && (size_t)index->ntotal == nb;
+        for (size_t l = 0; l < nlist; l++) whole &= ix->invlists->list_size(l) == (size_t)ls[l];
+        expect(whole, "add_core with a bad list number leaves the index as it was");
+    }
     ix->nprobe = nprobe;
 
     for (size_t ki = 0; ki < ks.numel(); ki++) {

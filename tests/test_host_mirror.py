@@ -8,18 +8,14 @@ import pytest
 
 from util import load_case, traces_from_gold
 
+import mirror_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_driver.cpp")
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    from auncel_amd import build
-    build.build_host()
-    exe = str(tmp_path_factory.mktemp("drv") / "host_mirror_driver")
-    subprocess.run(["g++", "-std=c++17", "-O1", DRIVER_SRC, "-o", exe, "-L" + build.LIBDIR, "-lfaiss_amd", "-launcel_amd",
-                    "-Wl,-rpath," + build.LIBDIR, "-pthread"], check=True)
-    return exe
+    return mirror_driver.host_mirror_driver(tmp_path_factory)
 
 
 def test_driver_builds_and_links(driver):
