@@ -34,6 +34,7 @@ SYMBOLS = [
     "amd_ivf_scan_arith",
     "amd_ivf_update_lists", "amd_ivf_remove_ids", "amd_ivf_last_update", "amd_ivf_layout_digest",
     "amd_ivf_subset", "amd_ivf_last_subset", "amd_ivf_concat", "amd_ivf_last_concat",
+    "amd_ivf_build_dev", "amd_ivf_last_build",
     "amd_ivf_selector_create", "amd_ivf_selector_destroy", "amd_ivf_selector_info",
     "amd_ivf_search_selected", "amd_ivf_search_preassigned_selected", "amd_ivf_search_resident_selected",
     "amd_ivf_selector_combine", "amd_ivf_range_search_selected", "amd_ivf_range_search_preassigned_selected",
@@ -469,6 +470,35 @@ class Handle:
         """(entries taken, parts, host-to-device bytes, device-to-host bytes) of the call that made this joined index"""
         out = (C.c_uint64 * 4)()
         _chk(lib().amd_ivf_last_concat(self._h, out))
+        return tuple(int(v) for v in out)
+
+    # ---- an index built on the device from device-resident rows (include/auncel_amd.h: amd_ivf_build_dev)
+    def build_dev(self, x, ids=None, id_base=0, assign=None, coarse_mode=0):
+        """a read-only Handle over the rows of the [n, d] fp32 / fp16 tensor x (on the handle's device; rows may be strided), grouped
+        into this handle's lists on the device: what a fresh owner holds after add(x, ids, assign).  ids / assign: int64 [n] tensors
+        on the device or None (id_base + i / this handle's own exact assignment); a negative assign entry skips its row.  Ordered
+        behind the current torch stream; complete on return.  Handle.concat([index, index.build_dev(x)]) adds from device memory."""
+        import torch
+        n = x.shape[0]
+        p, dtype, ldx = self._dev_rows(x) if n else (None, 0, C.c_size_t(self.d))  # (no rows: no stride to speak of)
+        for name, t in (("ids", ids), ("assign", assign)):
+            if t is not None and not (t.dtype == torch.int64 and t.shape == (n,) and t.is_contiguous() and t.is_cuda
+                                      and t.device.index == self.device):
+                raise ValueError(f"{name} must be a contiguous int64 [n] tensor on the handle's device")
+        c = Handle.__new__(Handle)
+        c.d, c.nlist, c.metric, c.device = self.d, self.nlist, self.metric, self.device
+        c._h = C.c_void_p()
+        if hasattr(self, "max_topk"):
+            c.max_topk = self.max_topk
+        _chk(lib().amd_ivf_build_dev(self._h, C.c_size_t(n), p, dtype, ldx, C.c_void_p(ids.data_ptr()) if ids is not None else None,
+                                     C.c_int64(int(id_base)), C.c_void_p(assign.data_ptr()) if assign is not None else None,
+                                     int(coarse_mode), self._dev_stream(), C.byref(c._h)))
+        return c
+
+    def last_build(self):
+        """(rows offered, rows stored, host-to-device bytes, device-to-host bytes) of the call that made this built index"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_last_build(self._h, out))
         return tuple(int(v) for v in out)
 
     # ---- search under an id selector (include/auncel_amd.h: amd_ivf_selector_create)

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/auncel_amd.h"
+#include "build_args.h"
 #include "dev_io_args.h"
 #include "exact_args.h"
 #include "ivf_kernels.h"
@@ -369,6 +370,7 @@ struct amd_ivf {
     bool is_subset = false;
     uint64_t last_subset[4] = {0, 0, 0, 0};  // amd_ivf_last_subset
     uint64_t last_concat[4] = {0, 0, 0, 0};  // amd_ivf_last_concat
+    uint64_t last_build[4] = {0, 0, 0, 0};   // amd_ivf_last_build
     PinnedBuf p_upd;
     DevBuf d_upd;
     DevBuf d_codes, d_ids, d_list_off, d_centroids, d_centroid_norms;
@@ -5945,6 +5947,133 @@ int amd_ivf_last_concat(amd_ivf_t* joined, uint64_t out[4]) {
     API_BEGIN
     if (!joined || !out) throw EngineError("null argument");
     for (int i = 0; i < 4; i++) out[i] = ix(joined)->last_concat[i];
+    API_END
+}
+
+// ------------------------------------------------------------------------------------ an index from device rows
+// A new index on q's device from n rows of a caller's device tensor, grouped into q's lists in HBM (ivf_build.hip): the device then
+// holds what amd_ivf_add of the same rows into a fresh owner, and its first upload, would have made.  The list sizes are counted on
+// the device and come back once, with the block table and two flag bits, because h_list_off / h_block_off are host state; what
+// crosses PCIe is O(nlist) words and 16 bytes of value range each way -- no row, no id, no list number.
+int amd_ivf_build_dev(amd_ivf_t* q, size_t n, const void* d_x, int dtype, size_t ldx, const int64_t* d_ids, int64_t id_base,
+                      const int64_t* d_assign, int coarse_mode, void* stream, amd_ivf_t** out) {
+    API_BEGIN
+    if (out) *out = nullptr;
+    BuildArgs a{q != nullptr, out != nullptr, q && q->parent, q && q->have_centroids, n, q ? (size_t)q->d : 0, d_x, DEV_PTR_DEVICE, dtype, ldx,
+                d_ids,        DEV_PTR_DEVICE, d_assign,       DEV_PTR_DEVICE};
+    if (build_args_error(a).empty() && n > 0) {  // (what the runtime knows of the pointers, asked only once the rest is in order)
+        use_device(q);
+        a.kind_x = dev_ptr_kind(q, d_x);
+        if (d_ids) a.kind_ids = dev_ptr_kind(q, d_ids);
+        if (d_assign) a.kind_assign = dev_ptr_kind(q, d_assign);
+    }
+    const std::string bad = build_args_error(a);
+    if (!bad.empty()) throw EngineError(bad);
+    amd_ivf* h = q;
+    if (tickets_out(h)) throw EngineError("tickets are still out: wait for them before building from this handle's quantizer");
+    use_device(h);
+    const size_t nlist = h->nlist;
+    const int dpad = h->dpad;
+    std::unique_ptr<amd_ivf> s = derived_index(h);  // (the quantizer, the Auncel state and the options come along)
+    hipStream_t st = s->stream;
+    uint64_t h2d = 0, d2h = 0, stored = 0;
+    if (n > 0) {
+        DevBuf b_keys, b_total, b_cnt, b_rank, b_run, b_range;
+        b_keys.ensure(n * 4);
+        b_total.ensure((nlist + 1) * 8);  // (the flag word behind the totals)
+        uint32_t* keys = b_keys.as<uint32_t>();
+        unsigned long long* total = b_total.as<unsigned long long>();
+        uint32_t* flags = reinterpret_cast<uint32_t*>(total + nlist);
+        HIP_CHECK(hipMemsetAsync(b_total.p, 0, (nlist + 1) * 8, st));
+        // ---- sweep 1: a key per row, the lists' totals
+        if (d_assign) {
+            wait_for_caller(s.get(), stream);
+            launch_build_keys(d_assign, n, (uint32_t)nlist, keys, total, flags, st);
+        } else {
+            // quantizer->assign on the device: amd_ivf_add's own call, block by block through q's staging and on q's stream, which
+            // therefore starts behind the zeroed totals and is waited for before the new index's stream goes on
+            HIP_CHECK(stream_sync(st));
+            wait_for_caller(h, stream);
+            wait_for_caller(s.get(), stream);
+            const size_t bs = 1 << 18, elem = dev_dtype_size(dtype);
+            h->w_x.ensure(std::min(bs, n) * dpad * sizeof(float));
+            h->w_cdis.ensure(std::min(bs, n) * 4);
+            h->w_ckeys.ensure(std::min(bs, n) * 8);
+            h->w_ingest.ensure((INGEST_MAX_PARTS + 1) * sizeof(QueryRange));
+            for (size_t i0 = 0; i0 < n; i0 += bs) {
+                const size_t m = std::min(bs, n - i0);
+                launch_ingest_rows(static_cast<const char*>(d_x) + i0 * ldx * elem, dtype, m, h->d, dpad, ldx, h->w_x.as<float>(),
+                                   h->w_ingest.as<QueryRange>(), h->stream);
+                coarse_dev(h, h->w_x.as<float>(), m, 1, coarse_mode, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(), 0);
+                launch_build_keys(h->w_ckeys.as<int64_t>(), m, (uint32_t)nlist, keys + i0, total, flags, h->stream);
+            }
+            HIP_CHECK(stream_sync(h->stream));
+            double ms[NCAT], ln[NCAT];
+            h->timer.collect(ms, NCAT, ln);
+        }
+        // ---- the offsets, the block table and the flags: the one read-back
+        s->d_list_off.ensure((nlist + 1) * 8);
+        s->d_block_off.ensure((nlist + 1) * 8);
+        launch_build_offsets(total, (uint32_t)nlist, s->d_list_off.as<uint64_t>(), s->d_block_off.as<uint64_t>(), flags, st);
+        s->h_block_off.assign(nlist + 1, 0);
+        uint32_t got_flags = 0;
+        HIP_CHECK(hipMemcpyAsync(s->h_list_off.data(), s->d_list_off.p, (nlist + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(s->h_block_off.data(), s->d_block_off.p, (nlist + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&got_flags, flags, 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(stream_sync(st));
+        d2h += 2 * (nlist + 1) * 8 + 4;
+        if (got_flags & BUILD_FLAG_LIST) throw EngineError("Invalid list number in add");
+        if (got_flags & BUILD_FLAG_LONG) throw EngineError("build_dev: a list would hold 2^32 entries or more");
+        stored = s->h_list_off[nlist];
+        if (stored > n) throw std::runtime_error("build_dev: more rows counted than offered");
+        if (stored >= (1ull << SCAN_VB_BITS)) throw EngineError("too many vectors for one index");
+        if (stored) {
+            // ---- sweep 2, chunk by chunk: ranks and counts, the counts into places, the rows to their places
+            s->d_codes.ensure(stored * dpad * sizeof(float));
+            s->d_ids.ensure(stored * sizeof(int64_t));
+            uint32_t rg[4] = {0, subset_range_key(0.f), subset_range_key(0.f), 0};
+            b_range.ensure(16);
+            HIP_CHECK(hipMemcpyAsync(b_range.p, rg, 16, hipMemcpyHostToDevice, st));
+            const char* chunk_env = getenv("AUNCEL_AMD_BUILD_CHUNK");  // (tests: rows a chunk, so that small inputs span several)
+            const uint64_t tiles_all = (n + BUILD_TILE - 1) / BUILD_TILE;
+            const uint64_t per_chunk = build_chunk_tiles(n, nlist, BUILD_TILE, BUILD_CHUNK_BYTES, chunk_env ? strtoull(chunk_env, nullptr, 10) : 0);
+            b_cnt.ensure(per_chunk * nlist * 4);
+            b_rank.ensure(per_chunk * BUILD_TILE * 2);
+            b_run.ensure(nlist * 4);
+            HIP_CHECK(hipMemsetAsync(b_run.p, 0, nlist * 4, st));
+            BuildPlaceArgs pa{d_x,  dtype, (uint64_t)ldx, h->d, dpad, d_ids, id_base, keys, b_rank.as<uint16_t>(), b_cnt.as<uint32_t>(), s->d_list_off.as<uint64_t>(),
+                              n,    0,     0,             (uint32_t)nlist, s->d_codes.as<float>(), s->d_ids.as<int64_t>(), b_range.as<uint32_t>()};
+            for (uint64_t t0 = 0; t0 < tiles_all; t0 += per_chunk) {
+                pa.row0 = t0 * BUILD_TILE;
+                pa.ntiles = (uint32_t)std::min<uint64_t>(per_chunk, tiles_all - t0);
+                HIP_CHECK(hipMemsetAsync(b_cnt.p, 0, (size_t)pa.ntiles * nlist * 4, st));
+                launch_build_count(keys, n, pa.row0, pa.ntiles, (uint32_t)nlist, b_rank.as<uint16_t>(), b_cnt.as<uint32_t>(), st);
+                launch_build_scan(b_cnt.as<uint32_t>(), pa.ntiles, (uint32_t)nlist, b_run.as<uint32_t>(), st);
+                launch_build_place(pa, st);
+            }
+            HIP_CHECK(hipMemcpyAsync(rg, b_range.p, 16, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(stream_sync(st));
+            h2d += 16;
+            d2h += 16;
+            // byte eligibility over the values STORED: a skipped row leaves no trace
+            s->db_range.ok = rg[0] == 0;
+            s->db_range.lo = subset_range_value(rg[1]);
+            s->db_range.hi = subset_range_value(rg[2]);
+        }
+    }
+    h2d += finish_derived_index(s.get(), stored);
+    s->last_build[0] = n;
+    s->last_build[1] = stored;
+    s->last_build[2] = h2d;
+    s->last_build[3] = d2h;
+    *out = s.release();
+    API_END
+}
+
+int amd_ivf_last_build(amd_ivf_t* built, uint64_t out[4]) {
+    API_BEGIN
+    if (!built || !out) throw EngineError("null argument");
+    for (int i = 0; i < 4; i++) out[i] = ix(built)->last_build[i];
     API_END
 }
 

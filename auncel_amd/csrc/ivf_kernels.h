@@ -748,6 +748,40 @@ struct ConcatPart {
 // the part's id_add.  Every array is device memory; range as launch_subset_compact's, over the rows taken.
 void launch_concat_rows(const ConcatPart* parts, uint32_t nparts, const uint64_t* src_start, const uint64_t* cum, const uint64_t* new_off,
                         uint32_t nlist, uint64_t nt, int dpad, float* codes, int64_t* ids, uint32_t* range, hipStream_t s);
+// ---------------------------------------------------------------------------- an index from device rows (ivf_build.hip)
+// amd_ivf_build_dev: n rows with a list number each, grouped into the lists in ascending input index.  Every array is device memory.
+constexpr uint32_t BUILD_TILE = 1024;          // rows a workgroup of the second sweep ranks and places
+constexpr uint32_t BUILD_SKIP = 0xffffffffu;   // the key of a row that is not stored
+constexpr uint32_t BUILD_FLAG_LIST = 1, BUILD_FLAG_LONG = 2;  // a list number >= nlist; a list of 2^32 entries or more
+// keys[i] = assign[i], BUILD_SKIP where it is negative; total[l] += rows of list l (the caller starts total and flags at zero)
+void launch_build_keys(const int64_t* assign, uint64_t n, uint32_t nlist, uint32_t* keys, unsigned long long* total, uint32_t* flags, hipStream_t s);
+// the totals into the lists' offsets and the block table of the padded copies (nlist + 1 each)
+void launch_build_offsets(const unsigned long long* total, uint32_t nlist, uint64_t* list_off, uint64_t* block_off, uint32_t* flags, hipStream_t s);
+// One chunk of the second sweep: tiles of BUILD_TILE rows from row0 on, `ntiles` of them.  count: rank[tile * BUILD_TILE + r] = rows
+// of the tile before row r with its key, cnt[tile * nlist + l] = rows of the tile in list l (cnt zeroed by the caller); scan: cnt ->
+// rows of the list in earlier tiles, of this chunk and of those before it (running[nlist], zero before the first chunk); place: rows
+// and ids to list_off[key] + cnt + rank, the rows read from x (dtype 0: fp32, 1: fp16; row stride ldx elements), range as
+// launch_subset_compact's over the rows stored.
+void launch_build_count(const uint32_t* keys, uint64_t n, uint64_t row0, uint32_t ntiles, uint32_t nlist, uint16_t* rank, uint32_t* cnt, hipStream_t s);
+void launch_build_scan(uint32_t* cnt, uint32_t ntiles, uint32_t nlist, uint32_t* running, hipStream_t s);
+struct BuildPlaceArgs {
+    const void* x;
+    int dtype;
+    uint64_t ldx;
+    int d, dpad;
+    const int64_t* in_ids;  // or null: id_base + i
+    int64_t id_base;
+    const uint32_t* keys;
+    const uint16_t* rank;
+    const uint32_t* before;  // (cnt after the scan)
+    const uint64_t* list_off;
+    uint64_t n, row0;
+    uint32_t ntiles, nlist;
+    float* codes;
+    int64_t* ids;
+    uint32_t* range;
+};
+void launch_build_place(const BuildPlaceArgs& a, hipStream_t s);
 // ---------------------------------------------------------------------------- stored vectors back (ivf_reconstruct.hip)
 // table[id - lo] = max(table[id - lo], list << 32 | offset) for every stored entry whose id lies in [lo, lo + n) (nt entries, list_off:
 // nlist + 1); the caller starts the table at -1 in every slot and counts at {0, 0}: counts[0] += entries outside the window,

@@ -149,6 +149,36 @@ int amd_ivf_concat(const amd_ivf_part_t* parts, size_t nparts, amd_ivf_t** out);
 /* {entries taken, parts, host-to-device bytes, device-to-host bytes} of the call that made `joined` */
 int amd_ivf_last_concat(amd_ivf_t* joined, uint64_t out[4]);
 
+/* ---- an index built on the device from device-resident rows ----------------------------
+ * The other half of the `_dev` searches below: vectors that were produced on the GPU get into an index without crossing to the host.
+ * *out is an index of its own on q's device -- q's d, nlist, metric, centroids (with norms and the fp16 range), centroid table of
+ * amd_ivf_set_interdis, tuner and options, copied as amd_ivf_subset copies them -- that holds exactly what a fresh owner holds after
+ * amd_ivf_add(n, x, xids, precomputed_idx) of the same values and its first upload: list l holds the rows assigned to l in ascending
+ * input index, with their ids; byte eligibility is decided over the values stored; amd_ivf_layout_digest is equal to that owner's in
+ * all eight words once the same derived copies were built.  q is an owner handle or an index made by amd_ivf_subset / amd_ivf_concat /
+ * amd_ivf_build_dev, not a clone; its lists are not read, it is not changed, and *out borrows nothing from it.
+ * d_x, dtype, ldx and stream are those of amd_ivf_search_dev: n rows of d elements, dtype 0 fp32 or 1 fp16 (widened exactly), row
+ * stride ldx >= d elements, nothing between the rows is read; the engine waits for everything `stream` holds before it reads a device
+ * argument, and the call returns when the new index is complete.  d_ids: n int64 ids in device memory, or NULL: row i gets id
+ * id_base + i.  d_assign: n list numbers in device memory -- a negative one skips its row, which leaves no trace -- or NULL: the list
+ * numbers are amd_ivf_add's own, the exact nearest centroid (coarse_mode as in amd_ivf_search), found in blocks of 2^18 rows through
+ * q's staging buffers and on q's stream, so q may not be searched from another thread during the call.
+ * The rows are grouped in HBM by a counting sort whose passes are ordered by the stream alone; the list sizes come
+ * back once, because the offsets are host state as well: what crosses PCIe is O(nlist) words and 16 bytes of value range each way,
+ * and no row, id or list number.  amd_ivf_concat of an index and a freshly built one is an add from device memory.
+ * The result is in a subset's state: no host rows, read-only.  Everything a subset allows works on it -- every search form, the
+ * `_dev` searches, clones, tickets, selectors, the exact calls, range search, amd_ivf_get_list, the reconstruct calls, amd_ivf_subset
+ * and amd_ivf_concat of it -- and the mutating entry points return -2.
+ * Returns -2 with *out = NULL, before anything is launched, for: a null q / out; q a clone, without centroids or with tickets out;
+ * what amd_ivf_search_dev refuses of d_x, dtype and ldx; d_ids or d_assign that is not device memory of q's device or not 8-byte
+ * aligned.  After the rows were counted and before one is moved: a list number >= nlist ("Invalid list number in add": the whole
+ * call is refused, as amd_ivf_add refuses it), a list of 2^32 entries or more, more rows than one index holds.  n == 0, or every row
+ * skipped, gives a valid index of ntotal 0. */
+int amd_ivf_build_dev(amd_ivf_t* q, size_t n, const void* d_x, int dtype, size_t ldx, const int64_t* d_ids, int64_t id_base,
+                      const int64_t* d_assign, int coarse_mode, void* stream, amd_ivf_t** out);
+/* {rows offered, rows stored, host-to-device bytes, device-to-host bytes} of the call that made `built` */
+int amd_ivf_last_build(amd_ivf_t* built, uint64_t out[4]);
+
 /* ---- search under an id selector, without a subset index -------------------------------
  * The same selectors as amd_ivf_subset (kind, a1, a2, sel, nsel: the five AMD_IVF_SUBSET_* kinds, the same membership rules, made
  * by the same pass over the resident ids), kept as ONE BIT PER STORED ENTRY instead of a second index: a selector moves no row and
