@@ -49,6 +49,7 @@ SYMBOLS = [
     "amd_ivf_search_and_reconstruct", "amd_ivf_search_and_reconstruct_resident",
     "amd_ivf_set_queries_dev", "amd_ivf_search_dev", "amd_ivf_search_preassigned_dev", "amd_ivf_search_resident_dev",
     "amd_ivf_search_exact_dev", "amd_ivf_search_adaptive_dev", "amd_ivf_last_dev_io",
+    "amd_ivf_assign", "amd_ivf_assign_dev", "amd_ivf_last_assign", "amd_ivf_kmeans_last_assign",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -161,6 +162,13 @@ def self_check(device=0):
     v = (C.c_uint64 * 4)()
     _chk(lib().amd_ivf_self_check(int(device), v))
     return {"adds": int(v[0]), "counted": int(v[1]), "wrong": int(v[2]), "xcd_mask": int(v[3])}
+
+
+def kmeans_last_assign():
+    """Handle.last_assign()'s counters summed over the iterations of this thread's last kmeans()"""
+    out = (C.c_uint64 * 4)()
+    _chk(lib().amd_ivf_kmeans_last_assign(out))
+    return tuple(int(v) for v in out)
 
 
 def kmeans(metric, x, k, niter=25, seed=1234, max_points_per_centroid=256, spherical=False, int_centroids=False, coarse_mode=0,
@@ -978,6 +986,34 @@ class Handle:
                                                my_nprobe.ctypes.data_as(_u64p), _f(t_recalls), C.c_void_p(D.data_ptr()),
                                                C.c_void_p(I.data_ptr())))
         return D, I
+
+    # ---- Index::assign (include/auncel_amd.h: amd_ivf_assign)
+    def assign(self, x):
+        """(assign int64 [n], dis float32 [n]): the nearest centroid of every row of x and the reference's distance to it -- bit for
+        bit the keys and distances of coarse(x, 1) -- by the fused matrix-core pass up to 128 dimensions"""
+        x = f32(x)
+        n = x.shape[0]
+        a, dis = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.float32)
+        _chk(lib().amd_ivf_assign(self._h, C.c_size_t(n), _f(x), a.ctypes.data_as(_i64p), _f(dis)))
+        return a, dis
+
+    def assign_dev(self, x):
+        """assign() for an [n, d] fp32 / fp16 tensor on the handle's device (rows may be strided); (assign, dis) are GPU tensors, and
+        assign is what build_dev(assign=...) takes.  Ordered behind the current torch stream; complete on return."""
+        import torch
+        n = x.shape[0]
+        p, dtype, ldx = self._dev_rows(x) if n else (None, 0, C.c_size_t(self.d))
+        a = torch.empty(n, dtype=torch.int64, device=x.device)
+        dis = torch.empty(n, dtype=torch.float32, device=x.device)
+        _chk(lib().amd_ivf_assign_dev(self._h, C.c_size_t(n), p, dtype, ldx, C.c_void_p(a.data_ptr()), C.c_void_p(dis.data_ptr()),
+                                      self._dev_stream()))
+        return a, dis
+
+    def last_assign(self):
+        """(rows, rows decided by the fused pass, rows flagged and sent the general way, candidates recomputed) of the last assignment"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().amd_ivf_last_assign(self._h, out))
+        return tuple(int(v) for v in out)
 
     def last_dev_io(self):
         """[query-row bytes host -> device, (D, I) bytes across the bus, ingest launches, 1 kernels stored the results / 2 a device

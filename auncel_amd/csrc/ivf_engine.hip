@@ -94,6 +94,8 @@ enum OptId {
     OPT_EXACT_WIDE_BYTES,   // amd_ivf_search_exact over byte-coded lists beyond 128 dimensions (up to 1024): 1 the workgroup-tiled byte list pass, 0 (the default) the general way
     OPT_SELECTED_SKIP_EMPTY,  // amd_ivf_search_adaptive_selected & co: 1 (the default) a list that keeps nothing under a query's selector is planned as
                               // an absent probe -- no row, no scan; the probe still counts -- 0 it is scanned and masked out like any other
+    OPT_ASSIGN_FUSED,   // exact rankings of length one (amd_ivf_add, amd_ivf_build_dev, amd_ivf_kmeans): 1 the fused matrix-core pass + rescoring
+                        // (ivf_assign.hip), 0 (the default) the general way; amd_ivf_assign / amd_ivf_assign_dev always take the fused pass
     N_OPT
 };
 struct OptSpec {
@@ -126,6 +128,7 @@ const OptSpec OPT_TABLE[N_OPT] = {
     {"exact_wide", "AUNCEL_AMD_EXACT_WIDE", nullptr},
     {"exact_wide_bytes", "AUNCEL_AMD_EXACT_WIDE_BYTES", nullptr},
     {"selected_skip_empty", "AUNCEL_AMD_SELECTED_SKIP_EMPTY", nullptr},
+    {"assign_fused", "AUNCEL_AMD_ASSIGN_FUSED", nullptr},
 };
 struct Options {
     // (atomic: amd_ivf_set_option on the owner may run while search contexts cloned from it are searching; a search reads the
@@ -492,6 +495,16 @@ struct amd_ivf {
     float centroid_norm_max = 0.f;  // max |c|^2 over the centroids, rounded up
     DevBuf d_cinfo;                 // range of the centroid table (launch_amax): the fp16 form of the approximate coarse ranking
     bool in_coarse_pick = false;    // (the exact re-run of flagged queries is inside coarse_dev)
+    // the fused nearest-centroid pass (ivf_assign.hip).  Of the index: the centroids as fp16 MFMA fragments, made by the first
+    // fused call after amd_ivf_set_centroids (assign_scale 0: the centroids have no usable fp16 scale, no table).  Of the handle:
+    // whether the call under way asked for the pass itself (amd_ivf_assign & co), its workspaces and its counters
+    DevBuf d_assign_table;
+    bool assign_table_valid = false;
+    float assign_scale = 0.f;
+    std::mutex assign_mu;
+    bool assign_call = false;
+    DevBuf a_cand, a_cnt, a_flag;
+    uint64_t last_assign[4] = {0, 0, 0, 0};  // rows, decided by the fused pass, flagged and sent the general way, candidates recomputed
     size_t coarse_picked = 0;       // rankings of the last coarse_dev call that came from coarse_pick_kernel
     DevBuf c_pick_flag, c_pick_x, c_pick_dis, c_pick_keys;  // coarse_pick_kernel: flagged queries and their exact re-run
     PinnedBuf p_pick;
@@ -1947,16 +1960,100 @@ struct WallClock {
 };
 
 // ------------------------------------------------------------------------------------ coarse
+void coarse_dev(amd_ivf* h, const float* d_x, size_t n, size_t nprobe, int mode, float* d_out_dis, int64_t* d_out_keys, int fused, size_t prefix = 0);
+// The nearest centroid of n device rows by the fused matrix-core pass (ivf_assign.hip): the candidates of every row,
+// their distances in the reference's sequence, and the rows the pass could not decide through coarse_dev as a call of their own,
+// scattered back -- as the flagged rankings of coarse_pick_kernel are.  false: the pass does not serve this index (beyond
+// ASSIGN_MAX_DPAD dimensions, centroids without a usable fp16 scale) and nothing was launched.
+static bool assign_fused(amd_ivf* h, const float* d_x, size_t n, int mode, float* d_out_dis, int64_t* d_out_keys, int fused) {
+    amd_ivf* idx = ix(h);
+    if (h->dpad > ASSIGN_MAX_DPAD || n >= (1ull << 32)) return false;
+    hipStream_t s = h->stream;
+    {
+        std::lock_guard<std::mutex> lock(idx->assign_mu);
+        if (!idx->assign_table_valid) {
+            uint32_t info[4];
+            HIP_CHECK(hipMemcpyAsync(info, idx->d_cinfo.p, 16, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(stream_sync(s));
+            idx->assign_scale = filter_half_scale(info, h->d);
+            if (idx->assign_scale != 0.f) {
+                idx->d_assign_table.ensure(assign_table_bytes((uint32_t)h->nlist, h->d));
+                launch_assign_table(idx->d_centroids.as<float>(), (uint32_t)h->nlist, h->d, h->dpad, h->metric, idx->assign_scale,
+                                    idx->d_assign_table.as<float>(), s);
+                HIP_CHECK(stream_sync(s));  // (other contexts of the index read it from their own streams)
+            }
+            idx->assign_table_valid = true;
+        }
+    }
+    if (idx->assign_scale == 0.f) return false;
+    h->a_cand.ensure(n * ASSIGN_CAND * 4);
+    h->a_cnt.ensure(n * 4);
+    h->a_flag.ensure((4 + n) * 4);
+    HIP_CHECK(hipMemsetAsync(h->a_flag.p, 0, 16, s));
+    AssignArgs a{};
+    a.x = d_x;
+    a.n = n;
+    a.table = idx->d_assign_table.as<float>();
+    a.centroids = idx->d_centroids.as<float>();
+    a.nlist = (uint32_t)h->nlist;
+    a.d = h->d;
+    a.dpad = h->dpad;
+    a.metric = h->metric;
+    a.inv_sy = 1.f / idx->assign_scale;
+    a.C = exact_float_constant(h->d, false);
+    a.cmax = idx->centroid_norm_max;
+    a.cand = h->a_cand.as<uint32_t>();
+    a.cnt = h->a_cnt.as<uint32_t>();
+    a.out_dis = d_out_dis;
+    a.out_keys = d_out_keys;
+    a.stat = h->a_flag.as<uint32_t>();
+    a.flagged = h->a_flag.as<uint32_t>() + 4;
+    const size_t timed = h->timer.begin(CAT_COARSE, s);
+    launch_assign_min(a, s);
+    launch_assign_rescore(a, s);
+    h->timer.end(timed, s);
+    uint32_t stat[4] = {0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(stat, h->a_flag.p, 16, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(stream_sync(s));
+    const uint32_t m = stat[0];
+    if (m) {
+        h->c_pick_x.ensure((size_t)m * h->dpad * sizeof(float));
+        h->c_pick_dis.ensure((size_t)m * 4);
+        h->c_pick_keys.ensure((size_t)m * 8);
+        launch_gather_rows(d_x, a.flagged, m, (uint32_t)h->dpad, h->c_pick_x.as<float>(), s);
+        struct Guard {
+            bool& f;
+            ~Guard() { f = false; }
+        } guard{h->in_coarse_pick};
+        h->in_coarse_pick = true;
+        coarse_dev(h, h->c_pick_x.as<float>(), m, 1, mode, h->c_pick_dis.as<float>(), h->c_pick_keys.as<int64_t>(), fused, 0);
+        launch_scatter_rows(h->c_pick_dis.p, a.flagged, m, 1, d_out_dis, s);
+        launch_scatter_rows(h->c_pick_keys.p, a.flagged, m, 2, d_out_keys, s);
+    }
+    h->coarse_picked = 0;
+    h->last_assign[0] = n;
+    h->last_assign[1] = n - m;
+    h->last_assign[2] = m;
+    h->last_assign[3] = (uint64_t)stat[2] | (uint64_t)stat[3] << 32;
+    return true;
+}
+
 // distances of n device queries (row stride dpad) to every centroid -> sorted top-nprobe on device
 // prefix != 0: the caller reads only the first `prefix` entries of every ranking (launch_sort_rows)
 void coarse_dev(amd_ivf* h, const float* d_x, size_t n, size_t nprobe, int mode, float* d_out_dis, int64_t* d_out_keys, int fused,
-                size_t prefix = 0) {
+                size_t prefix) {
     if (!ix(h)->have_centroids) throw EngineError("quantizer has no centroids");
     // mode 0: exact per-pair kernel; 1: GEMM formulation on the matrix cores; -1: the reference's own switch
     // (utils.cpp:624-655: exact for fewer than 20 queries when d % 4 == 0, BLAS otherwise)
     const bool gemm = mode == 1 || (mode < 0 && !(n < 20 && h->d % 4 == 0));
     const size_t nlist = h->nlist;
     hipStream_t s = h->stream;
+    // Exact rankings of length one: the fused pass where it is asked for and serves the shape (its flagged rows come back here)
+    if (nprobe == 1 && !gemm && prefix == 0 && !h->in_coarse_pick) {
+        if ((h->assign_call || opt(h, OPT_ASSIGN_FUSED, 0) != 0) && assign_fused(h, d_x, n, mode, d_out_dis, d_out_keys, fused)) return;
+        h->last_assign[0] = h->last_assign[2] = n;
+        h->last_assign[1] = h->last_assign[3] = 0;
+    }
     // Exact rankings of a large call that reads few entries of each (fixed nprobe): the matrix cores rank approximately, the
     // candidates that can be among the nprobe best are recomputed exactly (coarse_pick_kernel); queries in which exactly equal
     // distances meet -- where the reference's order is its heap's history -- come back flagged and take the path below.
@@ -3397,6 +3494,7 @@ int amd_ivf_set_centroids(amd_ivf_t* h, const float* centroids) {
     HIP_CHECK(stream_sync(h->stream));
     h->have_centroids = true;
     h->have_interdis = false;
+    h->assign_table_valid = false;  // (laid out again by the next fused assignment: assign_fused)
     {
         double mx = 0;  // max |c|^2: the error bound of the approximate coarse ranking (coarse_pick_kernel)
         for (size_t i = 0; i < h->nlist; i++) {
@@ -4857,9 +4955,16 @@ int amd_ivf_merge_tables(int metric, size_t n, size_t k, size_t nshard, const fl
 // iteration's assignment runs through the coarse kernels, the centroid update through ivf_kmeans.hip (fp32 sums in point
 // order); what is sequential in the reference -- permutations, the objective's running sum, void-cluster splitting -- stays
 // on the host (kmeans_host.h).
+static thread_local uint64_t g_kmeans_assign[4] = {0, 0, 0, 0};  // amd_ivf_last_assign's counters, summed over the iterations of this thread's last amd_ivf_kmeans
+int amd_ivf_kmeans_last_assign(uint64_t out[4]) {
+    if (!out) return -2;
+    for (int i = 0; i < 4; i++) out[i] = g_kmeans_assign[i];
+    return 0;
+}
 int amd_ivf_kmeans(int d, size_t n, const float* x_in, size_t k, int metric, int niter, long seed, size_t max_points_per_centroid,
                    int spherical, int int_centroids, int coarse_mode, int device, float* centroids, float* obj) {
     API_BEGIN
+    for (uint64_t& v : g_kmeans_assign) v = 0;
     namespace km = amdivf_kmeans;
     if (d <= 0 || k == 0) throw EngineError("bad dimension / k");
     if (n < k) throw EngineError("Number of training points should be at least as large as number of clusters");
@@ -4919,6 +5024,7 @@ int amd_ivf_kmeans(int d, size_t n, const float* x_in, size_t k, int metric, int
         if (amd_ivf_set_centroids(h.get(), centroids)) throw EngineError(g_last_error);
         coarse_dev(h.get(), h->d_resident.as<float>(), nx, 1, coarse_mode, d_dis.as<float>(), d_keys.as<int64_t>(),
                    h->allow_fused && h->centroid_range.fusable_with(qr, h->metric));
+        for (int i = 0; i < 4; i++) g_kmeans_assign[i] += h->last_assign[i];
         HIP_CHECK(hipMemcpyAsync(dis.data(), d_dis.p, nx * 4, hipMemcpyDeviceToHost, s));
         launch_kmeans_group(d_keys.as<int64_t>(), nx, (uint32_t)k, keys_in.as<uint32_t>(), keys_out.as<uint32_t>(), idx_in.as<uint32_t>(),
                             idx_out.as<uint32_t>(), counts.as<uint32_t>(), temp.p, temp_bytes, s);
@@ -4960,7 +5066,7 @@ static int opt_id(const char* key) {
 static double opt_default(OptId id) {
     switch (id) {
         case OPT_COARSE_TIES: case OPT_TIE_FIX: case OPT_PHASE_TIMING: return -1;
-        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: case OPT_EXACT_FLOAT: case OPT_EXACT_WIDE: case OPT_EXACT_WIDE_BYTES: return 0;  // (0: chosen per search)
+        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: case OPT_EXACT_FLOAT: case OPT_EXACT_WIDE: case OPT_EXACT_WIDE_BYTES: case OPT_ASSIGN_FUSED: return 0;  // (0: chosen per search)
         case OPT_ROUND_FIRST: return 12;
         case OPT_SCAN_PIPELINED: return 7;
         case OPT_FILTER: case OPT_COARSE_PICK: return 2;
@@ -7197,6 +7303,79 @@ int amd_ivf_search_adaptive_dev(amd_ivf_t* h, size_t start, size_t n, size_t que
     DevCall call(h, true);
     adaptive_core(h, q.d_x, start, n, query_topk, multipler, std_m, require_acc, gt_D, profile, coarse_mode, my_nprobe, t_recalls, d_D, d_I,
                   q.range);
+    API_END
+}
+
+// ---- Index::assign: the nearest centroid of every row, always by the fused pass where it serves the shape.  Blocks
+// of 2^20 rows through the handle's staging; the kernels write the caller's device buffers themselves.
+static void assign_blocks(amd_ivf* h, size_t n, const void* x, bool dev, int dtype, size_t ldx, int64_t* assign, float* dis) {
+    const size_t bs = (size_t)1 << 20, elem = dev ? dev_dtype_size(dtype) : sizeof(float);
+    h->w_x.ensure(std::min(bs, n) * h->dpad * sizeof(float));
+    h->w_cdis.ensure(std::min(bs, n) * 4);
+    if (!dev) h->w_ckeys.ensure(std::min(bs, n) * 8);
+    if (dev) h->w_ingest.ensure((INGEST_MAX_PARTS + 1) * sizeof(QueryRange));
+    struct Guard {
+        bool& f;
+        ~Guard() { f = false; }
+    } guard{h->assign_call};
+    h->assign_call = true;
+    uint64_t total[4] = {0, 0, 0, 0};
+    for (size_t i0 = 0; i0 < n; i0 += bs) {
+        const size_t m = std::min(bs, n - i0);
+        if (dev) {
+            launch_ingest_rows(static_cast<const char*>(x) + i0 * ldx * elem, dtype, m, h->d, h->dpad, ldx, h->w_x.as<float>(),
+                               h->w_ingest.as<QueryRange>(), h->stream);
+            coarse_dev(h, h->w_x.as<float>(), m, 1, 0, dis ? dis + i0 : h->w_cdis.as<float>(), assign + i0, 0);
+        } else {
+            upload_rows(h, h->w_x.as<float>(), static_cast<const float*>(x) + i0 * h->d, m);
+            coarse_dev(h, h->w_x.as<float>(), m, 1, 0, h->w_cdis.as<float>(), h->w_ckeys.as<int64_t>(), 0);
+            HIP_CHECK(hipMemcpyAsync(assign + i0, h->w_ckeys.p, m * 8, hipMemcpyDeviceToHost, h->stream));
+            if (dis) HIP_CHECK(hipMemcpyAsync(dis + i0, h->w_cdis.p, m * 4, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_CHECK(stream_sync(h->stream));  // (the staging is the next block's)
+        for (int i = 0; i < 4; i++) total[i] += h->last_assign[i];
+    }
+    for (int i = 0; i < 4; i++) h->last_assign[i] = total[i];
+    double ms[NCAT], ln[NCAT];
+    h->timer.collect(ms, NCAT, ln);
+}
+
+int amd_ivf_assign(amd_ivf_t* h, size_t n, const float* x, int64_t* assign, float* dis) {
+    API_BEGIN
+    if (!h || (n && (!x || !assign))) throw EngineError("assign: null argument");
+    require_device();
+    use_device(h);
+    for (uint64_t& v : h->last_assign) v = 0;
+    if (n == 0) return 0;
+    assign_blocks(h, n, x, false, 0, 0, assign, dis);
+    API_END
+}
+
+int amd_ivf_assign_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, int64_t* d_assign, float* d_dis, void* stream) {
+    API_BEGIN
+    if (!h) throw EngineError("assign_dev: null handle");
+    if (n && (!d_x || !d_assign)) throw EngineError("assign_dev: null pointer");
+    require_device();
+    use_device(h);
+    for (uint64_t& v : h->last_assign) v = 0;
+    if (n == 0) return 0;
+    dev_call_check("assign_dev", h, true, d_x, dtype, ldx, false, nullptr, nullptr);
+    {
+        std::string bad = dev_ptr_error("d_assign", d_assign, dev_ptr_kind(h, d_assign), sizeof(int64_t));
+        if (bad.empty() && d_dis) bad = dev_ptr_error("d_dis", d_dis, dev_ptr_kind(h, d_dis), sizeof(float));
+        if (!bad.empty()) throw EngineError("assign_dev: " + bad);
+    }
+    DevCall call(h, true);
+    wait_for_caller(h, stream);
+    assign_blocks(h, n, d_x, true, dtype, ldx, d_assign, d_dis);
+    API_END
+}
+
+int amd_ivf_last_assign(amd_ivf_t* h, uint64_t out[4]) {
+    API_BEGIN
+    if (!h || !out) throw EngineError("last_assign: null argument");
+    require_device();
+    for (int i = 0; i < 4; i++) out[i] = h->last_assign[i];
     API_END
 }
 

@@ -817,6 +817,38 @@ void launch_gather_rows(const GatherRowsArgs& a, hipStream_t s);
 constexpr uint32_t INGEST_MAX_PARTS = 512;
 void launch_ingest_rows(const void* x, int dtype, size_t n, int d, int dpad, size_t ldx, float* out, QueryRange* parts, hipStream_t s);
 
+// ---------------------------------------------------------------------------- nearest centroid in one fused pass (ivf_assign.hip)
+constexpr uint32_t ASSIGN_CAND = 8;     // candidate slots a row: a row with more centroids within the error bound of its minimum is flagged
+constexpr int ASSIGN_MAX_DPAD = 128;    // a wave keeps its rows' fp16 pieces in registers up to here
+constexpr int ASSIGN_QB = 2;            // 32-row blocks a wave (the register / LDS table)
+// 16-dimension pieces a centroid takes in the table (an even count), the table's bytes, and the table itself from the centroid rows:
+// fp16(sy * value) in MFMA fragment order, a block of 32 centroids followed by its 32 terms (|c|^2 under L2, 0 under the inner
+// product, +inf for the centroids that pad the last block).  sy: the power of two of the centroids' range (filter_half_scale), not 0
+uint32_t assign_pieces(int d);
+size_t assign_table_bytes(uint32_t nlist, int d);
+void launch_assign_table(const float* centroids, uint32_t nlist, int d, int dpad, int metric, float sy, float* table, hipStream_t s);
+struct AssignArgs {
+    const float* x;          // n rows, stride dpad (<= ASSIGN_MAX_DPAD), zero padded
+    size_t n;
+    const float* table;      // launch_assign_table
+    const float* centroids;  // nlist rows, stride dpad: the rescoring's operand
+    uint32_t nlist;
+    int d, dpad, metric;
+    float inv_sy;            // 1 / sy
+    float C;                 // |approximate - reference| <= C (|x|^2 + cmax) (L2) / C |x| sqrt(cmax) (inner product)
+    float cmax;              // max |c|^2, rounded up
+    uint32_t* cand;          // n x ASSIGN_CAND
+    uint32_t* cnt;           // n
+    float* out_dis;          // n: the reference's distance to ...
+    int64_t* out_keys;       // n: ... the nearest centroid, of the rows that are not flagged
+    uint32_t* stat;          // [0] += flagged rows, [2..3] (64 bits) += candidates recomputed; zeroed by the caller
+    uint32_t* flagged;       // [n] their numbers, in no order
+};
+// every centroid that can be a row's exact nearest into cand / cnt (no distance is stored) ...
+void launch_assign_min(const AssignArgs& a, hipStream_t s);
+// ... and the best of them by the reference's own distance; rows it cannot decide are flagged
+void launch_assign_rescore(const AssignArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------------------- search under an id selector (ivf_selector.hip)
 // kept[l] = the set bits of list l's words (a wave per list)
 void launch_selector_list_kept(const uint32_t* count, const uint64_t* block_off, uint32_t nlist, uint32_t* kept, hipStream_t s);

@@ -811,6 +811,10 @@ int amd_ivf_set_byte_codes(amd_ivf_t* h, int enable);
  *   "selected_skip_empty"  the adaptive and training calls under a selector (amd_ivf_search_adaptive_selected & co): 1 a list    1
  *                     that keeps nothing under a query's selector is planned as an absent probe, 0 it is scanned and masked
  *                     (AUNCEL_AMD_SELECTED_SKIP_EMPTY is the environment's form).  Cannot change a result
+ *   "assign_fused"    exact rankings of length one up to 128 dimensions (amd_ivf_add without precomputed_idx, amd_ivf_build_dev    0
+ *                     without d_assign, amd_ivf_kmeans, coarse mode 0): 1 the fused matrix-core pass of amd_ivf_assign, 0 the
+ *                     general way (AUNCEL_AMD_ASSIGN_FUSED is the environment's form, and the only one that reaches the handle
+ *                     amd_ivf_kmeans makes for itself).  Cannot change a result
  * amd_ivf_set_option(h, key, NAN) returns the key to "unset".  May be called while search contexts of the index are searching: a
  * search reads what shapes its launches once, when it starts, so the change takes effect with the searches that start after it. */
 int amd_ivf_set_option(amd_ivf_t* h, const char* key, double value);
@@ -850,6 +854,26 @@ int amd_ivf_search_adaptive_dev(amd_ivf_t* h, size_t start, size_t n, size_t que
                                 const float* gt_D, int profile, int coarse_mode, uint64_t* my_nprobe, float* t_recalls, float* d_D,
                                 int64_t* d_I);
 int amd_ivf_last_dev_io(amd_ivf_t* h, uint64_t out[4]);
+
+/* ------------------------------------------------------------------------------------------------
+ * Index::assign: the nearest centroid of every row.  assign[i] and dis[i] (dis may be NULL) equal, bit for bit, the key and the
+ * distance of amd_ivf_coarse(h, n, x, 1, ., ., 0): the reference's distance, the lowest centroid number between equal distances, -1
+ * and +-FLT_MAX where the reference's heap admits nothing.  Up to 128 dimensions the rows go through one fused matrix-core pass that
+ * stores no distance matrix (ivf_assign.hip): fp16 products rank the centroids, the few that lie within the error bound
+ * of a row's minimum are recomputed in the reference's rounding sequence, and rows the pass cannot decide (more such centroids than
+ * slots, a value that is not finite, no usable fp16 scale) take the general path as a call of their own.  Beyond 128 dimensions the
+ * call takes the general path whole.
+ *   amd_ivf_assign_dev   rows and results in device memory: d_x, dtype, ldx and stream as in the `_dev` calls above, d_assign n int64
+ *                        (what amd_ivf_build_dev accepts as d_assign), d_dis n floats or NULL; the same refusals (-2)
+ *   amd_ivf_last_assign  the handle's last assignment: out[0] rows, out[1] rows decided by the fused pass, out[2] rows flagged and
+ *                        sent the general way, out[3] candidates recomputed.  A call served whole by the general path: {n, 0, n, 0}.
+ * Option "assign_fused" (AUNCEL_AMD_ASSIGN_FUSED) = 1 sends the exact rankings of length one inside amd_ivf_add, amd_ivf_build_dev and
+ * amd_ivf_kmeans (coarse mode 0) through the same pass; it cannot change a result.  0 is the default. */
+int amd_ivf_assign(amd_ivf_t* h, size_t n, const float* x, int64_t* assign, float* dis);
+int amd_ivf_assign_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, int64_t* d_assign, float* d_dis /* may be NULL */, void* stream);
+int amd_ivf_last_assign(amd_ivf_t* h, uint64_t out[4]);
+/* amd_ivf_last_assign's counters summed over the iterations of the calling thread's last amd_ivf_kmeans (whose handle is its own) */
+int amd_ivf_kmeans_last_assign(uint64_t out[4]);
 
 /* ------------------------------------------------------------------------------------------------
  * Dataset files of the reference's harness (Auncel/eval/bound.cpp:29-113; host only).  Buffers are malloc'ed
