@@ -990,7 +990,8 @@ class Handle:
     # ---- Index::assign (include/auncel_amd.h: amd_ivf_assign)
     def assign(self, x):
         """(assign int64 [n], dis float32 [n]): the nearest centroid of every row of x and the reference's distance to it -- bit for
-        bit the keys and distances of coarse(x, 1) -- by the fused matrix-core pass up to 128 dimensions"""
+        bit the keys and distances of coarse(x, 1) -- by the fused matrix-core pass up to 128 dimensions and, with
+        option "assign_wide" = 1, up to 1024"""
         x = f32(x)
         n = x.shape[0]
         a, dis = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.float32)

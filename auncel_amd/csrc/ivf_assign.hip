@@ -11,7 +11,8 @@
 //                          (distance, centroid) per row, the lowest centroid number between bit-equal distances -- what the
 //                          reference's heap of one, which admits only a strictly better value, keeps.
 // Rows the pass cannot decide -- more candidates than slots, a candidate distance that is not finite, a row without a usable fp16
-// scale -- are FLAGGED and listed; the caller sends them through coarse_dev (ivf_engine.hip: assign_fused).
+// scale -- are FLAGGED and listed; the caller sends them through coarse_dev (ivf_engine.hip: assign_fused).  Beyond 128 dimensions
+// assign_rows16_kernel + assign_wide_kernel (below) take assign_min_kernel's place; the table and the rescoring are the same.
 //
 // Split of work.  A workgroup of four waves owns 4 x QB x 32 rows for the whole sweep over the centroids.  A wave's rows are read
 // once, scaled and rounded to fp16 and kept in registers as the N operand (JP pieces of 4 VGPRs per 32-row block).  The centroid
@@ -41,6 +42,8 @@
 #include "mfma_tile.h"
 
 #include <algorithm>
+#include <stdexcept>
+#include <string>
 #include <type_traits>
 
 namespace amdivf {
@@ -245,6 +248,231 @@ void launch_assign_min(const AssignArgs& a, hipStream_t s) {
     if (a.n == 0) return;
     if (a.metric == METRIC_L2) launch_assign_min_jp<METRIC_L2, ASSIGN_QB>(a, s);
     else launch_assign_min_jp<METRIC_IP, ASSIGN_QB>(a, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Beyond 128 dimensions (option "assign_wide").  At J = assign_pieces(d) = 10 .. 64 pieces a wave cannot keep its
+// rows' fragments in registers (64 pieces x 4 VGPRs x QB), so the roles of assign_min_kernel's two operands in memory are swapped:
+// the ROWS are laid out as fragments, once per chunk of the call, and go through LDS; the centroid table streams into registers.
+//
+//   assign_rows16_kernel  a wave per block of 32 rows: the row's power of two, |x|^2 and the bad flag exactly as assign_min_kernel
+//                         computes them (the same lanes hold the same columns, the same fma chain), into an AssignRowRec; the
+//                         row as J pieces of 64 lanes x 16 bytes in the table's fragment order.  The rows are read twice (range,
+//                         then conversion): J x 8 floats a lane do not fit registers either.  Rows that pad the last workgroup's
+//                         128 are the chunk's last row again, so that every block a workgroup stages holds valid data.
+//   assign_wide_kernel    <METRIC, EMIT>, launched twice per chunk, on mfma_tile.h's WideTile: a workgroup owns 4 x 32 rows for the
+//                         whole sweep; tile t is centroid blocks 4 t .. 4 t + 3, wave w owns block 4 t + w, which streams from the
+//                         table into its ring of SP pieces (a slot refilled right behind its MFMAs; behind a tile's last stage
+//                         with the first pieces of the wave's block of the NEXT tile); the workgroup's rows go through LDS in
+//                         stages of SP pieces, double-buffered, wave w staging row block w, one lds_barrier() a stage; the stages
+//                         do not depend on the tile, so the buffers alternate along the whole sweep.  Straight-line code: a wave
+//                         whose block lies past the table recomputes the tile's first and drops the result, pieces at or past J
+//                         are staged as zero.  The tile epilogue is assign_min_kernel's, with the row's multiplier and threshold
+//                         read from two LDS tables.  EMIT = false leaves every row's minimum in wmin (the lane halves joined by a
+//                         shuffle, the four waves -- which saw different centroids of the same rows -- through LDS); EMIT = true
+//                         hands out the row's candidate slots through ONE LDS counter per row, shared by the four waves.
+// The bound is the narrow pass's at this d: C16 grows with d (exact_float_constant), nothing else changes -- DESIGN.md 18.1 says why
+// no partial sum overflows and why the eighth of eps still covers the rounding of the sum at 1024 products.
+#ifndef AUNCEL_ASSIGN_WIDE_SP
+#define AUNCEL_ASSIGN_WIDE_SP 6  // (as AUNCEL_EXACT_WIDE_SP, ivf_exact.hip)
+#endif
+constexpr int ASSIGN_WIDE_SP = AUNCEL_ASSIGN_WIDE_SP;
+constexpr int ASSIGN_WIDE_QB = (int)(ASSIGN_WIDE_ROWS / 32);
+constexpr size_t ASSIGN_WIDE_LDS = wide_lds_bytes(ASSIGN_WIDE_QB, ASSIGN_WIDE_SP, 3);  // (the stages + multiplier, threshold and counter per row)
+static_assert(ASSIGN_WIDE_QB == 4, "wave w stages row block w");
+static_assert(ASSIGN_WIDE_SP >= 2 && ASSIGN_WIDE_SP % 2 == 0 && ASSIGN_WIDE_SP <= 10, "pieces are taken in pairs; a stage is not longer than the fewest pieces");
+static_assert(2 * ASSIGN_WIDE_LDS <= 160 * 1024, "two workgroups per compute unit");
+
+__global__ __launch_bounds__(256) void assign_rows16_kernel(AssignArgs a, int J) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane & 31, hh = lane >> 5;
+    const size_t blk = (size_t)blockIdx.x * 4 + wave, r = blk * 32 + q;
+    const float* xr = a.x + (r < a.n ? r : a.n - 1) * (size_t)a.dpad;
+    // the lane's eight columns of piece j (dpad % 4 == 0: four columns are inside the row or outside together)
+    auto load = [&](int j, int w) {
+        const int col = 16 * j + 8 * hh + 4 * w;
+        const v4f t = *(gv4f)(uintptr_t)(xr + (col < a.dpad ? col : 0));
+        return col < a.dpad ? t : v4f{0.f, 0.f, 0.f, 0.f};
+    };
+    uint32_t mx = 0;
+    float sq = 0.f;
+    for (int j = 0; j < J; j++)
+#pragma unroll
+        for (int w = 0; w < 2; w++) {
+            const v4f raw = load(j, w);
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const float val = raw[e], av = fabsf(val);
+                const uint32_t bits = av == av ? __float_as_uint(av) : 0x7f800000u;  // (a NaN counts as an infinity)
+                mx = bits > mx ? bits : mx;
+                sq = __builtin_fmaf(val, val, sq);
+            }
+        }
+    const uint32_t mo = (uint32_t)__shfl_xor((int)mx, 32);
+    mx = mo > mx ? mo : mx;
+    sq += __shfl_xor(sq, 32);
+    // (assign_min_kernel's rule: largest magnitude in [2^(e-1), 2^e), e = be - 126, usable for -24 <= e <= 24, scale 2^(15 - e))
+    const uint32_t be = mx >> 23;
+    const bool bad = mx != 0 && (be < 102u || be > 150u);
+    const float sx = mx == 0 ? 1.f : __uint_as_float((268u - be) << 23), inv_sx = mx == 0 ? 1.f : __uint_as_float((be - 14u) << 23);
+    const float ps = inv_sx * a.inv_sy;  // (powers of two: exact)
+    float* out = a.rows16 + blk * (size_t)J * 256 + (size_t)lane * 4;
+    for (int j = 0; j < J; j++) {
+        v8h piece;
+#pragma unroll
+        for (int w = 0; w < 2; w++) {
+            const v4f raw = load(j, w);
+#pragma unroll
+            for (int e = 0; e < 4; e++) piece[4 * w + e] = bad ? (_Float16)0.f : (_Float16)(raw[e] * sx);
+        }
+        *reinterpret_cast<v8h*>(out + (size_t)j * 256) = piece;
+    }
+    if (hh == 0) a.rec[r] = AssignRowRec{sq, bad ? 0.f : a.metric == METRIC_L2 ? -2.f * ps : -ps, bad ? 1u : 0u, 0u};
+}
+
+template <int METRIC, bool EMIT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void assign_wide_kernel(AssignArgs a, int J) {
+    constexpr int QB = ASSIGN_WIDE_QB, SP = ASSIGN_WIDE_SP;
+    extern __shared__ __align__(16) unsigned char assign_wide_smem[];
+    float* s_a = reinterpret_cast<float*>(assign_wide_smem);  // [2 buffers][row block][piece of the stage][lane][4]
+    float* s_mul = s_a + 2 * wide_stage_words(QB, SP);
+    float* s_thr = s_mul + ASSIGN_WIDE_ROWS;
+    uint32_t* s_cnt = reinterpret_cast<uint32_t*>(s_thr + ASSIGN_WIDE_ROWS);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int q = lane & 31, hh = lane >> 5;
+    const int S = (J + SP - 1) / SP;
+    const uint32_t nblk = (a.nlist + 31) / 32, ntile = (nblk + 3) / 4;
+    const size_t block_floats = (size_t)J * 256 + 32;  // of the table: the pieces, then the 32 terms
+    const size_t rbase = (size_t)blockIdx.x * ASSIGN_WIDE_ROWS;
+
+    // ---- per row of the workgroup, once: multiplier, threshold, counter (slot = thread & 127: the upper two waves write what the
+    // lower two write).  A row past n is the copy of a valid one and is never written out; nothing of it may take a slot.
+    const uint32_t sl = threadIdx.x & (ASSIGN_WIDE_ROWS - 1);
+    const bool slive = rbase + sl < a.n;
+    const AssignRowRec rec = a.rec[rbase + sl];
+    bool sbad = rec.bad != 0;
+    s_mul[sl] = rec.mul;
+    s_cnt[sl] = 0;
+    if constexpr (EMIT) {
+        const float m = a.wmin[rbase + sl];
+        const float eps = METRIC == METRIC_L2 ? a.C * (rec.xn + a.cmax) : a.C * sqrtf(rec.xn) * sqrtf(a.cmax);
+        const float t = m + 2.125f * eps;
+        sbad = sbad || !(fabsf(t) < 3.0e38f);
+        s_thr[sl] = sbad || !slive ? -__builtin_inff() : t;
+    }
+    // ---- the row operand: this wave stages row block `wave` of the workgroup's four
+    const WideTile<TileAssign, SP, QB> tile{s_a, a.rows16 + (rbase / 32 + (size_t)wave) * (size_t)J * 256 + (size_t)lane * 4, J, wave, lane};
+    v4f st[SP];
+    tile.stage_load(0, st);
+    tile.stage_write(0, 0, st);
+    // ---- this wave's centroid block, a ring of SP pieces (a block past the table: the tile's first again)
+    const float* fbase = a.table + (size_t)lane * 4;
+    auto wave_block = [&](uint32_t t) { return 4 * t + (uint32_t)wave < nblk ? 4 * t + (uint32_t)wave : 4 * t; };
+    v4f br[SP];
+    {
+        const float* b0 = fbase + wave_block(0) * block_floats;
+#pragma unroll
+        for (int jj = 0; jj < SP; jj++) br[jj] = *(gv4f)(uintptr_t)(b0 + (size_t)jj * 256);  // (SP <= 10 <= J)
+    }
+    lds_barrier();  // stage 0 and the per-row tables are in LDS
+
+    float mn[QB];
+#pragma unroll
+    for (int qb = 0; qb < QB; qb++) mn[qb] = __builtin_inff();
+    int buf = 0;
+    for (uint32_t t = 0; t < ntile; t++) {
+        const bool active = 4 * t + (uint32_t)wave < nblk;
+        const uint32_t cur = wave_block(t);
+        const float* bbase = fbase + cur * block_floats;
+        const float* nbase = fbase + wave_block(t + 1 < ntile ? t + 1 : t) * block_floats;  // (no next tile: this one again, never used)
+        v4f term[4];  // of this lane's centroids 8 g + 4 hh .. + 3
+#pragma unroll
+        for (int g = 0; g < 4; g++) term[g] = *(gv4f)(uintptr_t)(a.table + cur * block_floats + (size_t)J * 256 + (size_t)(2 * g + hh) * 4);
+        v16f acc[QB];
+#pragma unroll
+        for (int qb = 0; qb < QB; qb++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[qb][r] = 0.f;
+        for (int s = 0; s < S; s++) {
+            const bool lasts = s + 1 == S;
+            // the refill of ring slot jj: piece j + SP of this block (past J: J - 1 again, multiplied by a zero stage slot), or behind
+            // the last stage piece jj of the wave's block of the next tile
+            auto refill = [&](int j, int jj, v4f& bv) __attribute__((always_inline)) {
+                const float* src = lasts ? nbase + (size_t)jj * 256 : bbase + (size_t)(j + SP < J ? j + SP : J - 1) * 256;
+                bv = *(gv4f)(uintptr_t)src;
+            };
+            tile.template stage<QB>(buf, s, lasts ? 0 : s + 1, st, acc, br, refill);  // (behind a tile's last stage: stage 0, for the next tile)
+            buf ^= 1;
+        }
+        // ---- epilogue: register r of lane (q, hh) of tile qb is centroid (r & 3) + 8 (r >> 2) + 4 hh of the block, row 32 qb + q
+#pragma unroll
+        for (int qb = 0; qb < QB; qb++) {
+            const float mul = s_mul[32 * qb + q];
+            float v[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) v[r] = __builtin_fmaf(mul, acc[qb][r], term[r >> 2][r & 3]);
+            float bm = v[0];
+#pragma unroll
+            for (int r = 1; r < 16; r++) bm = __builtin_fminf(bm, v[r]);
+            if constexpr (!EMIT) {
+                mn[qb] = __builtin_fminf(mn[qb], active ? bm : __builtin_inff());
+            } else {
+                const float thr = s_thr[32 * qb + q];
+                if (active && bm <= thr) {  // (rare: a block that holds a candidate of this row)
+                    const size_t row = rbase + 32 * qb + q;
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        const uint32_t c = cur * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                        if (v[r] <= thr && c < a.nlist) {
+                            const uint32_t slot = atomicAdd(&s_cnt[32 * qb + q], 1u);
+                            if (slot < ASSIGN_CAND && row < a.n) a.cand[row * ASSIGN_CAND + slot] = c;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (!EMIT) {
+        // the stage buffers are free behind the sweep's last barrier: [wave][row] minima
+#pragma unroll
+        for (int qb = 0; qb < QB; qb++) {
+            const float m = __builtin_fminf(mn[qb], __shfl_xor(mn[qb], 32));
+            if (hh == 0) s_a[wave * (int)ASSIGN_WIDE_ROWS + 32 * qb + q] = m;
+        }
+        __syncthreads();
+        if (threadIdx.x < ASSIGN_WIDE_ROWS && slive) {
+            float m = s_a[sl];
+#pragma unroll
+            for (int w = 1; w < 4; w++) m = __builtin_fminf(m, s_a[w * (int)ASSIGN_WIDE_ROWS + sl]);
+            a.wmin[rbase + sl] = m;
+        }
+    } else {
+        __syncthreads();
+        if (threadIdx.x < ASSIGN_WIDE_ROWS && slive) a.cnt[rbase + sl] = sbad ? ASSIGN_FLAG : s_cnt[sl];
+    }
+}
+
+size_t assign_wide_chunk_rows(int d) {
+    return ASSIGN_WIDE_WORKSPACE / ((size_t)assign_pieces(d) * 32) / ASSIGN_WIDE_ROWS * ASSIGN_WIDE_ROWS;  // (32 bytes a piece and row)
+}
+template <int METRIC, bool EMIT> static void launch_assign_wide_sweep(const AssignArgs& a, int J, hipStream_t s) {
+    void (*kern)(AssignArgs, int) = assign_wide_kernel<METRIC, EMIT>;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ASSIGN_WIDE_LDS);
+    if (e != hipSuccess) throw std::runtime_error(std::string("assign_wide_kernel: cannot reserve LDS: ") + hipGetErrorString(e));
+    LAUNCH(kern, dim3((unsigned)((a.n + ASSIGN_WIDE_ROWS - 1) / ASSIGN_WIDE_ROWS)), dim3(256), ASSIGN_WIDE_LDS, s, a, J);
+}
+void launch_assign_wide(const AssignArgs& a, hipStream_t s) {
+    if (a.n == 0) return;
+    const int J = (int)assign_pieces(a.d);
+    if (a.dpad <= ASSIGN_MAX_DPAD || a.dpad > ASSIGN_WIDE_MAX_DPAD || a.n > assign_wide_chunk_rows(a.d)) throw std::runtime_error("assign_wide_kernel: shape not supported");
+    LAUNCH(assign_rows16_kernel, dim3((unsigned)((a.n + ASSIGN_WIDE_ROWS - 1) / ASSIGN_WIDE_ROWS)), dim3(256), 0, s, a, J);
+    if (a.metric == METRIC_L2) {
+        launch_assign_wide_sweep<METRIC_L2, false>(a, J, s);
+        launch_assign_wide_sweep<METRIC_L2, true>(a, J, s);
+    } else {
+        launch_assign_wide_sweep<METRIC_IP, false>(a, J, s);
+        launch_assign_wide_sweep<METRIC_IP, true>(a, J, s);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -96,6 +96,8 @@ enum OptId {
                               // an absent probe -- no row, no scan; the probe still counts -- 0 it is scanned and masked out like any other
     OPT_ASSIGN_FUSED,   // exact rankings of length one (amd_ivf_add, amd_ivf_build_dev, amd_ivf_kmeans): 1 the fused matrix-core pass + rescoring
                         // (ivf_assign.hip), 0 (the default) the general way; amd_ivf_assign / amd_ivf_assign_dev always take the fused pass
+    OPT_ASSIGN_WIDE,    // ... beyond 128 dimensions (up to 1024), for amd_ivf_assign / amd_ivf_assign_dev and, with assign_fused, its callers: 1 the
+                        // workgroup-tiled fused pass (assign_wide_kernel), 0 (the default) the general way
     N_OPT
 };
 struct OptSpec {
@@ -129,6 +131,7 @@ const OptSpec OPT_TABLE[N_OPT] = {
     {"exact_wide_bytes", "AUNCEL_AMD_EXACT_WIDE_BYTES", nullptr},
     {"selected_skip_empty", "AUNCEL_AMD_SELECTED_SKIP_EMPTY", nullptr},
     {"assign_fused", "AUNCEL_AMD_ASSIGN_FUSED", nullptr},
+    {"assign_wide", "AUNCEL_AMD_ASSIGN_WIDE", nullptr},
 };
 struct Options {
     // (atomic: amd_ivf_set_option on the owner may run while search contexts cloned from it are searching; a search reads the
@@ -504,6 +507,7 @@ struct amd_ivf {
     std::mutex assign_mu;
     bool assign_call = false;
     DevBuf a_cand, a_cnt, a_flag;
+    DevBuf a_rows16, a_rec, a_wmin;  // the wide pass's chunk: the rows as fp16 fragments, their records, the first sweep's minima
     uint64_t last_assign[4] = {0, 0, 0, 0};  // rows, decided by the fused pass, flagged and sent the general way, candidates recomputed
     size_t coarse_picked = 0;       // rankings of the last coarse_dev call that came from coarse_pick_kernel
     DevBuf c_pick_flag, c_pick_x, c_pick_dis, c_pick_keys;  // coarse_pick_kernel: flagged queries and their exact re-run
@@ -1964,10 +1968,12 @@ void coarse_dev(amd_ivf* h, const float* d_x, size_t n, size_t nprobe, int mode,
 // The nearest centroid of n device rows by the fused matrix-core pass (ivf_assign.hip): the candidates of every row,
 // their distances in the reference's sequence, and the rows the pass could not decide through coarse_dev as a call of their own,
 // scattered back -- as the flagged rankings of coarse_pick_kernel are.  false: the pass does not serve this index (beyond
-// ASSIGN_MAX_DPAD dimensions, centroids without a usable fp16 scale) and nothing was launched.
+// ASSIGN_MAX_DPAD dimensions without option "assign_wide", beyond ASSIGN_WIDE_MAX_DPAD, centroids without a usable fp16 scale) and
+// nothing was launched.  The wide pass works through the call in chunks of rows, whose fp16 copy is its workspace.
 static bool assign_fused(amd_ivf* h, const float* d_x, size_t n, int mode, float* d_out_dis, int64_t* d_out_keys, int fused) {
     amd_ivf* idx = ix(h);
-    if (h->dpad > ASSIGN_MAX_DPAD || n >= (1ull << 32)) return false;
+    const bool wide = h->dpad > ASSIGN_MAX_DPAD;
+    if (n >= (1ull << 32) || (wide && (h->dpad > ASSIGN_WIDE_MAX_DPAD || opt(h, OPT_ASSIGN_WIDE, 0) == 0))) return false;
     hipStream_t s = h->stream;
     {
         std::lock_guard<std::mutex> lock(idx->assign_mu);
@@ -2008,8 +2014,25 @@ static bool assign_fused(amd_ivf* h, const float* d_x, size_t n, int mode, float
     a.out_keys = d_out_keys;
     a.stat = h->a_flag.as<uint32_t>();
     a.flagged = h->a_flag.as<uint32_t>() + 4;
+    const size_t chunk = wide ? std::min(assign_wide_chunk_rows(h->d), (n + ASSIGN_WIDE_ROWS - 1) / ASSIGN_WIDE_ROWS * ASSIGN_WIDE_ROWS) : 0;
+    if (wide) {
+        h->a_rows16.ensure(chunk * assign_pieces(h->d) * 32);
+        h->a_rec.ensure(chunk * sizeof(AssignRowRec));
+        h->a_wmin.ensure(chunk * 4);
+        a.rows16 = h->a_rows16.as<float>();
+        a.rec = h->a_rec.as<AssignRowRec>();
+        a.wmin = h->a_wmin.as<float>();
+    }
     const size_t timed = h->timer.begin(CAT_COARSE, s);
-    launch_assign_min(a, s);
+    if (!wide) launch_assign_min(a, s);
+    for (size_t r0 = 0; wide && r0 < n; r0 += chunk) {  // (stream order: a chunk's kernels are done with the workspace before the next's write it)
+        AssignArgs c = a;
+        c.x = d_x + r0 * (size_t)h->dpad;
+        c.n = std::min(chunk, n - r0);
+        c.cand = a.cand + r0 * ASSIGN_CAND;
+        c.cnt = a.cnt + r0;
+        launch_assign_wide(c, s);
+    }
     launch_assign_rescore(a, s);
     h->timer.end(timed, s);
     uint32_t stat[4] = {0, 0, 0, 0};
@@ -5066,7 +5089,7 @@ static int opt_id(const char* key) {
 static double opt_default(OptId id) {
     switch (id) {
         case OPT_COARSE_TIES: case OPT_TIE_FIX: case OPT_PHASE_TIMING: return -1;
-        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: case OPT_EXACT_FLOAT: case OPT_EXACT_WIDE: case OPT_EXACT_WIDE_BYTES: case OPT_ASSIGN_FUSED: return 0;  // (0: chosen per search)
+        case OPT_FIXED_ROUNDS: case OPT_ROUND_INC: case OPT_ROUND_GROW: case OPT_EXACT_FLOAT: case OPT_EXACT_WIDE: case OPT_EXACT_WIDE_BYTES: case OPT_ASSIGN_FUSED: case OPT_ASSIGN_WIDE: return 0;  // (0: chosen per search)
         case OPT_ROUND_FIRST: return 12;
         case OPT_SCAN_PIPELINED: return 7;
         case OPT_FILTER: case OPT_COARSE_PICK: return 2;

@@ -821,14 +821,26 @@ void launch_ingest_rows(const void* x, int dtype, size_t n, int d, int dpad, siz
 constexpr uint32_t ASSIGN_CAND = 8;     // candidate slots a row: a row with more centroids within the error bound of its minimum is flagged
 constexpr int ASSIGN_MAX_DPAD = 128;    // a wave keeps its rows' fp16 pieces in registers up to here
 constexpr int ASSIGN_QB = 2;            // 32-row blocks a wave (the register / LDS table)
+// beyond ASSIGN_MAX_DPAD (option "assign_wide"): the rows go through LDS as the other MFMA operand, laid out as fp16
+// fragments chunk by chunk of the call so that the copy stays below ASSIGN_WIDE_WORKSPACE bytes
+constexpr int ASSIGN_WIDE_MAX_DPAD = 1024;
+constexpr uint32_t ASSIGN_WIDE_ROWS = 128;                 // rows a workgroup owns; a chunk is a multiple of it
+constexpr size_t ASSIGN_WIDE_WORKSPACE = (size_t)256 << 20;
 // 16-dimension pieces a centroid takes in the table (an even count), the table's bytes, and the table itself from the centroid rows:
 // fp16(sy * value) in MFMA fragment order, a block of 32 centroids followed by its 32 terms (|c|^2 under L2, 0 under the inner
 // product, +inf for the centroids that pad the last block).  sy: the power of two of the centroids' range (filter_half_scale), not 0
 uint32_t assign_pieces(int d);
 size_t assign_table_bytes(uint32_t nlist, int d);
 void launch_assign_table(const float* centroids, uint32_t nlist, int d, int dpad, int metric, float sy, float* table, hipStream_t s);
+// what the wide pass keeps of a row beside its fp16 pieces
+struct AssignRowRec {
+    float xn;                // |x|^2: assign_min_kernel's fma chain over the fp32 values
+    float mul;               // -2 / (sx sy) (L2), -1 / (sx sy) (inner product); 0 for a bad row, whose pieces are zeros
+    uint32_t bad;            // a NaN, an infinity or a magnitude outside 2^+-24: the row is flagged
+    uint32_t pad;
+};
 struct AssignArgs {
-    const float* x;          // n rows, stride dpad (<= ASSIGN_MAX_DPAD), zero padded
+    const float* x;          // n rows, stride dpad (<= ASSIGN_WIDE_MAX_DPAD), zero padded
     size_t n;
     const float* table;      // launch_assign_table
     const float* centroids;  // nlist rows, stride dpad: the rescoring's operand
@@ -843,9 +855,17 @@ struct AssignArgs {
     int64_t* out_keys;       // n: ... the nearest centroid, of the rows that are not flagged
     uint32_t* stat;          // [0] += flagged rows, [2..3] (64 bits) += candidates recomputed; zeroed by the caller
     uint32_t* flagged;       // [n] their numbers, in no order
+    // the wide pass (128 < dpad <= ASSIGN_WIDE_MAX_DPAD), per chunk of rows; n rounded up to ASSIGN_WIDE_ROWS = np
+    float* rows16;           // np / 32 blocks of assign_pieces(d) pieces: the rows as scaled fp16 MFMA fragments (launch_assign_rows16)
+    AssignRowRec* rec;       // np
+    float* wmin;             // np: the first sweep's minimum of every row
 };
 // every centroid that can be a row's exact nearest into cand / cnt (no distance is stored) ...
 void launch_assign_min(const AssignArgs& a, hipStream_t s);
+// the same for 128 < dpad <= ASSIGN_WIDE_MAX_DPAD, of one chunk of rows (a.n <= assign_wide_chunk_rows(a.d)): the rows' fragments
+// and records, then the two sweeps (minimum, candidates)
+size_t assign_wide_chunk_rows(int d);
+void launch_assign_wide(const AssignArgs& a, hipStream_t s);
 // ... and the best of them by the reference's own distance; rows it cannot decide are flagged
 void launch_assign_rescore(const AssignArgs& a, hipStream_t s);
 

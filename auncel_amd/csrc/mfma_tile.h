@@ -1,6 +1,6 @@
 // The matrix-core tile of the list passes (gfx950): the operand types, and the workgroup tile beyond 128 dimensions that
 // scan_filter_wide_kernel (ivf_filter.hip: fp16 / fp32), scan_all_wide_f16_kernel and scan_all_wide_i8_kernel (ivf_exact.hip: fp16,
-// int8) are built from.
+// int8) and assign_wide_kernel (ivf_assign.hip: fp16, the operands' roles swapped) are built from.
 //
 // The workgroup tile.  Four waves share up to QB query blocks of 32 rows.  Wave w owns one 32-vector block of the list, whose pieces
 // (1 KiB: 64 lanes x 16 bytes) stream from HBM once, straight into a register ring of SP pieces: the slot of a piece is refilled
@@ -71,6 +71,21 @@ template <bool HALF> struct TileFloat {
 #pragma unroll
                 for (int q = 0; q < NQB; q++) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q][e], bv[e], acc[q], 0, 0, 0);
         }
+    }
+};
+// The assignment's operands (ivf_assign.hip: assign_wide_kernel): fp16 with the two arguments swapped -- the ring's block (centroids)
+// is M and the staged rows are N, so a lane's 16 accumulators are 16 centroids of ONE row -- and the staged rows are themselves
+// laid out in fragment order: a lane's pieces lie one KiB apart.
+struct TileAssign {
+    typedef float word;
+    typedef v4f vec;
+    typedef gv4f gvec;
+    typedef v16f acc_t;
+    typedef float row;
+    static constexpr int step = 256;
+    template <int NQB> static __device__ __forceinline__ void mac(v16f* acc, const v4f (&af)[NQB], const v4f& bv) {
+#pragma unroll
+        for (int q = 0; q < NQB; q++) filter_mac<true>(acc[q], bv, af[q]);
     }
 };
 struct TileI8 {

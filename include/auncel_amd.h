@@ -815,6 +815,10 @@ int amd_ivf_set_byte_codes(amd_ivf_t* h, int enable);
  *                     without d_assign, amd_ivf_kmeans, coarse mode 0): 1 the fused matrix-core pass of amd_ivf_assign, 0 the
  *                     general way (AUNCEL_AMD_ASSIGN_FUSED is the environment's form, and the only one that reaches the handle
  *                     amd_ivf_kmeans makes for itself).  Cannot change a result
+ *   "assign_wide"     ... beyond 128 dimensions (128 < d <= 1024): 1 amd_ivf_assign / amd_ivf_assign_dev and, beside                0
+ *                     "assign_fused" = 1, its callers take the workgroup-tiled fused pass (the rows as fp16 fragments through
+ *                     LDS, chunk by chunk of the call), 0 the general way for the whole call (AUNCEL_AMD_ASSIGN_WIDE is the
+ *                     environment's form, and the only one that reaches amd_ivf_kmeans' own handle).  Cannot change a result
  * amd_ivf_set_option(h, key, NAN) returns the key to "unset".  May be called while search contexts of the index are searching: a
  * search reads what shapes its launches once, when it starts, so the change takes effect with the searches that start after it. */
 int amd_ivf_set_option(amd_ivf_t* h, const char* key, double value);
@@ -861,14 +865,17 @@ int amd_ivf_last_dev_io(amd_ivf_t* h, uint64_t out[4]);
  * and +-FLT_MAX where the reference's heap admits nothing.  Up to 128 dimensions the rows go through one fused matrix-core pass that
  * stores no distance matrix (ivf_assign.hip): fp16 products rank the centroids, the few that lie within the error bound
  * of a row's minimum are recomputed in the reference's rounding sequence, and rows the pass cannot decide (more such centroids than
- * slots, a value that is not finite, no usable fp16 scale) take the general path as a call of their own.  Beyond 128 dimensions the
- * call takes the general path whole.
+ * slots, a value that is not finite, no usable fp16 scale) take the general path as a call of their own.  Beyond 128 dimensions, up
+ * to 1024, option "assign_wide" = 1 gives the same pass as a workgroup tile (the rows laid out as fp16 fragments chunk
+ * by chunk and staged through LDS, the centroids streamed into registers; the same contract, the same counters); without it, and
+ * beyond 1024 dimensions, the call takes the general path whole.
  *   amd_ivf_assign_dev   rows and results in device memory: d_x, dtype, ldx and stream as in the `_dev` calls above, d_assign n int64
  *                        (what amd_ivf_build_dev accepts as d_assign), d_dis n floats or NULL; the same refusals (-2)
  *   amd_ivf_last_assign  the handle's last assignment: out[0] rows, out[1] rows decided by the fused pass, out[2] rows flagged and
  *                        sent the general way, out[3] candidates recomputed.  A call served whole by the general path: {n, 0, n, 0}.
  * Option "assign_fused" (AUNCEL_AMD_ASSIGN_FUSED) = 1 sends the exact rankings of length one inside amd_ivf_add, amd_ivf_build_dev and
- * amd_ivf_kmeans (coarse mode 0) through the same pass; it cannot change a result.  0 is the default. */
+ * amd_ivf_kmeans (coarse mode 0) through the same pass -- beyond 128 dimensions together with "assign_wide" = 1; neither can change
+ * a result.  0 is the default of both. */
 int amd_ivf_assign(amd_ivf_t* h, size_t n, const float* x, int64_t* assign, float* dis);
 int amd_ivf_assign_dev(amd_ivf_t* h, size_t n, const void* d_x, int dtype, size_t ldx, int64_t* d_assign, float* d_dis /* may be NULL */, void* stream);
 int amd_ivf_last_assign(amd_ivf_t* h, uint64_t out[4]);

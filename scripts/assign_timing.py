@@ -4,8 +4,9 @@ auncel_amd/synth.py, IVF4096, as a torch tensor on the device.  Per case, in one
 REPS calls after one warm-up call each: amd_ivf_build_dev with the option 0 and 1, and amd_ivf_assign_dev alone (always the fused
 pass; its assignment is compared with the option-0 build's list sizes).  Then amd_ivf_kmeans (1M x 128, k = 4096, 5 iterations),
 AUNCEL_AMD_ASSIGN_FUSED unset and set, alternating (its handle is its own: the environment is what reaches it).  Host clocks
-around calls that return after the engine's stream has finished.  One JSON line per case.
-usage: python3 scripts/assign_timing.py [--nb N] [--case sift|deep|kmeans] [--reps R] [--nk N]"""
+around calls that return after the engine's stream has finished.  Case "gist": the GIST-like set (1M x 960, L2), "assign_fused" and
+"assign_wide" both 0 against both 1 in build_dev, assign_dev and amd_ivf_kmeans (section 18.1).  One JSON line per case.
+usage: python3 scripts/assign_timing.py [--nb N] [--case sift|deep|gist|kmeans] [--reps R] [--nk N] [--ng N]"""
 import json
 import os
 import statistics
@@ -21,6 +22,7 @@ from auncel_amd import capi, synth  # noqa: E402
 args = sys.argv[1:]
 NB = int(args[args.index("--nb") + 1]) if "--nb" in args else 10_000_000
 NK = int(args[args.index("--nk") + 1]) if "--nk" in args else 1_000_000
+NG = int(args[args.index("--ng") + 1]) if "--ng" in args else 1_000_000
 REPS = int(args[args.index("--reps") + 1]) if "--reps" in args else 3
 ONLY = args[args.index("--case") + 1] if "--case" in args else None
 NLIST = 4096
@@ -72,6 +74,45 @@ for name, make, d, metric in CASES:
                       "fused_mfma_flops": flops, "fused_table_bytes_into_lds": lds_fill}), flush=True)
     q.close()
     del x, a
+
+if not ONLY or ONLY == "gist":
+    # beyond 128 dimensions: "assign_fused" and "assign_wide" both 0 (the general path: what every such call
+    # launched before the wide pass existed) against both 1, alternating -- build_dev, assign_dev alone, then amd_ivf_kmeans under the
+    # two environment variables
+    d = 960
+    xb, _ = synth.gist_like(NG, 1, d=d)
+    q = capi.Handle(d, NLIST, capi.METRIC_L2, 0)
+    q.set_centroids(synth.sample_centroids(xb, NLIST))
+    x = torch.from_numpy(xb).cuda()
+    ms = {(w, on): [] for w in ("build", "assign", "kmeans") for on in (0, 1)}
+    digest, got, last, cen = {}, {}, {}, {}
+    for rep in range(REPS + 1):
+        for on in (0, 1):
+            q.set_option("assign_fused", on)
+            q.set_option("assign_wide", on)
+            t, b = timed(lambda: q.build_dev(x))
+            digest[on], last["build", on] = b.layout_digest(), q.last_assign()
+            b.close()
+            t2, (got[on], _) = timed(lambda: q.assign_dev(x))
+            last["assign", on] = q.last_assign()
+            for k in ("AUNCEL_AMD_ASSIGN_FUSED", "AUNCEL_AMD_ASSIGN_WIDE"):
+                os.environ.pop(k, None)
+                if on:
+                    os.environ[k] = "1"
+            t3, (cen[on], _) = timed(lambda: capi.kmeans(capi.METRIC_L2, xb, NLIST, niter=5))
+            last["kmeans", on] = capi.kmeans_last_assign()
+            if rep:
+                ms["build", on].append(t), ms["assign", on].append(t2), ms["kmeans", on].append(t3)
+    jp = (((d + 15) // 16) + 1) & ~1
+    print(json.dumps({"case": "gist", "nb": NG, "d": d, "nlist": NLIST, "reps": REPS, **{f"{w}_ms_{'on' if on else 'off'}": med(v) for (w, on), v in ms.items()},
+                      "all_ms": {f"{w}_{on}": [round(t, 1) for t in v] for (w, on), v in ms.items()}, "same_layout": digest[0] == digest[1],
+                      "same_assignment": bool(torch.equal(got[0], got[1])), "same_centroids": bool(np.array_equal(cen[0].view(np.uint32), cen[1].view(np.uint32))),
+                      "last_assign_on": {w: last[w, 1] for w in ("build", "assign", "kmeans")}, "wide_mfma_flops": 2 * 2.0 * NG * NLIST * 16 * jp,
+                      "wide_bytes_from_l2_per_sweep": 1.0 * ((NG + 127) // 128) * ((NLIST + 127) // 128) * 2 * 128 * jp * 32}), flush=True)
+    q.close()
+    del x, xb, got
+    for k in ("AUNCEL_AMD_ASSIGN_FUSED", "AUNCEL_AMD_ASSIGN_WIDE"):
+        os.environ.pop(k, None)
 
 if not ONLY or ONLY == "kmeans":
     xk, _ = synth.sift_like(NK, 1, d=128)
