@@ -49,7 +49,7 @@ SYMBOLS = [
     "amd_ivf_search_and_reconstruct", "amd_ivf_search_and_reconstruct_resident",
     "amd_ivf_set_queries_dev", "amd_ivf_search_dev", "amd_ivf_search_preassigned_dev", "amd_ivf_search_resident_dev",
     "amd_ivf_search_exact_dev", "amd_ivf_search_adaptive_dev", "amd_ivf_last_dev_io",
-    "amd_ivf_assign", "amd_ivf_assign_dev", "amd_ivf_last_assign", "amd_ivf_kmeans_last_assign",
+    "amd_ivf_assign", "amd_ivf_assign_dev", "amd_ivf_last_assign", "amd_ivf_kmeans_last_assign", "amd_ivf_kmeans_dev",
     "amd_ivf_read_fvecs", "amd_ivf_read_ivecs", "amd_ivf_read_fbin", "amd_ivf_read_ibin", "amd_ivf_free",
 ]
 
@@ -181,6 +181,27 @@ def kmeans(metric, x, k, niter=25, seed=1234, max_points_per_centroid=256, spher
     _chk(lib().amd_ivf_kmeans(int(d), C.c_size_t(n), _f(x), C.c_size_t(k), int(metric), int(niter), C.c_long(seed),
                               C.c_size_t(max_points_per_centroid), int(spherical), int(int_centroids), int(coarse_mode), int(device),
                               _f(cen), _f(obj)))
+    return cen, obj
+
+
+def kmeans_dev(metric, x, k, niter=25, seed=1234, max_points_per_centroid=256, spherical=False, int_centroids=False, coarse_mode=0):
+    """kmeans() for an [n, d] fp32 / fp16 tensor on a GPU (rows may be strided; include/auncel_amd.h: amd_ivf_kmeans_dev) ->
+    (centroids, a (k, d) float32 tensor on x's device; objective per iteration, numpy).  Ordered behind the current torch stream;
+    complete on return."""
+    import torch
+    if not (x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.float16)):
+        raise ValueError("x must be a float32 or float16 [n, d] tensor on a GPU")
+    n, d = x.shape
+    if d > 1 and x.stride(1) != 1:
+        raise ValueError("the columns of x must be contiguous (x.stride(1) == 1)")
+    ldx = x.stride(0) if n > 1 else max(x.stride(0), d)  # (the stride of a single row means nothing)
+    dev = x.device.index
+    cen = torch.zeros((k, d), dtype=torch.float32, device=x.device)
+    obj = np.zeros(niter, np.float32)
+    _chk(lib().amd_ivf_kmeans_dev(int(d), C.c_size_t(n), C.c_void_p(x.data_ptr()), 0 if x.dtype == torch.float32 else 1, C.c_size_t(ldx),
+                                  C.c_size_t(k), int(metric), int(niter), C.c_long(seed), C.c_size_t(max_points_per_centroid),
+                                  int(spherical), int(int_centroids), int(coarse_mode), int(dev), C.c_void_p(cen.data_ptr()), _f(obj),
+                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return cen, obj
 
 

@@ -7402,6 +7402,166 @@ int amd_ivf_last_assign(amd_ivf_t* h, uint64_t out[4]) {
     API_END
 }
 
+// amd_ivf_set_centroids for the handle amd_ivf_kmeans_dev makes for itself, from k x d compact centroids in device memory: the
+// padded table, the row norms, the fp16 range (d_cinfo), centroid_norm_max -- the same double sum in element order, max over the
+// rows, times 1 + 1e-6 -- and the IntRange, without h_centroids.  What chooses the next assignment's arithmetic on the host comes
+// back in one copy of 24 bytes, with the call's error flags (d_state: launch_kmeans_dev_install), which are returned.
+static uint32_t install_centroids_dev(amd_ivf* h, const float* d_cen, uint32_t* d_state) {
+    hipStream_t s = h->stream;
+    h->d_centroids.ensure(h->nlist * h->dpad * sizeof(float));
+    h->d_centroid_norms.ensure(h->nlist * sizeof(float));
+    h->d_cinfo.ensure(16);
+    launch_kmeans_dev_install(d_cen, (uint32_t)h->nlist, h->d, h->dpad, h->d_centroids.as<float>(), d_state, h->d_cinfo.as<uint32_t>(), s);
+    launch_row_norms(h->d_centroids.as<float>(), h->nlist, h->dpad, h->d_centroid_norms.as<float>(), s);
+    launch_amax(h->d_centroids.as<float>(), h->nlist, h->dpad, h->d_cinfo.as<uint32_t>(), s);
+    uint32_t got[6];
+    HIP_CHECK(hipMemcpyAsync(got, d_state, sizeof got, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(stream_sync(s));
+    h->have_centroids = true;
+    h->have_interdis = false;
+    h->assign_table_valid = false;
+    double mx;
+    memcpy(&mx, got + 4, 8);
+    h->centroid_norm_max = (float)(mx * (1.0 + 1e-6));
+    h->centroid_range.ok = got[0] == 0;
+    h->centroid_range.lo = subset_range_value(got[1]);
+    h->centroid_range.hi = subset_range_value(got[2]);
+    return got[3];
+}
+
+// amd_ivf_kmeans with the training rows taken from device memory: the same permutations on the host, because they
+// are mt19937 by definition, and everything between two assignment passes as kernels on the handle's stream (ivf_kmeans_dev.hip).
+// Inside the loop the host reads 24 bytes an iteration (install_centroids_dev) beside what the assignment itself reads back.
+int amd_ivf_kmeans_dev(int d, size_t n, const void* d_x, int dtype, size_t ldx, size_t k, int metric, int niter, long seed,
+                       size_t max_points_per_centroid, int spherical, int int_centroids, int coarse_mode, int device, float* d_centroids, float* obj,
+                       void* stream) {
+    API_BEGIN
+    for (uint64_t& v : g_kmeans_assign) v = 0;
+    namespace km = amdivf_kmeans;
+    if (!d_x || !d_centroids) throw EngineError("kmeans_dev: null pointer");
+    if (d <= 0 || k == 0) throw EngineError("bad dimension / k");
+    if (n < k) throw EngineError("Number of training points should be at least as large as number of clusters");
+    if (n > (size_t)INT_MAX) throw EngineError("kmeans_dev: more training points than the reference's int permutation numbers");
+    if (max_points_per_centroid == 0) throw EngineError("max_points_per_centroid must be positive");
+    if (dev_dtype_size(dtype) == 0) throw EngineError("kmeans_dev: dtype must be 0 (fp32) or 1 (fp16)");
+    if (ldx < (size_t)d) throw EngineError("kmeans_dev: ldx must be at least d");
+    require_device();
+    amd_ivf_t* raw = nullptr;
+    if (const int rc = amd_ivf_create(d, k, metric, device, &raw)) {
+        if (rc == -2) throw EngineError(g_last_error);
+        throw std::runtime_error(g_last_error);
+    }
+    std::unique_ptr<amd_ivf> h(raw);
+    use_device(h.get());
+    {
+        std::string bad = dev_rows_error(d_x, dev_ptr_kind(h.get(), d_x), dtype, ldx, (size_t)d);
+        if (bad.empty()) bad = dev_ptr_error("d_centroids", d_centroids, dev_ptr_kind(h.get(), d_centroids), sizeof(float));
+        if (!bad.empty()) throw EngineError("kmeans_dev: " + bad);
+    }
+    // the fused assignment passes, unless the environment says 0: they cannot change a result, and no other call makes this handle
+    for (OptId id : {OPT_ASSIGN_FUSED, OPT_ASSIGN_WIDE})
+        if (!h->opt.is_set(id)) h->opt.v[id].store(1, std::memory_order_relaxed);
+    hipStream_t s = h->stream;
+    const int dpad = h->dpad;
+    wait_for_caller(h.get(), stream);
+    DevBuf b_state, b_perm, b_perm2, d_dis, d_keys, b_keys, b_total, b_off, b_boff, b_cnt, b_rank, b_run, b_idx, b_order, b_pop, b_obj;
+    // 8 words of the centroids' state (launch_kmeans_dev_install), then the sample's range and, in its fourth word, the finite flag
+    const uint32_t key0 = subset_range_key(0.f);
+    const uint32_t init[16] = {0, key0, key0, 0, 0, 0, 0, 0, 0, key0, key0, 0, 0, 0, 0, 0};
+    b_state.ensure(sizeof init);
+    HIP_CHECK(hipMemcpyAsync(b_state.p, init, sizeof init, hipMemcpyHostToDevice, s));
+    uint32_t* state = b_state.as<uint32_t>();
+    uint32_t* srange = state + 8;
+    // the reference checks the whole input before it sub-samples (Clustering.cpp:85-89): one reduction over the caller's tensor,
+    // which runs while the host draws the permutations
+    launch_kmeans_dev_finite(d_x, dtype, n, d, ldx, srange + 3, s);
+    size_t nx = n;
+    std::vector<int> perm, perm2;
+    const bool sub = (n - 1) / k >= max_points_per_centroid;  // (n > k * max_points_per_centroid, without the product)
+    if (sub) {
+        perm.resize(n);
+        km::rand_perm(perm.data(), n, seed);
+        nx = k * max_points_per_centroid;
+    }
+    uint32_t got[4] = {0, 0, 0, 0};
+    if (nx == k) {  // the reference's corner case: the first k rows of the input become the centroids
+        HIP_CHECK(hipMemcpyAsync(got, srange, 16, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(stream_sync(s));
+        if (got[3]) throw EngineError("input contains NaN's or Inf's");
+        launch_kmeans_dev_rows(d_x, dtype, ldx, d, nullptr, k, d_centroids, s);
+        HIP_CHECK(stream_sync(s));
+        return 0;
+    }
+    if (sub) {
+        b_perm.ensure(nx * sizeof(int));
+        HIP_CHECK(hipMemcpyAsync(b_perm.p, perm.data(), nx * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    h->d_resident.ensure(nx * dpad * sizeof(float));
+    float* sample = h->d_resident.as<float>();
+    launch_kmeans_dev_sample(d_x, dtype, ldx, d, dpad, sub ? b_perm.as<int>() : nullptr, nx, sample, srange, s);
+    perm2.resize(nx);
+    km::rand_perm(perm2.data(), nx, seed + 1);
+    HIP_CHECK(hipMemcpyAsync(got, srange, 16, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(stream_sync(s));
+    if (got[3]) throw EngineError("input contains NaN's or Inf's");
+    IntRange qr;
+    qr.ok = got[0] == 0;
+    qr.lo = subset_range_value(got[1]);
+    qr.hi = subset_range_value(got[2]);
+    b_perm2.ensure(k * sizeof(int));
+    HIP_CHECK(hipMemcpyAsync(b_perm2.p, perm2.data(), k * sizeof(int), hipMemcpyHostToDevice, s));
+    launch_kmeans_dev_rows(sample, 0, (uint64_t)dpad, d, b_perm2.as<int>(), k, d_centroids, s);
+    launch_kmeans_dev_post(d_centroids, (uint32_t)k, d, spherical, int_centroids, s);
+
+    const uint64_t tiles_all = (nx + BUILD_TILE - 1) / BUILD_TILE;
+    const uint64_t per_chunk = build_chunk_tiles(nx, k, BUILD_TILE, BUILD_CHUNK_BYTES, 0);
+    if (niter > 0) {
+        d_dis.ensure(nx * 4);
+        d_keys.ensure(nx * 8);
+        b_keys.ensure(nx * 4);
+        b_total.ensure(k * 8);
+        b_off.ensure((k + 1) * 8);
+        b_boff.ensure((k + 1) * 8);
+        b_cnt.ensure(per_chunk * k * 4);
+        b_rank.ensure(per_chunk * BUILD_TILE * 2);
+        b_run.ensure(k * 4);
+        b_idx.ensure(nx * 4);
+        b_order.ensure(k * 4);
+        b_pop.ensure(k * 4);
+        b_obj.ensure((size_t)niter * 4);
+    }
+    const char* outside = "k-means: the assignment step returned a centroid number outside [0, k)";
+    for (int it = 0; it < niter; it++) {
+        if (install_centroids_dev(h.get(), d_centroids, state)) throw EngineError(outside);
+        coarse_dev(h.get(), sample, nx, 1, coarse_mode, d_dis.as<float>(), d_keys.as<int64_t>(),
+                   h->allow_fused && h->centroid_range.fusable_with(qr, h->metric));
+        for (int i = 0; i < 4; i++) g_kmeans_assign[i] += h->last_assign[i];
+        if (obj) launch_kmeans_dev_objective(d_dis.as<float>(), nx, b_obj.as<float>() + it, s);
+        // the points grouped by centroid in ascending point number: the build's stable counting sort, offsets left on the device
+        HIP_CHECK(hipMemsetAsync(b_total.p, 0, k * 8, s));
+        HIP_CHECK(hipMemsetAsync(b_run.p, 0, k * 4, s));
+        launch_build_keys(d_keys.as<int64_t>(), nx, (uint32_t)k, b_keys.as<uint32_t>(), b_total.as<unsigned long long>(), state + 3, s);
+        launch_build_offsets(b_total.as<unsigned long long>(), (uint32_t)k, b_off.as<uint64_t>(), b_boff.as<uint64_t>(), state + 3, s);
+        for (uint64_t t0 = 0; t0 < tiles_all; t0 += per_chunk) {
+            const uint32_t ntiles = (uint32_t)std::min<uint64_t>(per_chunk, tiles_all - t0);
+            HIP_CHECK(hipMemsetAsync(b_cnt.p, 0, (size_t)ntiles * k * 4, s));
+            launch_build_count(b_keys.as<uint32_t>(), nx, t0 * BUILD_TILE, ntiles, (uint32_t)k, b_rank.as<uint16_t>(), b_cnt.as<uint32_t>(), s);
+            launch_build_scan(b_cnt.as<uint32_t>(), ntiles, (uint32_t)k, b_run.as<uint32_t>(), s);
+            launch_kmeans_dev_place(b_keys.as<uint32_t>(), b_rank.as<uint16_t>(), b_cnt.as<uint32_t>(), b_off.as<uint64_t>(), nx, t0 * BUILD_TILE,
+                                    ntiles, (uint32_t)k, b_idx.as<uint32_t>(), state + 3, s);
+        }
+        launch_kmeans_dev_update(sample, dpad, d, b_idx.as<uint32_t>(), b_off.as<uint64_t>(), (uint32_t)k, b_order.as<uint32_t>(), d_centroids, s);
+        launch_kmeans_dev_split(d_centroids, b_total.as<unsigned long long>(), (uint32_t)k, d, nx, b_pop.as<uint32_t>(), state + 3, s);
+        launch_kmeans_dev_post(d_centroids, (uint32_t)k, d, spherical, int_centroids, s);
+    }
+    uint32_t flags = 0;
+    HIP_CHECK(hipMemcpyAsync(&flags, state + 3, 4, hipMemcpyDeviceToHost, s));
+    if (obj && niter > 0) HIP_CHECK(hipMemcpyAsync(obj, b_obj.p, (size_t)niter * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(stream_sync(s));
+    if (flags) throw EngineError(outside);
+    API_END
+}
+
 int amd_ivf_last_dev_io(amd_ivf_t* h, uint64_t out[4]) {
     API_BEGIN
     if (!h || !out) throw EngineError("last_dev_io: null argument");

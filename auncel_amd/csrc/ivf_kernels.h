@@ -782,6 +782,33 @@ struct BuildPlaceArgs {
     uint32_t* range;
 };
 void launch_build_place(const BuildPlaceArgs& a, hipStream_t s);
+// ---------------------------------------------------------------------------- k-means from device rows (ivf_kmeans_dev.hip)
+// amd_ivf_kmeans_dev.  Every array is device memory; x / dtype / ldx as launch_build_place's.
+// *flag |= 1 when any of the n x d elements is a NaN or an infinity
+void launch_kmeans_dev_finite(const void* x, int dtype, uint64_t n, int d, uint64_t ldx, uint32_t* flag, hipStream_t s);
+// sample row i (fp32, stride dpad, zero padded) <- row perm[i] of x (perm null: row i); range as launch_subset_compact's
+void launch_kmeans_dev_sample(const void* x, int dtype, uint64_t ldx, int d, int dpad, const int* perm, uint64_t nx, float* out, uint32_t* range,
+                              hipStream_t s);
+// m compact rows of d floats <- rows perm[i] (perm null: i) of x
+void launch_kmeans_dev_rows(const void* x, int dtype, uint64_t ldx, int d, const int* perm, uint64_t m, float* out, hipStream_t s);
+// k x d compact centroids -> k x dpad padded; state (8 words) is started here but for word 3: 0..2 the values' range as
+// launch_subset_compact's, 3 the call's error flags, 4..5 the bits of the largest row's double sum of squares in element order;
+// cinfo: launch_amax's four words, zeroed
+void launch_kmeans_dev_install(const float* cen, uint32_t k, int d, int dpad, float* out, uint32_t* state, uint32_t* cinfo, hipStream_t s);
+// the place step of the build's counting sort for point numbers alone: idx_sorted[list_off[key] + before + rank] = i; a point
+// without a key (an assignment outside [0, nlist)) raises *flags
+void launch_kmeans_dev_place(const uint32_t* keys, const uint16_t* rank, const uint32_t* before, const uint64_t* list_off, uint64_t n, uint64_t row0,
+                             uint32_t ntiles, uint32_t nlist, uint32_t* idx_sorted, uint32_t* flags, hipStream_t s);
+// cen[c] = fp32 sum of sample rows idx_sorted[list_off[c] .. list_off[c + 1]) in that order / their count, 0 for an empty run;
+// order: k words of workspace (the centroids, long runs first)
+void launch_kmeans_dev_update(const float* x, int dpad, int d, const uint32_t* idx_sorted, const uint64_t* list_off, uint32_t k, uint32_t* order,
+                              float* cen, hipStream_t s);
+// kmeans_host.h's split_void_clusters and post_process on compact centroids; total: points per cluster, pop: k words of workspace
+void launch_kmeans_dev_split(float* cen, const unsigned long long* total, uint32_t k, int d, uint64_t n, uint32_t* pop, uint32_t* flags,
+                             hipStream_t s);
+void launch_kmeans_dev_post(float* cen, uint32_t k, int d, int spherical, int int_centroids, hipStream_t s);
+// *out = the running fp32 sum of dis[0 .. n) in index order
+void launch_kmeans_dev_objective(const float* dis, uint64_t n, float* out, hipStream_t s);
 // ---------------------------------------------------------------------------- stored vectors back (ivf_reconstruct.hip)
 // table[id - lo] = max(table[id - lo], list << 32 | offset) for every stored entry whose id lies in [lo, lo + n) (nt entries, list_off:
 // nlist + 1); the caller starts the table at -1 in every slot and counts at {0, 0}: counts[0] += entries outside the window,

@@ -883,6 +883,24 @@ int amd_ivf_last_assign(amd_ivf_t* h, uint64_t out[4]);
 int amd_ivf_kmeans_last_assign(uint64_t out[4]);
 
 /* ------------------------------------------------------------------------------------------------
+ * amd_ivf_kmeans with the n training rows taken from device memory: d_x, dtype (0 fp32, 1 fp16), ldx >= d elements and
+ * stream as in the `_dev` calls above; d_centroids k x d floats in device memory; obj niter floats on the host, or NULL.  The same
+ * centroids and objectives, bit for bit, as amd_ivf_kmeans on the same values.  The permutations are drawn on the host (they are
+ * mt19937 by definition) and their first entries uploaded; the finite check over all n rows, sub-sampling, the centroid install,
+ * grouping (a counting sort, no library), the centroid update, void-cluster splitting, post-processing and the objective are
+ * kernels: inside the loop no row, distance, assignment, count or centroid crosses the bus, the host reads 24 bytes an iteration
+ * (the centroids' value range, their norm bound, the error flags) beside what the assignment pass reads of itself.  The handle the
+ * call makes for itself has options "assign_fused" and "assign_wide" on unless the environment sets them to 0.  The work is ordered
+ * behind `stream` and complete on return; amd_ivf_kmeans_last_assign reports the call's counters.  Before any device is touched,
+ * -2 for: a null d_x or d_centroids, d <= 0, k == 0, n < k, n > INT_MAX (the reference's permutation is an int array),
+ * max_points_per_centroid == 0, a dtype outside {0, 1}, ldx < d; after that, -4 without a device.  -2 also for a NaN or an infinity
+ * anywhere in the n rows ("input contains NaN's or Inf's"; d_centroids is then left as it was), for pointers that are not memory of
+ * `device`, and for an assignment outside [0, k). */
+int amd_ivf_kmeans_dev(int d, size_t n, const void* d_x, int dtype, size_t ldx, size_t k, int metric, int niter, long seed,
+                       size_t max_points_per_centroid, int spherical, int int_centroids, int coarse_mode, int device,
+                       float* d_centroids /* device, k x d */, float* obj /* host, niter, may be NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Dataset files of the reference's harness (Auncel/eval/bound.cpp:29-113; host only).  Buffers are malloc'ed
  * here and released with amd_ivf_free.  Where the harness aborts (missing file, size that is not a whole number of rows,
  * short read) these return -2 and amd_ivf_last_error() says why.
